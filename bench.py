@@ -8,6 +8,14 @@ fwd+bwd over the batch; with N > 1 GPUs each rank runs its own 8 clips (weak sca
 the step includes the RCCL gradient all-reduce.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2] [--no-graph]
+                  [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--dump-outputs DIR writes what the last timed step computed (the streams' outputs and every
+parameter's gradient, float32) as DIR/<name>.npy; inputs and weights are seeded, so two
+builds run with the same arguments can be compared array for array.  --full adds the
+measurements that take runs of their own after the timed region: the data-parallel
+all-reduce self-check, the dominant kernel's roofline and the CPU baseline.
 
 --gpus N > 1 without a launcher (WORLD_SIZE unset): this process starts N rank processes of
 the same command (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT in their
@@ -15,7 +23,7 @@ environment, one GPU each) and exits with their status; it never touches the GPU
 Under torch.distributed.run (WORLD_SIZE set) --gpus must agree with WORLD_SIZE.
 SCA_DIST_BACKEND=gloo rehearses N ranks on fewer GPUs (ranks share devices round-robin).
 
-Prints ONE JSON line on rank 0 (contract in the build instructions), including:
+Prints ONE JSON line on rank 0; with --full it includes:
   roofline      the dominant kernel's algorithmic FLOP rate (HIP events around each of its
                 launches in an instrumented eager step after the timed region) vs fp32 MFMA peak
   cpu_baseline  the CPU oracle (plain PyTorch fp32 restatement) timed on this host's cores
@@ -64,7 +72,15 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--dropout", type=float, default=0.0,
                     help="train-mode dropout p for every block (the yaml's 0.2 = the secondary run)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs and gradients as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the all-reduce self-check, the roofline step and the "
+                         "CPU baseline")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def spawn_ranks(n):
@@ -147,10 +163,13 @@ def main(args):
     # rehearsals all-reduce the buckets after the step instead (reducer.sync)
     reducer = GradBuckets(params, world) if use_dp else None
 
+    last_outs = []
+
     def fwd_bwd():
         if args.dropout > 0:
             ops.advance_dropout()  # device-side step counter: fresh masks on every graph replay
         outs = model(kp, mask)
+        last_outs[:] = outs  # what a caller receives (a graph replay refills the same tensors)
         outs = outs[:1] if fusion else outs  # config 3: the loss seed sits on the fusion output
         torch.autograd.backward(outs, grads_out)
 
@@ -229,6 +248,72 @@ def main(args):
     clips = w["B"] * world * args.steps / elapsed
     step_flops = W.flops_per_step(w)
 
+    if args.dump_outputs and rank == 0:  # before anything below runs another step
+        dump_outputs(args.dump_outputs, last_outs, list(model.named_parameters()))
+
+    dp_check = roofline = cpu = None
+    if args.full:
+        dp_check, roofline, cpu = full_extras(args, w, model, params, reducer, graph, fwd_bwd, sync, step, ms,
+                                              step_flops, rank, world, fusion)
+
+    if rank == 0:
+        line = {
+            "metric": "clips/sec fwd+bwd, (B=8,T=256,K=79,d=256) at 1/2/4/8 MI355X",
+            "value": round(clips, 2), "unit": "clips/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(ms, 4), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "fp32", "data": "synthetic (U[0,1) keypoints, MSCA_Net init)",
+            "config": {"workload": f"{args.workload}: " + describe(w), "clips_per_gpu": w["B"], "frames": w["T"],
+                       "joints": w["K_all"], "streams": w["groups"], "d_model": w["d"], "heads": w["H"],
+                       "layers": w["L"], "dropout": args.dropout, "hipgraph": graph is not None,
+                       "parallelism": f"dp{world}", "devices": min(world, max(1, ndev))},
+            "ms_per_step_median": round(ms_median, 4),
+            "full": args.full,
+            "roofline": roofline,
+            "cpu_baseline": cpu,
+        }
+        if reducer is not None:
+            line["config"]["grad_allreduce"] = {
+                "backend": dist.get_backend(), "buckets_mb": [round(b / 2 ** 20, 2) for b in reducer.bucket_sizes()],
+                "overlapped": reducer.overlap, "in_graph": reducer.overlap and graph is not None,
+                "fallback_params": len(reducer.last_fallback)}
+            if dp_check is not None:
+                line["config"]["grad_allreduce"].update(dp_check)
+        print(json.dumps(line), flush=True)
+    if use_dp:
+        reducer.close()
+        dist.destroy_process_group()
+
+
+DUMP_BUDGET_BYTES = 48 * 2 ** 20  # all files of one --dump-outputs together (float32)
+
+
+def dump_outputs(dirpath, outs, named_params):
+    """The last timed step's results as <dirpath>/<name>.npy, float32: out<g> = the g-th tensor
+    the model returned, grad.<parameter name> = that parameter's gradient.  Arrays that would
+    take the files past DUMP_BUDGET_BYTES together are written as a sample: every array gets
+    an equal share of the budget, and a larger one keeps the elements (of the flattened array,
+    in index order) at positions drawn without replacement from a generator seeded by the
+    array's name and size — the same positions in every run and every build."""
+    import zlib
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    arrays = [(f"out{g}", o.detach()) for g, o in enumerate(outs) if torch.is_tensor(o)]
+    arrays += [(f"grad.{n}", p.grad.detach()) for n, p in named_params if p.grad is not None]
+    share = DUMP_BUDGET_BYTES // 4 // max(1, len(arrays))
+    if sum(t.numel() for _, t in arrays) * 4 <= DUMP_BUDGET_BYTES:
+        share = max(share, max(t.numel() for _, t in arrays))
+    for name, t in arrays:
+        t = t.float()
+        if t.numel() > share:
+            rng = np.random.default_rng([zlib.crc32(name.encode()), t.numel()])
+            idx = np.sort(rng.choice(t.numel(), size=share, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(dirpath, name + ".npy"), t.cpu().numpy())
+
+
+def full_extras(args, w, model, params, reducer, graph, fwd_bwd, sync, step, ms, step_flops, rank, world, fusion):
+    """--full: what the benchmark measures beside its headline figure, each in runs of its own
+    after the timed region.  Returns (all-reduce self-check, roofline, CPU baseline)."""
     # ---- data parallel: the averaged buckets checked once against an eager gather-and-mean ----
     dp_check = None
     if reducer is not None and reducer.collective and args.dropout == 0:
@@ -269,32 +354,7 @@ def main(args):
     cpu = None
     if rank == 0 and world == 1 and not args.no_cpu_baseline and not fusion and args.dropout == 0:
         cpu = cpu_baseline(w, model, args.cpu_seconds)
-
-    if rank == 0:
-        line = {
-            "metric": "clips/sec fwd+bwd, (B=8,T=256,K=79,d=256) at 1/2/4/8 MI355X",
-            "value": round(clips, 2), "unit": "clips/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms, 4), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "fp32", "data": "synthetic (U[0,1) keypoints, MSCA_Net init)",
-            "config": {"workload": f"{args.workload}: " + describe(w), "clips_per_gpu": w["B"], "frames": w["T"],
-                       "joints": w["K_all"], "streams": w["groups"], "d_model": w["d"], "heads": w["H"],
-                       "layers": w["L"], "dropout": args.dropout, "hipgraph": graph is not None,
-                       "parallelism": f"dp{world}", "devices": min(world, max(1, ndev))},
-            "ms_per_step_median": round(ms_median, 4),
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-        }
-        if reducer is not None:
-            line["config"]["grad_allreduce"] = {
-                "backend": dist.get_backend(), "buckets_mb": [round(b / 2 ** 20, 2) for b in reducer.bucket_sizes()],
-                "overlapped": reducer.overlap, "in_graph": reducer.overlap and graph is not None,
-                "fallback_params": len(reducer.last_fallback)}
-            if dp_check is not None:
-                line["config"]["grad_allreduce"].update(dp_check)
-        print(json.dumps(line), flush=True)
-    if use_dp:
-        reducer.close()
-        dist.destroy_process_group()
+    return dp_check, roofline, cpu
 
 
 def check_allreduce(reducer, graph, fwd_bwd, sync, params):

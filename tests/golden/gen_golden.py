@@ -35,6 +35,9 @@ from model.layers import CoordinateMapping  # noqa: E402
 from model.residual import ResidualNetwork  # noqa: E402
 from model.utils import create_attention_mask, create_causal_attention_mask  # noqa: E402
 
+sys.path.insert(0, os.path.dirname(HERE))
+from golden_util import save_parts  # noqa: E402
+
 
 def lengths_for(B, T):
     base = [T, max(T - 37, 1) if T > 40 else max(T - 5, 1), T // 2, 1, 0]
@@ -85,7 +88,7 @@ def capture(name, module, inputs, call, meta, grad_inputs=()):
     for k, p in module.named_parameters():
         if p.grad is not None:
             arrs["grad.param." + k] = p.grad.numpy()
-    np.savez_compressed(os.path.join(HERE, name + ".npz"), **arrs)
+    save_parts(name, arrs, HERE)  # <name>.npz (+ <name>.partN.npz: no committed file over 1 MiB)
     meta = dict(meta)
     meta["out_shape"] = list(out.shape)
     return name, meta

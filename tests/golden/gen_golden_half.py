@@ -15,7 +15,6 @@ import json
 import os
 import sys
 
-import numpy as np
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -41,7 +40,7 @@ def capture(name, module, inputs, call, meta, grad_inputs=()):
     arrs["out"], arrs["gout"] = np_(out), Gout.numpy()
     arrs.update({"grad.in." + k: np_(inputs[k].grad) for k in grad_inputs})
     arrs.update({"grad.param." + k: np_(p.grad) for k, p in module.named_parameters() if p.grad is not None})
-    np.savez_compressed(os.path.join(HERE, name + ".npz"), **arrs)
+    G.save_parts(name, arrs, HERE)
     return name, dict(meta, out_shape=list(out.shape), dtype=str(out.dtype))
 
 

@@ -13,10 +13,43 @@ def manifest(fname="manifest.json"):
         return json.load(f)
 
 
+PART_BYTES = 900 * 1024  # array bytes per file: every committed fixture file stays under 1 MiB
+
+
+def save_parts(name, arrs, directory=GOLDEN):
+    """Write the arrays of one fixture as <name>.npz and, when they do not fit in PART_BYTES,
+    the rest as <name>.part2.npz, <name>.part3.npz, ... (keys in order, each array whole)."""
+    parts, size = [{}], 0
+    for k, v in arrs.items():
+        v = np.asarray(v)
+        if parts[-1] and size + v.nbytes > PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][k] = v
+        size += v.nbytes
+    for i, part in enumerate(parts):
+        np.savez_compressed(os.path.join(directory, name + (f".part{i + 1}" if i else "") + ".npz"), **part)
+    return len(parts)
+
+
+def load_arrays(name):
+    """Every array of fixture `name`, from <name>.npz and its .partN.npz continuations."""
+    z, i = {}, 1
+    path = os.path.join(GOLDEN, name + ".npz")
+    while os.path.exists(path):
+        with np.load(path) as f:  # allow_pickle=False (default)
+            z.update({k: f[k] for k in f.files})
+        i += 1
+        path = os.path.join(GOLDEN, f"{name}.part{i}.npz")
+    if not z:
+        raise FileNotFoundError(os.path.join(GOLDEN, name + ".npz"))
+    return z
+
+
 def load(name, manifest_name="manifest.json"):
-    z = np.load(os.path.join(GOLDEN, name + ".npz"))  # allow_pickle=False (default)
+    z = load_arrays(name)
     fx = {"in": {}, "param": {}, "grad_in": {}, "grad_param": {}}
-    for k in z.files:
+    for k in z:
         v = torch.from_numpy(z[k].copy())
         if k.startswith("in."):
             fx["in"][k[3:]] = v

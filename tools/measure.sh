@@ -15,14 +15,14 @@ if [ "$1" = tests ]; then
     > $out/gpu_tests.log 2>&1; rc=$?; tail -3 $out/gpu_tests.log; [ $rc -eq 0 ] || exit $rc
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.txt 2>&1 || exit $?
   tail -1 $out/smoke.txt
-  timeout -k 10 400 python bench.py > $out/bench_default.log 2>&1 || exit $?
+  timeout -k 10 400 python bench.py --full > $out/bench_default.log 2>&1 || exit $?
   grep '"metric"' $out/bench_default.log > $out/bench_default.json
   for wl in cfg3 cfg5; do
     st=20; [ $wl = cfg5 ] && st=10
-    timeout -k 10 400 python bench.py --workload $wl --steps $st --no-cpu-baseline > $out/bench_$wl.log 2>&1 || exit $?
+    timeout -k 10 400 python bench.py --full --workload $wl --steps $st --no-cpu-baseline > $out/bench_$wl.log 2>&1 || exit $?
     grep '"metric"' $out/bench_$wl.log > $out/bench_$wl.json
   done
-  timeout -k 10 300 python bench.py --dropout 0.2 --steps 40 --no-cpu-baseline > $out/bench_dropout.log 2>&1 || exit $?
+  timeout -k 10 300 python bench.py --full --dropout 0.2 --steps 40 --no-cpu-baseline > $out/bench_dropout.log 2>&1 || exit $?
   grep '"metric"' $out/bench_dropout.log > $out/bench_dropout.json
   for f in $out/bench_*.json; do echo "$f $(grep -o '"value": [0-9.]*' $f)"; done
 fi

@@ -11,5 +11,5 @@ rc=$?; echo "pytest rc=$rc"; tail -15 $out/gpu_tests.log
 ok $rc || exit $rc
 timeout -k 10 300 python bench.py --no-cpu-baseline > $out/bench.log 2>&1 || { tail -20 $out/bench.log; exit 1; }
 grep '"metric"' $out/bench.log | cut -c1-400
-SCA_DIST_BACKEND=gloo timeout -k 10 300 python bench.py --gpus 2 --steps 10 --no-cpu-baseline > $out/bench_gpus2_gloo.log 2>&1 || { tail -20 $out/bench_gpus2_gloo.log; exit 1; }
+SCA_DIST_BACKEND=gloo timeout -k 10 300 python bench.py --full --gpus 2 --steps 10 --no-cpu-baseline > $out/bench_gpus2_gloo.log 2>&1 || { tail -20 $out/bench_gpus2_gloo.log; exit 1; }
 grep -o '"grad_allreduce": {[^}]*}' $out/bench_gpus2_gloo.log
