@@ -37,6 +37,10 @@
  *   sca_clamp              RecognitionHead logit clamp(+-50) (model/__init__.py:54-58)
  *   sca_lstm_cell_fwd/bwd  AlignmentModule's bidirectional nn.LSTM cell
  *                          (model/alignment_module.py:24-30, :68-69)
+ *   sca_optim_grad_sqnorm  torch.nn.utils.clip_grad_norm_(model.parameters(), 1.0)
+ *   sca_optim_scale_grads  (opt.py:34) and the NaN-loss test of opt.py:32
+ *   sca_optim_adam_step    optimizer.step() (opt.py:35) of the torch.optim.Adam built by
+ *                          optimizer.py:49-66, one parameter group per model child
  */
 #ifndef SCATTEN_H
 #define SCATTEN_H
@@ -570,6 +574,74 @@ int sca_lstm_cell_fwd(const float* gates, float* act, float* c, float* y, float*
                       int step, void* stream);
 int sca_lstm_cell_bwd(const float* dh, const float* dy, const float* act, const float* c, float* dc, float* dg,
                       int B, int T, int H, int ndir, int step, void* stream);
+
+/* ---- training update: gradient clip + Adam over every parameter tensor in two launches ----
+ * Replaces clip_grad_norm_(model.parameters(), max_norm) + optimizer.step() (opt.py:34-35)
+ * for the torch.optim.Adam of optimizer.py:49-66, and the NaN-loss skip of opt.py:32-37
+ * without its host sync.  The kernels read four tables in DEVICE memory:
+ *   tensors  one entry per parameter tensor that has a gradient
+ *   chunks   the tensors cut into pieces of a fixed size (the last piece of a tensor may be
+ *            shorter; no piece spans two tensors); workgroups stride over this list
+ *   groups   the hyper-parameters of each parameter group (doubles, as torch keeps them)
+ *   state    step counter, skip flag, and the last step's gradient norm and clip coefficient
+ * partials: workspace of sca_optim_blocks(max_blocks, nchunks) floats, written by
+ * sca_optim_grad_sqnorm and read by the launch that follows it with the same nchunks and
+ * max_blocks (0: the default grid cap, 8 workgroups per CU).  Sums run in a fixed order with
+ * no atomics: results are bitwise reproducible for a given table and max_blocks.          */
+typedef struct {
+  float* p;                /* parameter, numel floats                                      */
+  float* g;                /* its gradient (read; scaled in place by sca_optim_scale_grads) */
+  float* exp_avg;          /* first moment                                                 */
+  float* exp_avg_sq;       /* second moment                                                */
+  float* max_exp_avg_sq;   /* amsgrad: running maximum of the second moment, else NULL     */
+  long numel;
+  int group;               /* index into the group table                                   */
+  int t0;                  /* state.step before this tensor's first update: its own step
+                              (torch keeps one per parameter) is state.step - t0           */
+} sca_optim_tensor;
+
+typedef struct {
+  int tensor;              /* index into the tensor table                                  */
+  int len;                 /* elements in this chunk                                       */
+  long offset;             /* first element, from the tensor's base                        */
+} sca_optim_chunk;
+
+typedef struct {
+  double lr, beta1, beta2, eps, weight_decay;
+} sca_optim_group;
+
+typedef struct {
+  int step;                /* updates applied so far                                       */
+  int skipped;             /* 1 when the last call saw a non-finite loss                   */
+  float grad_norm;         /* total 2-norm of the last call's gradients, before clipping   */
+  float clip_coef;         /* min(1, max_norm / (grad_norm + 1e-6)); 1 with clipping off   */
+} sca_optim_state;
+
+int sca_optim_blocks(int max_blocks, int nchunks);
+/* Pass 1: partials[w] = workgroup w's sum of g^2; workgroup 0 also reads *loss (device
+ * scalar, or NULL), sets state.skipped = !isfinite(loss) and increments state.step when not
+ * skipped.                                                                                */
+int sca_optim_grad_sqnorm(const sca_optim_tensor* tensors, const sca_optim_chunk* chunks, int nchunks,
+                          int max_blocks, const float* loss, sca_optim_state* state, float* partials,
+                          void* stream);
+/* Pass 2: grad_norm = sqrt(sum partials), clip_coef (max_norm <= 0: clipping off) stored in
+ * state; unless state.skipped, per element with t = state.step - t0 (torch.optim.Adam with
+ * L2 weight decay, optional amsgrad through max_exp_avg_sq):
+ *   g' = clip_coef g + wd p ; m += (1 - b1)(g' - m) ; v = b2 v + (1 - b2) g'^2
+ *   p -= lr / (1 - b1^t) * m / (sqrt(amsgrad ? vmax = max(vmax, v) : v) / sqrt(1 - b2^t) + eps)
+ * The gradient is not written.                                                            */
+int sca_optim_adam_step(const sca_optim_tensor* tensors, const sca_optim_chunk* chunks, int nchunks,
+                        const sca_optim_group* groups, int max_blocks, float max_norm, sca_optim_state* state,
+                        const float* partials, void* stream);
+/* After pass 1: g *= clip_coef in place (stand-alone clip_grad_norm_); stores grad_norm and
+ * clip_coef in state.                                                                     */
+int sca_optim_scale_grads(const sca_optim_tensor* tensors, const sca_optim_chunk* chunks, int nchunks,
+                          int max_blocks, float max_norm, sca_optim_state* state, const float* partials,
+                          void* stream);
+/* Asynchronous host-to-device copy of a table on `stream` (a memcpy node under capture).
+ * src must be pinned host memory that is left unmodified and alive for as long as a graph
+ * holding the copy can be replayed.                                                       */
+int sca_optim_upload(void* dst, const void* src, long bytes, void* stream);
 
 const char* sca_last_error(void);
 int sca_version(void);

@@ -121,6 +121,24 @@ class CoordMapBwdProblem(ctypes.Structure):
                 ("partial", c_void_p)]
 
 
+class OptimTensor(ctypes.Structure):
+    _fields_ = [("p", c_void_p), ("g", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p),
+                ("max_exp_avg_sq", c_void_p), ("numel", c_long), ("group", c_int), ("t0", c_int)]
+
+
+class OptimChunk(ctypes.Structure):
+    _fields_ = [("tensor", c_int), ("len", c_int), ("offset", c_long)]
+
+
+class OptimGroup(ctypes.Structure):
+    _fields_ = [("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double),
+                ("eps", ctypes.c_double), ("weight_decay", ctypes.c_double)]
+
+
+class OptimState(ctypes.Structure):
+    _fields_ = [("step", c_int), ("skipped", c_int), ("grad_norm", c_float), ("clip_coef", c_float)]
+
+
 EXPORTS = {
     "sca_gemm": ([c_int, c_int, c_void_p, c_int, c_void_p, c_void_p], c_int),
     "sca_gemm_partial": ([c_int, c_int, c_void_p, c_int, c_void_p, c_void_p], c_int),
@@ -170,6 +188,12 @@ EXPORTS = {
     "sca_clamp": ([c_void_p] * 4 + [c_long, c_float, c_float, c_void_p], c_int),
     "sca_lstm_cell_fwd": ([c_void_p] * 5 + [c_int] * 5 + [c_void_p], c_int),
     "sca_lstm_cell_bwd": ([c_void_p] * 6 + [c_int] * 5 + [c_void_p], c_int),
+    "sca_optim_blocks": ([c_int, c_int], c_int),
+    "sca_optim_grad_sqnorm": ([c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
+    "sca_optim_adam_step": ([c_void_p, c_void_p, c_int, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p],
+                            c_int),
+    "sca_optim_scale_grads": ([c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p], c_int),
+    "sca_optim_upload": ([c_void_p, c_void_p, c_long, c_void_p], c_int),
     "sca_last_error": ([], ctypes.c_char_p),
     "sca_version": ([], c_int),
     "sca_build_digest": ([], ctypes.c_char_p),
