@@ -767,15 +767,31 @@ constexpr int TNK_PLD = 68;  // partial-tile row stride (floats): 16-B shift per
 // 48-KB ring and three workgroups share a CU (the one-round form took 70 KB: two per CU)
 constexpr int TNK_RED = 2 * 64 * TNK_PLD * 4 + 4 * 64 * 4;
 
-// SUB: K slices per ring stage (one wait + barrier per SUB x 32 k rows).  REG: the operand
-// stream of gemm_tnb_kernel instead of the LDS-DMA ring — 64 k rows per iteration (wave w
-// takes rows 16w .. 16w+15), the next iteration's pieces register-staged (4 + 4 float4 per
-// thread), loads / stores / fragment reads interleaved with the MFMAs; one segment, K % 64 == 0
+// REG form's LDS allocation: only the reduction uses it (TNK_RED, 35.8 KB), padded to the 48 KB
+// of the ring it replaced — at its natural size it sits beside a 113-KB gemm_lnb workgroup
+// and the step is 0.2 % slower
+constexpr int TNK_REG_SMEM = 48 * 1024;
+static_assert(TNK_REG_SMEM >= TNK_RED, "the reduction's two partial tiles and bias rows");
+
+// one buffer load per M MFMAs, R rounds (masks as ilv_store)
+template <int I, int R, int M>
+__device__ __forceinline__ void ilv_load() {
+  if constexpr (I < R) {
+    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+    __builtin_amdgcn_sched_group_barrier(0x008, M, 0);
+    ilv_load<I + 1, R, M>();
+  }
+}
+
+// SUB: K slices per ring stage (one wait + barrier per SUB x 32 k rows).  REG: no ring — 64 k
+// rows per iteration (wave w takes rows 16w .. 16w+15), every lane loading its own operand
+// float4s from global memory into registers one iteration ahead, the loads interleaved
+// with the MFMAs; the main loop has no LDS access and no barrier; one segment, K % 64 == 0
 template <int S, int SUB, bool REG = false>
-__global__ __launch_bounds__(256) void gemm_tnk_kernel(const GemmArgs args) {
+__global__ __launch_bounds__(256, REG ? 3 : 1) void gemm_tnk_kernel(const GemmArgs args) {
   constexpr int SLICE = 2 * GL_OP_BYTES;
   constexpr int STAGE = SUB * SLICE;
-  constexpr int SMEM = S * STAGE > TNK_RED ? S * STAGE : TNK_RED;
+  constexpr int SMEM = REG ? TNK_REG_SMEM : S * STAGE > TNK_RED ? S * STAGE : TNK_RED;
   __shared__ __attribute__((aligned(1024))) char smem[SMEM];
 
   const unsigned gx = gridDim.x, gy = gridDim.y;
@@ -880,73 +896,57 @@ __global__ __launch_bounds__(256) void gemm_tnk_kernel(const GemmArgs args) {
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(G.A), 0, (int)(((long)(K - 1) * G.lda + P.M) * 4), 0x00020000);
     const __amdgpu_buffer_rsrc_t rb =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(G.B), 0, (int)(((long)(K - 1) * G.ldb + P.N) * 4), 0x00020000);
-    // thread's pieces j < 4: k row (tid >> 4) + 16j of the iteration, columns 4 (tid & 15) .. +3
-    const int tid = threadIdx.x, srow = tid >> 4, scol = 4 * (tid & 15);
-    const int va = (int)(((long)(kbeg + srow) * G.lda + min(m0 + scol, P.M - 4)) * 4);
-    const int vb = (int)(((long)(kbeg + srow) * G.ldb + min(n0 + scol, P.N - 4)) * 4);
-    const int rowA = 16 * G.lda * 4, rowB = 16 * G.ldb * 4, itA = TB_BK * G.lda * 4, itB = TB_BK * G.ldb * 4;
-    float* As = reinterpret_cast<float*>(smem);  // [64 k][64 m], then [64 k][64 n]
-    float* Bs = As + TB_BK * GL_BM;
-    f32x4 st[8];
-    auto load = [&](int it) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        st[j] = tb_load(ra, va, it * itA + j * rowA);
-        st[4 + j] = tb_load(rb, vb, it * itB + j * rowB);
-      }
-    };
-    auto store = [&]() {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        st4(As + (srow + 16 * j) * GL_BM + scol, st[j]);
-        st4(Bs + (srow + 16 * j) * GL_BN + scol, st[4 + j]);
-      }
-    };
-    auto iter = [&](auto wr_c, auto ld_c, int it) {
-      constexpr bool WR = decltype(wr_c)::value, LD = decltype(ld_c)::value;
-      f32x4 a[4], b[4];
+    // lane (g, c) of wave w owns the operand rows it multiplies: k row 16w + 4n + g (n < 4) of
+    // the iteration, columns 4c .. 4c+3 of A and of B — no other wave reads them, so they go
+    // from global memory straight into the MFMA operand registers: no LDS, no barrier.  One
+    // load instruction covers 4 k rows x 256 contiguous bytes.  The next iteration's operands
+    // are in flight while this one's are multiplied: two register sets, swapped by unrolling
+    const int krow = kbeg + 16 * wave + g;
+    const int va = (int)(((long)krow * G.lda + min(m0 + 4 * c, P.M - 4)) * 4);
+    const int vb = (int)(((long)krow * G.ldb + min(n0 + 4 * c, P.N - 4)) * 4);
+    const int rowA = 4 * G.lda * 4, rowB = 4 * G.ldb * 4, itA = TB_BK * G.lda * 4, itB = TB_BK * G.ldb * 4;
+    f32x4 oa[2][4], ob[2][4];
+    // the iteration past the last one re-reads the last: every step issues its loads, so the
+    // loop body has no branch around a load and the compiler's s_waitcnt stay counted ones
+    auto load = [&](auto s_c, int it) {
+      constexpr int s = decltype(s_c)::value;
+      it = min(it, nit - 1);
 #pragma unroll
       for (int n = 0; n < 4; ++n) {
-        const int k = 16 * wave + 4 * n + g;
-        a[n] = ld4(As + k * GL_BM + 4 * c);
-        b[n] = ld4(Bs + k * GL_BN + 4 * c);
+        oa[s][n] = tb_load(ra, va, it * itA + n * rowA);
+        ob[s][n] = tb_load(rb, vb, it * itB + n * rowB);
       }
+    };
+    auto step = [&](auto s_c, int it) {
+      constexpr int s = decltype(s_c)::value;
+      load(std::integral_constant<int, s ^ 1>{}, it + 1);
 #pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = mfma16(a[0][i], b[0][j], acc[i][j]);
-      ilv_read<0, 2, 4, 8>();
-      __builtin_amdgcn_sched_barrier(0);
-      __syncthreads();
-      __builtin_amdgcn_sched_barrier(0);
-      if constexpr (WR) {
-        store();
-        if constexpr (LD) load(it + 2);
-      }
-#pragma unroll
-      for (int n = 1; n < 4; ++n)
+      for (int n = 0; n < 4; ++n) {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
-          for (int j = 0; j < 4; ++j) acc[i][j] = mfma16(a[n][i], b[n][j], acc[i][j]);
-      if constexpr (WR) ilv_store<0, 8, 1, 6>();
-      if (do_bias) {
-#pragma unroll
-        for (int n = 0; n < 4; ++n) bs4 += a[n];
+          for (int j = 0; j < 4; ++j) acc[i][j] = mfma16(oa[s][n][i], ob[s][n][j], acc[i][j]);
+        bs4 += oa[s][n];  // used only where do_bias; summed everywhere to keep the loop branch-free
       }
-      __syncthreads();
+      ilv_load<0, 8, 8>();
+      __builtin_amdgcn_sched_barrier(0);
     };
     if (nit > 0) {
-      load(0);
-      store();
-      if (nit > 1) load(1);
-      __syncthreads();
-    }
-    int it = 0;
+      // an odd count takes its first iteration out of set 1, so the loop always runs whole
+      // pairs and both ways into it have set 0's eight loads in flight
+      int it = nit & 1;
+      if (it) {
+        load(std::integral_constant<int, 1>{}, 0);
+        step(std::integral_constant<int, 1>{}, 0);
+      } else {
+        load(std::integral_constant<int, 0>{}, 0);
+      }
 #pragma unroll 1
-    for (; it + 2 < nit; ++it) iter(std::true_type{}, std::true_type{}, it);
-    if (it + 1 < nit) iter(std::true_type{}, std::false_type{}, it++);
-    if (it < nit) iter(std::false_type{}, std::false_type{}, it);
+      for (; it < nit; it += 2) {
+        step(std::integral_constant<int, 0>{}, it);
+        step(std::integral_constant<int, 1>{}, it + 1);
+      }
+    }
   } else {
 #pragma unroll
   for (int i = 0; i < S - 1; ++i)
@@ -1911,7 +1911,9 @@ __global__ __launch_bounds__(LgCfg<BM>::NW * 64) void gemm_ln_kernel(const GemmL
     }
   }
   // REG chained passes: iteration u = 64 k rows of pass pass_of(u >> 2); thread's pieces j < 8:
-  // B rows (tid >> 4) + 32j, k 4 (tid & 15) .. +3 — the first one loaded under the LayerNorm
+  // B rows 32 wave + (lane >> 4) + 4j, k 4 (lane & 15) .. +3 — the rows this wave's MFMAs read
+  // and no other's, so the passes need no workgroup barrier; the first one loaded under the
+  // LayerNorm
   const int nit2 = CH && REG ? 4 * LN.npass : 0;
   f32x4 st2[8];
   auto load2 = [&](int u) {
@@ -1923,13 +1925,13 @@ __global__ __launch_bounds__(LgCfg<BM>::NW * 64) void gemm_ln_kernel(const GemmL
     const int t = threadIdx.x;
 #pragma unroll
     for (int j = 0; j < 8; ++j)
-      st2[j] = tb_load(rb, (((t >> 4) + 32 * j) * Q.ldb + 4 * (t & 15)) * 4, (u & 3) * 256);
+      st2[j] = tb_load(rb, ((32 * (t >> 6) + ((t & 63) >> 4) + 4 * j) * Q.ldb + 4 * (t & 15)) * 4, (u & 3) * 256);
   };
   auto store2 = [&]() {
     float* Bi = reinterpret_cast<float*>(smem);
     const int t = threadIdx.x;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) st4(Bi + ((t >> 4) + 32 * j) * 68 + 4 * (t & 15), st2[j]);
+    for (int j = 0; j < 8; ++j) st4(Bi + (32 * (t >> 6) + ((t & 63) >> 4) + 4 * j) * 68 + 4 * (t & 15), st2[j]);
   };
   if constexpr (CH && REG) {
     if (nit2 > 0) load2(0);
@@ -2046,7 +2048,10 @@ __global__ __launch_bounds__(LgCfg<BM>::NW * 64) void gemm_ln_kernel(const GemmL
       steps(0, 4);
       ilv_read<0, 4, 4, 4>();
       __builtin_amdgcn_sched_barrier(0);
-      __syncthreads();  // every wave has read the B image
+      // this wave has read its rows of the B image (no other wave reads or writes them)
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       __builtin_amdgcn_sched_barrier(0);
       if constexpr (WR) {
         store2();
@@ -2079,7 +2084,10 @@ __global__ __launch_bounds__(LgCfg<BM>::NW * 64) void gemm_ln_kernel(const GemmL
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       }
-      __syncthreads();  // the next B tile is in LDS
+      // this wave's rows of the next B tile are in LDS
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     };
     int u = 0;
 #pragma unroll 1
