@@ -41,6 +41,10 @@
  *   sca_optim_scale_grads  (opt.py:34) and the NaN-loss test of opt.py:32
  *   sca_optim_adam_step    optimizer.step() (opt.py:35) of the torch.optim.Adam built by
  *                          optimizer.py:49-66, one parameter group per model child
+ *   sca_ctc_greedy_decode  utils.ctc_decode (utils.py:164-189: tf.nn.ctc_beam_search_decoder
+ *   sca_ctc_beam_decode    on the host) as evaluate_fn calls it (opt.py:84-89)
+ *   sca_wer_counts         metrics.wer_single / edit_distance / get_alignment
+ *                          (metrics.py:2793-2907)
  */
 #ifndef SCATTEN_H
 #define SCATTEN_H
@@ -544,6 +548,51 @@ int sca_ctc_loss_fwd(const float* logits, const int* labels, const int* in_len, 
                      int C, int S, float* nll, float* loss, float* ws, void* stream);
 int sca_ctc_loss_bwd(const float* logits, const int* labels, const int* in_len, const int* tgt_len, int B, int T,
                      int C, int S, const float* dloss, const float* ws, float* dlogits, void* stream);
+
+/* ---- evaluation: CTC decoding and WER counts (opt.py:50-128) ----------------------------
+ * Decoders over the same batch-major fp32 logits (B, T, C); blank = class 0 (the reference's
+ * column rotation and "+ 1", utils.py:168-183, cancel: ids are the model's class indices).
+ * in_len (B) int32 device, clamped in-kernel to [0, T].  tokens (B, T) int32 padded with 0,
+ * out_len (B) int32, score (B) fp32.  ws: sca_ctc_decode_workspace_bytes(B, T, C, W) bytes
+ * (0 for unsupported sizes; the greedy decoder needs W = 1), 8-byte aligned.
+ *
+ * sca_ctc_greedy_decode: per frame the arg-max over C (ties to the lowest class), repeats
+ * collapsed, blanks dropped; score = the sum of the arg-max log-probabilities.
+ *
+ * sca_ctc_beam_decode: CTC prefix beam search in log space, the algorithm of
+ * tf.nn.ctc_beam_search_decoder (utils.py:172-177) with top_paths = 1 and no label merging
+ * inside the search; 1 <= beam_width <= 32, C <= 8192.  A beam is a label prefix with
+ * lb (ends in blank), ll (ends in its last label), total = logaddexp(lb, ll); start: the
+ * empty prefix with lb = 0, ll = -inf.  Frame t < in_len[b], lp = log_softmax(logits[b, t]):
+ *   every active beam p with last label e:  lb' = total + lp[0];  ll' = ll + lp[e] (-inf for
+ *     the empty prefix);  if p's parent prefix q is an active beam, ll' = logaddexp(ll',
+ *     lp[e] + (e == last(q) ? lb_q : total_q))
+ *   every active beam q and label c != 0 whose prefix q + c is not an active beam is a
+ *     candidate with lb = -inf, ll = lp[c] + (c == last(q) ? lb_q : total_q); candidates at
+ *     -inf are dropped
+ *   the new beams are the beam_width best of both sets by total; ties: updated beams before
+ *     candidates, then the lower beam slot, then the lower class.
+ * The result is the best beam by total after the last frame (ties to the lower slot); score
+ * is its total; in_len = 0 gives the empty hypothesis with score 0.  collapse_repeats != 0
+ * merges adjacent equal labels of the result (the groupby of utils.py:185-188, which
+ * collapses genuine repeats too).                                                          */
+#define SCA_CTC_MAX_BEAM 32
+long sca_ctc_decode_workspace_bytes(int B, int T, int C, int W);
+int sca_ctc_greedy_decode(const float* logits, const int* in_len, int B, int T, int C, int* tokens, int* out_len,
+                          float* score, void* ws, void* stream);
+int sca_ctc_beam_decode(const float* logits, const int* in_len, int B, int T, int C, int beam_width,
+                        int collapse_repeats, int* tokens, int* out_len, float* score, void* ws, void* stream);
+
+/* counts (N, 4) int32 = (num_del, num_ins, num_sub, num_ref) of metrics.wer_single
+ * (metrics.py:2793-2907) per pair of ref (N, Rmax) / hyp (N, Hmax) int32 token rows, padded,
+ * with lengths (N) int32 clamped in-kernel to [0, Rmax] / [0, Hmax]; Rmax, Hmax <= 128.
+ * The matrix of metrics.edit_distance (del 3, ins 3, sub 4; equal tokens copy the diagonal
+ * cell) and the back-trace of metrics.get_alignment (correct, substitution, insertion,
+ * deletion, in this order of preference).  Cells are 16-bit: the wrap of the reference's
+ * uint8 matrix once 3 (R + H) > 255 is not reproduced.                                     */
+#define SCA_WER_MAX_LEN 128
+int sca_wer_counts(const int* ref, const int* ref_len, const int* hyp, const int* hyp_len, int N, int Rmax,
+                   int Hmax, int* counts, void* stream);
 
 /* SeqKD over R rows of C logits (student, teacher): columns [start, C) only (use_blank=False
  * -> start 1), temperature temp:

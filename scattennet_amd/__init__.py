@@ -15,6 +15,8 @@ from .residual import ResidualBlock, ResidualNetwork  # noqa: F401
 from .data import JointParts, collate_keypoints, normalize_keypoints  # noqa: F401
 from .alignment import AlignmentModule  # noqa: F401
 from .heads import RecognitionHead, SeqKD, compute_loss, distillation_loss  # noqa: F401
+from .decode import (ctc_decode, ctc_decode_device, ctc_greedy_decode_device, decode_outputs, wer_counts,  # noqa: F401
+                     wer_from_counts)
 from .optim import FusedAdam, WarmupCosineAnnealingScheduler, build_optimizer, clip_grad_norm_  # noqa: F401
 from . import library  # noqa: F401  (torch.ops.scatten.*)
 from .utils import KeyPaddingMask, create_attention_mask, create_causal_attention_mask, key_padding_mask  # noqa: F401

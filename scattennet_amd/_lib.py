@@ -188,6 +188,10 @@ EXPORTS = {
     "sca_clamp": ([c_void_p] * 4 + [c_long, c_float, c_float, c_void_p], c_int),
     "sca_lstm_cell_fwd": ([c_void_p] * 5 + [c_int] * 5 + [c_void_p], c_int),
     "sca_lstm_cell_bwd": ([c_void_p] * 6 + [c_int] * 5 + [c_void_p], c_int),
+    "sca_ctc_decode_workspace_bytes": ([c_int] * 4, c_long),
+    "sca_ctc_greedy_decode": ([c_void_p, c_void_p] + [c_int] * 3 + [c_void_p] * 5, c_int),
+    "sca_ctc_beam_decode": ([c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 5, c_int),
+    "sca_wer_counts": ([c_void_p] * 4 + [c_int] * 3 + [c_void_p, c_void_p], c_int),
     "sca_optim_blocks": ([c_int, c_int], c_int),
     "sca_optim_grad_sqnorm": ([c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
     "sca_optim_adam_step": ([c_void_p, c_void_p, c_int, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p],

@@ -102,6 +102,11 @@ __host__ __device__ __forceinline__ uint32_t sca_mix32(uint32_t x) {
 
 extern "C" const unsigned long long* sca_drop_offset_ptr(void);
 
+// heads.hip: one wave per row of C logits, rowstat[2 row] = max, rowstat[2 row + 1] =
+// log(sum exp(x - max)); the CTC loss and the CTC decoders (decode.hip) share it
+__attribute__((visibility("hidden"))) void sca_ctc_rowstat_launch(const float* x, float* rowstat, long rows, int C,
+                                                                  hipStream_t st);
+
 struct DropMask {
   uint32_t key, thr;
   float scale;

@@ -1,0 +1,512 @@
+// Evaluation path of the reference's evaluate_fn (opt.py:50-128) on the device:
+//   * CTC decoding of the recognition-head logits: best path (greedy) and prefix beam search,
+//     the algorithm of tf.nn.ctc_beam_search_decoder (utils.py:164-189, top_paths = 1, no
+//     label merging inside the search), in log space.  Blank = class 0: the reference's
+//     column rotation and its "+ 1" cancel, so output ids are the model's class indices.
+//   * WER counts (metrics.py:2793-2907): the weighted edit-distance matrix (del 3, ins 3,
+//     sub 4; on equal tokens the cell IS the diagonal value, not a minimum) and the
+//     back-trace in the reference's order of preference (correct, substitution, insertion,
+//     deletion).  The reference keeps the matrix in uint8, which wraps once 3 (R + H) > 255;
+//     here the cells are 16-bit (3 * 256 = 768 at most), so that defect is NOT reproduced.
+// The T frames of a clip are a dependent chain (like the alpha recursion of the CTC loss),
+// so a clip is one workgroup; everything that does not depend on the beam (row normaliser,
+// the W + 1 best classes of every frame) is computed beforehand by row-parallel launches.
+// No float atomics; every sum runs in a fixed order: results are deterministic.
+#include "common.h"
+#include "../../include/scatten.h"
+
+extern "C" void sca_set_error(const char* msg);
+
+namespace {
+
+constexpr float NEG_INF = -__builtin_huge_valf();
+constexpr int NONE = 0x7fffffff;
+constexpr int DEC_MAX_W = SCA_CTC_MAX_BEAM;
+constexpr int DEC_MAX_ITEMS = DEC_MAX_W * (DEC_MAX_W + 1) + DEC_MAX_W;  // candidates + updated beams
+constexpr int KEY_CAND = 64;                                             // keys below: updated beams
+constexpr int DEC_ARENA_LDS = 2048;                                      // arena nodes mirrored in LDS
+
+struct DecDims {
+  int B, T, C, W;
+};
+
+// workspace layout: rowstat float[2 BT] | cls int[BT (W+1)] | clp float[BT (W+1)] |
+// arena u64[B (T W + 1)] (dec_pl words).  The greedy path keeps its per-frame arg-max in cls.
+struct DecWs {
+  float* rowstat;
+  int* cls;
+  float* clp;
+  unsigned long long* arena;
+  __host__ __device__ DecWs(void* ws, DecDims d) {
+    const long BT = (long)d.B * d.T, K = d.W + 1;
+    rowstat = static_cast<float*>(ws);
+    cls = reinterpret_cast<int*>(rowstat + 2 * BT);
+    clp = reinterpret_cast<float*>(cls + BT * K);
+    arena = reinterpret_cast<unsigned long long*>(clp + BT * K);  // 2 BT (K + 1) floats in front: 8-byte aligned
+  }
+};
+
+__device__ __forceinline__ float dec_lp(float x, float m, float ls) { return (x - m) - ls; }
+
+__device__ __forceinline__ float logaddexp(float a, float b) {
+  const float hi = fmaxf(a, b), lo = fminf(a, b);
+  if (lo == NEG_INF) return hi;
+  return hi + __logf(1.0f + __expf(lo - hi));
+}
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+
+// (v, c) beats (w, d): larger value, ties to the lower index
+__device__ __forceinline__ bool beats(float v, int c, float w, int d) { return v > w || (v == w && c < d); }
+
+__device__ __forceinline__ void wave_argmax(float& v, int& c) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float w = __shfl_xor(v, o, 64);
+    const int d = __shfl_xor(c, o, 64);
+    if (beats(w, d, v, c)) { v = w; c = d; }
+  }
+}
+
+// (value, key) as one unsigned word that orders like "larger value first, then lower key":
+// the float's bits made monotone (-0 folded into +0), the key complemented below them.
+// Never 0 for a finite or infinite value, so 0 marks a dropped item.
+__device__ __forceinline__ unsigned long long dec_ord(float v, int key) {
+  unsigned u = __float_as_uint(v + 0.0f);
+  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ((unsigned long long)u << 32) | (unsigned)(NONE - key);
+}
+
+// an arena node, and a beam's identity as "child of node par by label lab", as one word
+__device__ __forceinline__ unsigned long long dec_pl(int par, int lab) {
+  return ((unsigned long long)(unsigned)par << 32) | (unsigned)lab;
+}
+__device__ __forceinline__ int dec_par(unsigned long long v) { return (int)(v >> 32); }
+__device__ __forceinline__ int dec_lab(unsigned long long v) { return (int)(v & 0xffffffffull); }
+
+// One wave per (b, t) row: the K = min(W + 1, C - 1) labels (c != 0) with the largest
+// log-probability, in descending order, ties to the lower class.  Round k takes the best
+// element strictly after round k - 1's pick in that order, so nothing is marked as taken.
+__global__ __launch_bounds__(256) void ctc_topk_kernel(const float* __restrict__ x, const int* __restrict__ in_len,
+                                                       DecDims d, DecWs w) {
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= (long)d.B * d.T) return;
+  const int b = (int)(row / d.T), t = (int)(row - (long)b * d.T);
+  if (t >= clampi(in_len[b], 0, d.T)) return;
+  const float* xr = x + row * d.C;
+  const float m = w.rowstat[2 * row], ls = w.rowstat[2 * row + 1];
+  const int K = min(d.W + 1, d.C - 1);
+  float pv = 0.0f;
+  int pc = -1;
+  for (int k = 0; k < K; ++k) {
+    float bv = NEG_INF;
+    int bc = NONE;
+    for (int c = 1 + lane; c < d.C; c += 64) {
+      const float v = dec_lp(xr[c], m, ls);
+      const bool open = k == 0 || v < pv || (v == pv && c > pc);
+      if (open && v > bv) { bv = v; bc = c; }  // ascending c: the first of equal values stays
+    }
+    wave_argmax(bv, bc);
+    if (lane == 0) {
+      w.cls[row * (d.W + 1) + k] = bc == NONE ? 0 : bc;  // 0: no label left above -inf
+      w.clp[row * (d.W + 1) + k] = bv;
+    }
+    pv = bv;
+    pc = bc;
+  }
+}
+
+// One workgroup (one wave) per clip.  Beam slot state lives in LDS, double-buffered; slots
+// are kept sorted by total, so slot 0 is the best beam.  A prefix is a node (parent, label)
+// of the clip's arena; a candidate whose (parent, label) pair already has a node (a pruned
+// prefix that comes back) takes that node again, so a prefix has one node for good and
+// "is this prefix an active beam" is a comparison of node ids.  Log-probabilities are kept
+// relative to the best beam's total of the previous frame (the sum of those shifts is
+// carried in a double): the selection is shift-invariant and fp32 rounding then acts on
+// numbers of the size of the beam's spread, not of the whole clip's log-probability.
+//
+// The frame loop is a latency chain, so nothing in it waits for global memory that could have
+// been asked for earlier: frame t + 1's normaliser, blank logit and best labels are loaded
+// during frame t, and so are frame t + 1's logits of every label a new beam can end in (the
+// active beams' labels and frame t's best labels).  The first DEC_ARENA_LDS arena nodes are
+// mirrored in LDS for the look-up; the hand-offs between phases are then LDS-only barriers
+// that leave those loads in flight.  The beam_width best of the M <= W (W + 2) items are
+// found by counting, for each item, the items in front of it (M LDS broadcast reads per
+// item, no cross-lane traffic).
+__global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ x, const int* __restrict__ in_len,
+                                                      DecDims d, int collapse, int* __restrict__ tokens,
+                                                      int* __restrict__ out_len, float* __restrict__ score,
+                                                      DecWs w) {
+  __shared__ int s_node[2][DEC_MAX_W], s_lab[2][DEC_MAX_W], s_par[2][DEC_MAX_W];
+  __shared__ float s_lb[2][DEC_MAX_W], s_ll[2][DEC_MAX_W], s_tot[2][DEC_MAX_W];
+  __shared__ float s_xe[2][DEC_MAX_W];  // this frame's logit of the beam's last label
+  __shared__ float u_lb[DEC_MAX_W], u_ll[DEC_MAX_W];
+  __shared__ float it_val[DEC_MAX_ITEMS];
+  __shared__ unsigned long long it_ord[DEC_MAX_ITEMS];
+  __shared__ int f_cls[DEC_MAX_W + 1];                       // this frame's best labels ...
+  __shared__ float f_clp[DEC_MAX_W + 1];                     // ... and their log-probabilities
+  __shared__ float n_xc[DEC_MAX_W + 1], n_xb[DEC_MAX_W];     // the next frame's logits of those / of the beams' labels
+  __shared__ int sel[DEC_MAX_W], found[DEC_MAX_W];
+  __shared__ unsigned long long s_pl[2][DEC_MAX_W];  // dec_pl(s_par, s_lab)
+  __shared__ unsigned long long want[DEC_MAX_W];     // the node a fresh beam looks for, else ~0
+  __shared__ unsigned long long a_lds[DEC_ARENA_LDS];
+  __shared__ int s_len;
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int T = d.T, C = d.C, W = d.W, KS = W + 1, K = min(W + 1, C - 1);
+  const int Tb = clampi(in_len[b], 0, T);
+  unsigned long long* arena = w.arena + (long)b * ((long)T * W + 1);
+  int nn = 1, nb = 1, cur = 0;  // arena nodes, active beams, state buffer (all wave-uniform)
+  double offset = 0.0;
+  // the frame's beam-independent inputs, loaded one frame ahead
+  float pm = 0.0f, pls = 0.0f, px0 = 0.0f, pclp = NEG_INF;
+  int pcls = 0;
+  auto prefetch = [&](int t) {
+    const long row = (long)b * T + t;
+    pm = w.rowstat[2 * row];
+    pls = w.rowstat[2 * row + 1];
+    px0 = x[row * C];
+    if (lane < K) {
+      pcls = w.cls[row * KS + lane];
+      pclp = w.clp[row * KS + lane];
+    }
+  };
+  if (Tb > 0) prefetch(0);
+  if (lane == 0) {
+    arena[0] = dec_pl(-1, 0);  // the empty prefix
+    a_lds[0] = dec_pl(-1, 0);
+    s_node[0][0] = 0; s_lab[0][0] = 0; s_par[0][0] = -1; s_pl[0][0] = dec_pl(-1, 0);
+    s_lb[0][0] = 0.0f; s_ll[0][0] = NEG_INF; s_tot[0][0] = 0.0f; s_xe[0][0] = 0.0f;
+  }
+  __syncthreads();
+  for (int t = 0; t < Tb; ++t) {
+    const float m = pm, ls = pls, lp0 = dec_lp(px0, pm, pls);
+    const int nxt = cur ^ 1;
+    if (lane < K) { f_cls[lane] = pcls; f_clp[lane] = pclp; }
+    if (lane < W) sel[lane] = -1;
+    float nxc = 0.0f, nxb = 0.0f;
+    if (t + 1 < Tb) {  // wave-uniform
+      const float* xn = x + ((long)b * T + t + 1) * C;
+      if (lane < K) nxc = xn[pcls];
+      if (lane < nb) nxb = xn[s_lab[cur][lane]];
+      prefetch(t + 1);
+    }
+    lds_barrier();
+    // updated beams
+    if (lane < nb) {
+      const int e = s_lab[cur][lane], par = s_par[cur][lane];
+      const float nlb = s_tot[cur][lane] + lp0;
+      float nll = NEG_INF;
+      if (par >= 0) {
+        const float lpe = dec_lp(s_xe[cur][lane], m, ls);
+        nll = s_ll[cur][lane] + lpe;
+        int pj = -1;  // the parent prefix's slot: node ids of active beams are distinct
+#pragma unroll 8
+        for (int j = 0; j < nb; ++j) pj = s_node[cur][j] == par ? j : pj;
+        if (pj >= 0) nll = logaddexp(nll, lpe + (e == s_lab[cur][pj] ? s_lb[cur][pj] : s_tot[cur][pj]));
+      }
+      const float tot = logaddexp(nlb, nll);
+      u_lb[lane] = nlb;
+      u_ll[lane] = nll;
+      it_val[lane] = tot;
+      it_ord[lane] = dec_ord(tot, lane);
+    }
+    // extension candidates: beam j x the frame's k-th best label
+    const int M = nb + nb * K;
+    for (int n = lane; n < nb * K; n += 64) {
+      const int j = n / K, k = n - j * K;
+      const int c = f_cls[k];
+      float v = NEG_INF;
+      if (c > 0) {
+        const unsigned long long qc = dec_pl(s_node[cur][j], c);
+        bool active = false;
+#pragma unroll 4
+        for (int i = 0; i < nb; ++i) active |= s_pl[cur][i] == qc;
+        if (!active) v = f_clp[k] + (c == s_lab[cur][j] ? s_lb[cur][j] : s_tot[cur][j]);
+      }
+      it_val[nb + n] = v;
+      it_ord[nb + n] = v == NEG_INF ? 0ull : dec_ord(v, KEY_CAND + j * SCA_CTC_MAX_C + c);  // -inf: dropped
+    }
+    lds_barrier();
+    // the W best by (total, key): updated beams first, then lower slot, then lower class.
+    // An item's rank is the number of items in front of it; the keys are distinct.
+    for (int n = lane; n < M; n += 64) {
+      const unsigned long long mine = it_ord[n];
+      if (mine == 0ull) continue;
+      int rank = 0;
+#pragma unroll 8
+      for (int i = 0; i < M; ++i) rank += it_ord[i] > mine;
+      if (rank < W) sel[rank] = n;
+    }
+    if (lane < K) n_xc[lane] = nxc;
+    if (lane < nb) n_xb[lane] = nxb;
+    lds_barrier();
+    const int R = __popcll(__ballot(lane < W && sel[lane < W ? lane : 0] >= 0));
+    // the new beam set, in selection order
+    int node = -1, lab = 0, par = -1;
+    float lb = NEG_INF, ll = NEG_INF, tot = NEG_INF, xe = 0.0f;
+    bool fresh = false;
+    if (lane < R) {
+      const int idx = max(sel[lane], 0);  // ranks are a permutation unless a total is NaN: stay in bounds
+      tot = it_val[idx];
+      if (idx < nb) {
+        node = s_node[cur][idx]; lab = s_lab[cur][idx]; par = s_par[cur][idx];
+        lb = u_lb[idx]; ll = u_ll[idx];
+        xe = n_xb[idx];
+      } else {
+        const int n = idx - nb, j = n / K, k = n - j * K;
+        par = s_node[cur][j];
+        lab = f_cls[k];
+        ll = tot;
+        xe = n_xc[k];
+        fresh = true;
+      }
+      s_par[nxt][lane] = par;
+      s_lab[nxt][lane] = lab;
+      s_pl[nxt][lane] = dec_pl(par, lab);
+      want[lane] = fresh ? dec_pl(par, lab) : ~0ull;
+      found[lane] = -1;
+    }
+    const unsigned long long any_fresh = __ballot(fresh);
+    lds_barrier();
+    if (any_fresh) {  // a prefix that was pruned and comes back keeps its node
+      const int nl = min(nn, DEC_ARENA_LDS);
+      for (int n0 = lane; n0 < nl; n0 += 256) {  // four nodes per lane and pass: fewer dependent LDS trips
+        unsigned long long nd[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) nd[u] = n0 + 64 * u < nl ? a_lds[n0 + 64 * u] : ~0ull;
+#pragma unroll 8
+        for (int r = 0; r < R; ++r) {
+          const unsigned long long wr = want[r];
+          if (wr == ~0ull) continue;
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+            if (wr == nd[u]) found[r] = n0 + 64 * u;
+        }
+      }
+      for (int n = DEC_ARENA_LDS + lane; n < nn; n += 64) {  // nodes beyond the mirror
+        const unsigned long long nd = arena[n];
+#pragma unroll 4
+        for (int r = 0; r < R; ++r)
+          if (want[r] == nd) found[r] = n;
+      }
+    }
+    lds_barrier();
+    const bool alloc = fresh && found[lane < R ? lane : 0] < 0;
+    const unsigned long long am = __ballot(alloc);
+    if (fresh) {
+      node = found[lane];
+      if (alloc) {
+        node = nn + __popcll(am & ((1ull << lane) - 1ull));  // < nn + W <= T W + 1
+        arena[node] = dec_pl(par, lab);
+        if (node < DEC_ARENA_LDS) a_lds[node] = dec_pl(par, lab);
+      }
+    }
+    nn += __popcll(am);
+    const float shift = __shfl(tot, 0, 64);  // slot 0: the best total
+    if (shift != NEG_INF) {
+      offset += (double)shift;
+      lb -= shift; ll -= shift; tot -= shift;
+    }
+    if (lane < R) {
+      s_node[nxt][lane] = node;
+      s_lb[nxt][lane] = lb; s_ll[nxt][lane] = ll; s_tot[nxt][lane] = tot; s_xe[nxt][lane] = xe;
+    }
+    nb = R;
+    cur = nxt;
+    // nodes beyond the LDS mirror are read back from global memory by the next look-up
+    if (nn > DEC_ARENA_LDS) __syncthreads();
+    else lds_barrier();
+  }
+  __syncthreads();
+  // slot 0 is the best beam (ties to the lower slot); walk its prefix back to the root
+  int* tok = tokens + (long)b * T;
+  if (lane == 0) {
+    const int leaf = s_node[cur][0];
+    int len = 0;
+    for (int n = leaf; len < Tb && dec_par(arena[n]) >= 0; n = dec_par(arena[n])) ++len;
+    int n = leaf;
+    for (int i = len - 1; i >= 0; --i) {
+      const unsigned long long nd = arena[n];
+      tok[i] = dec_lab(nd);
+      n = dec_par(nd);
+    }
+    if (collapse) {  // utils.py:185-188: groupby over the decoded labels
+      int o = 0, prev = 0;
+      for (int i = 0; i < len; ++i) {
+        const int v = tok[i];
+        if (i == 0 || v != prev) tok[o++] = v;
+        prev = v;
+      }
+      len = o;
+    }
+    s_len = len;
+    out_len[b] = len;
+    score[b] = (float)(offset + (double)s_tot[cur][0]);
+  }
+  __syncthreads();
+  for (int i = s_len + lane; i < T; i += 64) tok[i] = 0;
+}
+
+// One workgroup of 16 waves per clip: each wave takes every 16th frame's arg-max (ties to the
+// lowest class; a frame is a chain of dependent loads, so frames run side by side), then
+// wave 0 collapses repeats and drops blanks with a ballot scan.
+constexpr int GREEDY_WAVES = 16;
+__global__ __launch_bounds__(64 * GREEDY_WAVES) void ctc_greedy_kernel(const float* __restrict__ x,
+                                                                        const int* __restrict__ in_len, DecDims d,
+                                                                        int* __restrict__ tokens,
+                                                                        int* __restrict__ out_len,
+                                                                        float* __restrict__ score, DecWs w) {
+  __shared__ float part[GREEDY_WAVES];
+  __shared__ int s_len;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int T = d.T, C = d.C;
+  const int Tb = clampi(in_len[b], 0, T);
+  int* amax = w.cls + (long)b * T;
+  float acc = 0.0f;
+  for (int t = wave; t < Tb; t += GREEDY_WAVES) {
+    const long row = (long)b * T + t;
+    const float* xr = x + row * C;
+    float bv = NEG_INF;
+    int bc = NONE;
+    for (int c = lane; c < C; c += 64) {
+      const float v = xr[c];
+      if (v > bv) { bv = v; bc = c; }
+    }
+    wave_argmax(bv, bc);
+    if (bc == NONE) bc = 0;
+    if (lane == 0) amax[t] = bc;
+    acc += dec_lp(xr[bc], w.rowstat[2 * row], w.rowstat[2 * row + 1]);
+  }
+  if (lane == 0) part[wave] = acc;
+  __syncthreads();
+  int* tok = tokens + (long)b * T;
+  if (wave == 0) {
+    int count = 0;
+    for (int base = 0; base < Tb; base += 64) {
+      const int t = base + lane;
+      const int a = t < Tb ? amax[t] : 0;
+      const int prev = (t > 0 && t < Tb) ? amax[t - 1] : 0;
+      const bool keep = t < Tb && a != 0 && (t == 0 || a != prev);
+      const unsigned long long mask = __ballot(keep);
+      if (keep) tok[count + __popcll(mask & ((1ull << lane) - 1ull))] = a;
+      count += __popcll(mask);
+    }
+    if (lane == 0) {
+      s_len = count;
+      out_len[b] = count;
+      float sum = 0.0f;
+      for (int i = 0; i < GREEDY_WAVES; ++i) sum += part[i];
+      score[b] = sum;
+    }
+  }
+  __syncthreads();
+  for (int i = s_len + tid; i < T; i += 64 * GREEDY_WAVES) tok[i] = 0;
+}
+
+constexpr int WER_LD = SCA_WER_MAX_LEN + 3;  // odd dword stride along an anti-diagonal
+constexpr int WER_DEL = 3, WER_INS = 3, WER_SUB = 4;
+
+// One workgroup per (reference, hypothesis) pair; thread i owns matrix row i + 1 and the
+// matrix is filled one anti-diagonal per barrier.  Lane 0 walks the alignment back.
+__global__ __launch_bounds__(128) void wer_kernel(const int* __restrict__ ref, const int* __restrict__ ref_len,
+                                                  const int* __restrict__ hyp, const int* __restrict__ hyp_len,
+                                                  int Rmax, int Hmax, int* __restrict__ counts) {
+  __shared__ unsigned short dm[(SCA_WER_MAX_LEN + 1) * WER_LD];
+  __shared__ int r_s[SCA_WER_MAX_LEN], h_s[SCA_WER_MAX_LEN];
+  const int n = blockIdx.x, tid = threadIdx.x;
+  const int R = clampi(ref_len[n], 0, Rmax), H = clampi(hyp_len[n], 0, Hmax);
+  if (tid < R) r_s[tid] = ref[(long)n * Rmax + tid];
+  if (tid < H) h_s[tid] = hyp[(long)n * Hmax + tid];
+  for (int j = tid; j <= H; j += 128) dm[j] = (unsigned short)(j * WER_INS);
+  for (int i = tid; i <= R; i += 128) dm[i * WER_LD] = (unsigned short)(i * WER_DEL);
+  __syncthreads();
+  const int i = tid + 1;
+  for (int k = 2; k <= R + H; ++k) {
+    const int j = k - i;
+    if (i <= R && j >= 1 && j <= H) {
+      int v = dm[(i - 1) * WER_LD + j - 1];
+      if (r_s[i - 1] != h_s[j - 1])
+        v = min(v + WER_SUB, min((int)dm[i * WER_LD + j - 1] + WER_INS, (int)dm[(i - 1) * WER_LD + j] + WER_DEL));
+      dm[i * WER_LD + j] = (unsigned short)v;
+    }
+    lds_barrier();
+  }
+  if (tid == 0) {
+    int xx = R, yy = H, nd = 0, ni = 0, ns = 0;
+    for (int step = 0; step <= 3 * (R + H) && (xx > 0 || yy > 0); ++step) {
+      const int v = dm[xx * WER_LD + yy];
+      if (xx >= 1 && yy >= 1 && v == dm[(xx - 1) * WER_LD + yy - 1] && r_s[xx - 1] == h_s[yy - 1]) {
+        --xx; --yy;
+      } else if (xx >= 1 && yy >= 1 && v == dm[(xx - 1) * WER_LD + yy - 1] + WER_SUB) {
+        ++ns; --xx; --yy;
+      } else if (yy >= 1 && v == dm[xx * WER_LD + yy - 1] + WER_INS) {
+        ++ni; --yy;
+      } else {
+        ++nd; xx = max(xx - 1, 0);
+      }
+    }
+    int* out = counts + 4L * n;
+    out[0] = nd; out[1] = ni; out[2] = ns; out[3] = R;
+  }
+}
+
+bool dec_dims_ok(int B, int T, int C, int W) {
+  return B >= 1 && T >= 1 && C >= 1 && C <= SCA_CTC_MAX_C && W >= 1 && W <= SCA_CTC_MAX_BEAM;
+}
+
+}  // namespace
+
+extern "C" long sca_ctc_decode_workspace_bytes(int B, int T, int C, int W) {
+  if (!dec_dims_ok(B, T, C, W)) return 0;
+  const long BT = (long)B * T;
+  return 4 * (2 * BT + 2 * BT * (W + 1)) + 8 * (long)B * ((long)T * W + 1);
+}
+
+extern "C" int sca_ctc_greedy_decode(const float* logits, const int* in_len, int B, int T, int C, int* tokens,
+                                     int* out_len, float* score, void* ws, void* stream) {
+  if (!dec_dims_ok(B, T, C, 1) || !logits || !in_len || !tokens || !out_len || !score || !ws) {
+    sca_set_error("sca_ctc_greedy_decode: bad arguments (B, T >= 1, 1 <= C <= 8192)");
+    return SCA_ERR_ARG;
+  }
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const DecDims d{B, T, C, 1};
+  const DecWs w(ws, d);
+  sca_ctc_rowstat_launch(logits, w.rowstat, (long)B * T, C, st);
+  hipLaunchKernelGGL(ctc_greedy_kernel, dim3(B), dim3(64 * GREEDY_WAVES), 0, st, logits, in_len, d, tokens, out_len,
+                     score, w);
+  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_ctc_greedy_decode: launch failed"); return SCA_ERR_LAUNCH; }
+  return SCA_OK;
+}
+
+extern "C" int sca_ctc_beam_decode(const float* logits, const int* in_len, int B, int T, int C, int beam_width,
+                                   int collapse_repeats, int* tokens, int* out_len, float* score, void* ws,
+                                   void* stream) {
+  if (!dec_dims_ok(B, T, C, beam_width) || !logits || !in_len || !tokens || !out_len || !score || !ws) {
+    sca_set_error("sca_ctc_beam_decode: bad arguments (B, T >= 1, 1 <= C <= 8192, 1 <= beam_width <= 32)");
+    return SCA_ERR_ARG;
+  }
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const DecDims d{B, T, C, beam_width};
+  const DecWs w(ws, d);
+  const long rows = (long)B * T;
+  sca_ctc_rowstat_launch(logits, w.rowstat, rows, C, st);
+  hipLaunchKernelGGL(ctc_topk_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, logits, in_len, d, w);
+  hipLaunchKernelGGL(ctc_beam_kernel, dim3(B), dim3(64), 0, st, logits, in_len, d, collapse_repeats != 0, tokens,
+                     out_len, score, w);
+  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_ctc_beam_decode: launch failed"); return SCA_ERR_LAUNCH; }
+  return SCA_OK;
+}
+
+extern "C" int sca_wer_counts(const int* ref, const int* ref_len, const int* hyp, const int* hyp_len, int N,
+                              int Rmax, int Hmax, int* counts, void* stream) {
+  if (N < 1 || Rmax < 0 || Rmax > SCA_WER_MAX_LEN || Hmax < 0 || Hmax > SCA_WER_MAX_LEN || !ref_len || !hyp_len ||
+      (Rmax > 0 && !ref) || (Hmax > 0 && !hyp) || !counts) {
+    sca_set_error("sca_wer_counts: bad arguments (N >= 1, 0 <= Rmax, Hmax <= 128)");
+    return SCA_ERR_ARG;
+  }
+  hipLaunchKernelGGL(wer_kernel, dim3(N), dim3(128), 0, reinterpret_cast<hipStream_t>(stream), ref, ref_len, hyp,
+                     hyp_len, Rmax, Hmax, counts);
+  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_wer_counts: launch failed"); return SCA_ERR_LAUNCH; }
+  return SCA_OK;
+}

@@ -428,6 +428,11 @@ bool ctc_dims_ok(int B, int T, int C, int S) {
 
 }  // namespace
 
+// the row max / log-sum-exp pass, shared with the CTC decoders (decode.hip)
+void sca_ctc_rowstat_launch(const float* x, float* rowstat, long rows, int C, hipStream_t st) {
+  hipLaunchKernelGGL(ctc_rowstat_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, x, rowstat, rows, C);
+}
+
 extern "C" long sca_ctc_workspace_floats(int B, int T, int S) {
   const long BT = (long)B * T;
   return 2 * BT + 2 * BT * (2L * S + 1) + 2L * B;
@@ -442,7 +447,7 @@ extern "C" int sca_ctc_loss_fwd(const float* logits, const int* labels, const in
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const CtcDims d{B, T, C, S};
   const long rows = (long)B * T;
-  hipLaunchKernelGGL(ctc_rowstat_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, logits, ws, rows, C);
+  sca_ctc_rowstat_launch(logits, ws, rows, C, st);
   hipLaunchKernelGGL(ctc_alpha_beta_kernel, dim3(B, 2), dim3(CTC_THREADS), 0, st, logits, labels, in_len, tgt_len,
                      d, ws);
   hipLaunchKernelGGL(ctc_finalize_kernel, dim3(1), dim3(256), 0, st, d, ws, nll, loss);
