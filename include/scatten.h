@@ -45,6 +45,11 @@
  *   sca_ctc_beam_decode    on the host) as evaluate_fn calls it (opt.py:84-89)
  *   sca_wer_counts         metrics.wer_single / edit_distance / get_alignment
  *                          (metrics.py:2793-2907)
+ *   sca_finite_scan        the isnan().any() / isinf().any() tests of MSCA_Net.forward
+ *                          (model/__init__.py:130-235), all tensors in one launch
+ *   sca_step_report        total_loss (model/__init__.py:207,237), the loss terms the
+ *                          training loop logs (opt.py:39-42) and the device-side form of
+ *                          the non-finite skip (opt.py:32) over every checked tensor
  */
 #ifndef SCATTEN_H
 #define SCATTEN_H
@@ -607,7 +612,8 @@ int sca_seqkd_fwd(const float* student, const float* teacher, int R, int C, int 
 int sca_seqkd_bwd(const float* student, const float* teacher, int R, int C, int start, float temp,
                   const float* dloss, const float* ws, float* dstudent, float* dteacher, void* stream);
 
-/* torch.clamp(x, lo, hi) over n elements (dy == NULL), or its backward dx = dy * [lo <= x <= hi] */
+/* torch.clamp(x, lo, hi) over n elements (dy == NULL; a NaN stays a NaN), or its backward
+ * dx = dy * [lo <= x <= hi] */
 int sca_clamp(const float* x, float* y, const float* dy, float* dx, long n, float lo, float hi, void* stream);
 
 /* One time step of a (bi)directional LSTM cell (AlignmentModule's nn.LSTM,
@@ -691,6 +697,36 @@ int sca_optim_scale_grads(const sca_optim_tensor* tensors, const sca_optim_chunk
  * src must be pinned host memory that is left unmodified and alive for as long as a graph
  * holding the copy can be replayed.                                                       */
 int sca_optim_upload(void* dst, const void* src, long bytes, void* stream);
+
+/* ---- finite guard: the NaN / Inf checks of MSCA_Net.forward without their host reads ----
+ * sca_finite_scan: ntensors (0..16) contiguous fp32 tensors, given as HOST arrays ptrs /
+ * numels (copied into the kernel arguments: no device table).  flags: ntensors 32-bit words in
+ * device memory; the call clears them on `stream` (a memset node under capture) and one
+ * launch ORs into word t  bit 0 when tensor t holds a NaN,  bit 1 when it holds +-Inf.
+ * Elements are classified from their exponent / mantissa bits.  Workgroups stride over
+ * SCA_GUARD_CHUNK-element chunks (no chunk spans two tensors), with 16-byte loads between the
+ * chunk's first and last 16-byte boundary and 4-byte loads outside; a workgroup issues at
+ * most one atomic OR per tensor, none when it found nothing.  numel 0 is legal (no launch
+ * when every tensor is empty).  SCA_ERR_ARG: ntensors > 16, a negative numel, a null or
+ * misaligned (not 4-byte) pointer with numel > 0.                                          */
+#define SCA_GUARD_MAX_TENSORS 16
+#define SCA_GUARD_CHUNK 4096
+int sca_finite_scan(int ntensors, const float* const* ptrs, const long* numels, unsigned* flags, void* stream);
+
+/* sca_step_report: one small launch after the scan.  report (device, nflags + ndistill + 4
+ * 32-bit words) receives
+ *   [0, nflags)            the flag words (zeros when flags == NULL: guard switched off)
+ *   then, as fp32:         alignment_loss (0 when NULL), fuse_coord_loss, the ndistill
+ *                          distillation terms, total_loss, guard
+ * with total_loss = fuse_coord_loss + distill[0] + ... in that order (also stored to
+ * *total_loss when not NULL) and guard = total_loss when every flag word is zero, NaN
+ * otherwise — the scalar FusedAdam.step(loss=...) / sca_optim_grad_sqnorm test, so a flagged
+ * tensor that does not feed total_loss skips the update too.  distill: HOST array of device
+ * scalars.                                                                                 */
+#define SCA_REPORT_MAX_FLAGS 64
+#define SCA_REPORT_MAX_DISTILL 8
+int sca_step_report(const unsigned* flags, int nflags, const float* alignment_loss, const float* fuse_coord_loss,
+                    int ndistill, const float* const* distill, float* total_loss, void* report, void* stream);
 
 const char* sca_last_error(void);
 int sca_version(void);

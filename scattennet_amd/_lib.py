@@ -28,6 +28,8 @@ SOFTMAX_MAX_PROBLEMS = 8
 GELU_MAX_PROBLEMS = 8
 DROPOUT_MAX_PROBLEMS = 12
 ACT_NONE, ACT_RELU = 0, 1
+GUARD_MAX_TENSORS, GUARD_CHUNK = 16, 4096
+REPORT_MAX_FLAGS, REPORT_MAX_DISTILL = 64, 8
 
 
 class GemmSeg(ctypes.Structure):
@@ -198,6 +200,8 @@ EXPORTS = {
                             c_int),
     "sca_optim_scale_grads": ([c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p], c_int),
     "sca_optim_upload": ([c_void_p, c_void_p, c_long, c_void_p], c_int),
+    "sca_finite_scan": ([c_int, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
+    "sca_step_report": ([c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
     "sca_last_error": ([], ctypes.c_char_p),
     "sca_version": ([], c_int),
     "sca_build_digest": ([], ctypes.c_char_p),

@@ -351,7 +351,7 @@ __global__ __launch_bounds__(256) void clamp_kernel(const float* __restrict__ x,
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
     const float v = x[i];
     if (dy) dx[i] = (v >= lo && v <= hi) ? dy[i] : 0.0f;  // torch clamp backward gate
-    else y[i] = fminf(fmaxf(v, lo), hi);
+    else y[i] = v < lo ? lo : (v > hi ? hi : v);  // a NaN stays a NaN, as in torch.clamp (fminf / fmaxf drop it)
   }
 }
 

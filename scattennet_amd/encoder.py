@@ -21,9 +21,13 @@ class SCAEncoder(nn.Module):
 
     @fp32_compute()
     def forward(self, keypoints, mask):
+        return self.encode(keypoints, mask)
+
+    def encode(self, keypoints, mask):
         """keypoints (B, T, K_all, 2), mask (B, T) -> (fuse, left, right, body) embeddings.
         The three streams run in lock-step (one launch per stage), their joint slicing
-        (model/__init__.py:133-142) fused into the mapping kernel's gather."""
+        (model/__init__.py:133-142) fused into the mapping kernel's gather.  (MSCA_Net, a
+        subclass with a forward of its own, calls this directly.)"""
         mods = [self.body_encoder, self.left_encoder, self.right_encoder]
         idx = getattr(self, "_idx", None)
         if idx is None or idx[0].device != keypoints.device:

@@ -1,0 +1,70 @@
+"""The training step of opt.py:28-38 on the device: zero_grad, forward, the non-finite test,
+backward, clip_grad_norm_ and optimizer.step() with no host read in between.
+
+`train_step(model, optimizer, src_input)` enqueues one whole step — forward with the finite
+check deferred, backward of `total_loss`, `FusedAdam.step(loss=guard)` — and returns the
+model's outputs.  The update is skipped on the device when any checked tensor was not finite
+(`guard` is NaN then), including tensors that do not feed `total_loss`, as the reference's
+`raise` would have stopped the step.  `read_report(outputs)` is the single host read:
+the loss terms as Python floats plus `skipped`, raising the reference's ValueError when
+flagged — by then the parameters are untouched.
+
+Capture.  For a fixed (B, T, S) the step is capturable into one hipGraph:
+
+1. hand `src_input` over as device tensors (their storage is what every replay reads);
+2. run one eager `train_step` on a side stream (it allocates the optimizer's moments and
+   tables, the library's lazy state and the dropout counter);
+3. capture `train_step` with `torch.cuda.graph` and keep the returned outputs: replays refill
+   the same tensors;
+4. between replays, call `optimizer.sync_hyperparameters()` after a scheduler step, and
+   `read_report` whenever the host wants the numbers.
+"""
+import math
+
+from . import ops
+from .model import _students_of, first_error, flag_names, guard_of
+from .model import read_report as model_read_report
+
+
+def train_step(model, optimizer, src_input):
+    """One training step of MSCA_Net with FusedAdam, enqueued on the current stream without a
+    host read.  Returns the forward's outputs (`finite_report` holds the losses and flags)."""
+    for p in model.parameters():
+        p.grad = None
+    ops.advance_dropout()
+    check, model.check = model.check, ("off" if model.check == "off" else "defer")
+    try:
+        outputs = model(src_input)
+    finally:
+        model.check = check
+    ops.fork_ledger_begin()
+    try:
+        outputs["total_loss"].backward()
+        # weight gradients held back for the side stream and deferred LayerNorm-affine
+        # reductions are normally launched by the backward's final callback; a backward that
+        # left some behind must not reach the update without them
+        ops.flush_held()
+        ops.flush_deferred_affine()
+    except BaseException:
+        try:
+            ops.fork_ledger_end()
+        except RuntimeError:
+            pass  # the backward's own error is the one to report
+        raise
+    ops.fork_ledger_end()  # every stream forked in the step has joined the origin (capture rule)
+    optimizer.step(loss=guard_of(outputs))
+    return outputs
+
+
+def read_report(outputs):
+    """The step's one host read: the loss terms (`total_loss`, `alignment_loss`,
+    `fuse_coord_loss`, `*_distill_loss`) and `guard` as Python floats, the flag words, and
+    `skipped` (the update did not happen: `guard` was not finite, the test FusedAdam makes on
+    the device).  Raises the reference's ValueError (model/__init__.py:130-235) when a checked
+    tensor was not finite."""
+    rep = model_read_report(outputs)
+    rep["skipped"] = not math.isfinite(rep["guard"])
+    msg = first_error(rep["flags"], flag_names(_students_of(outputs)))
+    if msg is not None:
+        raise ValueError(msg)
+    return rep

@@ -1,0 +1,152 @@
+"""Time the whole MSCA_Net training step (scattennet_amd.train_step: forward, finite guard,
+backward of total_loss, FusedAdam) on one MI355X at the Phoenix-2014T yaml shapes: B = 8,
+T = 256, BASELINE config 3's encoder, heads with vocabulary C (1124), BiLSTM alignment head
+(1024 -> 2 x 512, 2 layers), 24 glosses per clip.  Synthetic data, eval mode (dropout off),
+as tools/heads_bench.py.
+
+Three variants of the same step:
+  graph_off    one captured hipGraph, model.check = "off"   (no scan; the report launch stays)
+  graph_defer  one captured hipGraph, model.check = "defer" (scan + report, no host read)
+  eager_sync   eager launches + read_report() every step     (one host read per step)
+The two graphs are timed in alternated windows (device events around `--steps` replays each)
+and reported as medians over `--windows` windows; the scan's cost is defer - off.  The scan
+kernel alone is timed as a captured graph of `--scan-reps` sca_finite_scan calls over
+tensors of the step's shapes (they stay cache-resident between calls: the figure is the
+kernel's rate on 25.6 MB it re-reads, not an HBM stream).  Prints one JSON line.
+
+Usage: python tools/model_bench.py [--B 8] [--T 256] [--C 1124] [--steps 10] [--windows 7]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def build(a, dev):
+    import scattennet_amd as S
+    from scattennet_amd import workloads as W
+    w = dict(W.WORKLOADS["cfg3"], B=a.B, T=a.T)
+    cfg = W.encoder_cfg(w)
+    cfg.update({"self_distillation": True, "distillation_weight": {"left": 0.25, "right": 0.25, "body": 0.25},
+                "alignment_module": {"input_size": w["out_fusion"], "hidden_size": 1024, "num_layers": 2,
+                                     "dropout": 0.3, "bidirectional": True}})
+    torch.manual_seed(0)
+    model = S.MSCA_Net(cfg, a.C, device="cuda").to(dev).eval()
+    kp, mask, _ = W.synthetic_batch(w, dev, seed=1)
+    t4 = W.pooled_frames(w)
+    g = torch.Generator().manual_seed(2)
+    src = {"keypoints": kp, "mask": mask, "valid_len_in": torch.full((a.B,), t4, device=dev),
+           "gloss_labels": torch.randint(1, a.C, (a.B, a.S), generator=g).to(dev),
+           "gloss_lengths": torch.randint(a.S // 2, a.S + 1, (a.B,), generator=g).to(dev)}
+    return model, src, w, t4
+
+
+def capture(model, src, check, dev):
+    import scattennet_amd as S
+    model.check = check
+    opt = S.FusedAdam(model.parameters(), lr=1e-4, betas=(0.9, 0.998), weight_decay=1e-3, max_grad_norm=1.0)
+    s = torch.cuda.Stream(device=dev)
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        for _ in range(2):
+            S.train_step(model, opt, src)
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        out = S.train_step(model, opt, src)
+    out = {k: v.detach() for k, v in out.items()}  # the same storage, without the captured autograd graph
+    for _ in range(2):
+        graph.replay()
+    torch.cuda.synchronize()
+    return graph, out, opt
+
+
+def window(graph, steps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(steps):
+        graph.replay()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / steps
+
+
+def scan_alone(a, w, t4, dev):
+    import scattennet_amd as S
+    shapes = ([(a.B, a.T, w["K_all"], 2)] + [(a.B, t4, w["residual_blocks"][-1])] * 3 + [(a.B, t4, w["out_fusion"])] +
+              [(a.B, t4, a.C)] * 5 + [()] * 5)
+    ts = [torch.randn(s, device=dev) for s in shapes]
+    nbytes = 4 * sum(t.numel() for t in ts)
+    S.finite_flags(ts)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        for _ in range(a.scan_reps):
+            flags = S.finite_flags(ts)
+    graph.replay()
+    torch.cuda.synchronize()
+    us = sorted(window(graph, 5) * 1e3 / a.scan_reps for _ in range(a.windows))[a.windows // 2]
+    assert flags.cpu().tolist() == [0] * len(ts)
+    return nbytes, us
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--B", type=int, default=8)
+    ap.add_argument("--T", type=int, default=256)
+    ap.add_argument("--C", type=int, default=1124)
+    ap.add_argument("--S", type=int, default=24)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--windows", type=int, default=7)
+    ap.add_argument("--scan-reps", type=int, default=50)
+    a = ap.parse_args()
+    import scattennet_amd as S
+    if not torch.cuda.is_available():
+        raise SystemExit("model_bench needs a GPU: there is no CPU path to time")
+    dev = torch.device("cuda:0")
+    model, src, w, t4 = build(a, dev)
+    graphs = {k: capture(model, src, k, dev) for k in ("off", "defer")}
+    ms = {k: [] for k in graphs}
+    for _ in range(a.windows):  # alternated windows
+        for k, (graph, _, _) in graphs.items():
+            ms[k].append(window(graph, a.steps))
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    rep = S.read_report(graphs["defer"][1])
+
+    model.check = "sync"
+    opt = S.FusedAdam(model.parameters(), lr=1e-4, betas=(0.9, 0.998), weight_decay=1e-3, max_grad_norm=1.0)
+    eager = []
+    for i in range(3 + a.steps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        S.read_report(S.train_step(model, opt, src))  # the report read is the step's one host read
+        torch.cuda.synchronize()
+        if i >= 3:
+            eager.append((time.perf_counter() - t0) * 1e3)
+    nbytes, scan_us = scan_alone(a, w, t4, dev)
+    scan_ms = med["defer"] - med["off"]
+    print(json.dumps({
+        "workload": "MSCA_Net train_step (fwd + finite guard + bwd of total_loss + FusedAdam), eval mode",
+        "B": a.B, "T": a.T, "T_pooled": t4, "C": a.C, "S": a.S,
+        "parameters": sum(p.numel() for p in model.parameters()),
+        "graph_off_ms": round(med["off"], 4), "graph_defer_ms": round(med["defer"], 4),
+        "graph_off_windows_ms": [round(v, 4) for v in ms["off"]],
+        "graph_defer_windows_ms": [round(v, 4) for v in ms["defer"]],
+        "eager_sync_ms": round(statistics.median(eager), 4),
+        "scan_cost_ms": round(scan_ms, 4), "scan_cost_fraction_of_step": round(scan_ms / med["defer"], 5),
+        "scan_bytes": nbytes, "scan_kernel_us": round(scan_us, 3),
+        "scan_GBps_cache_resident": round(nbytes / (scan_us * 1e-6) / 1e9, 1),
+        "scan_hbm_roofline_us": round(nbytes / 6.3e12 * 1e6, 3),
+        "clips_per_s_graph_defer": round(a.B / med["defer"] * 1e3, 1),
+        "total_loss": rep["total_loss"], "skipped": rep["skipped"]}))
+
+
+if __name__ == "__main__":
+    main()
