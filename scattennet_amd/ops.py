@@ -9,6 +9,7 @@ Parameters keep the nn.Linear / nn.LayerNorm layouts of the reference (W is [out
 """
 import ctypes
 import os
+from typing import NamedTuple, Optional
 
 import torch
 from torch.autograd import Function
@@ -505,21 +506,12 @@ def _ln_bwd_or_handoff(dys, vs, gam, means, rstds, lnsaved, bet):
     if hs is None:
         dys = _contig(_zeros_for_none(dys, vs))
         return _ln_bwd(dys, vs, gam, means, rstds, defer_affine=_LN_AFFINE_SIDE, params=params) + (None,)
-    G, N, nblk = len(gam), gam[0].shape[0], hs[0][4]
+    N, nblk = gam[0].shape[0], hs[0][4]
     dg = [param_grad_empty(t) for t in gam]
     db = [param_grad_empty(b) for b in bet]
-    part = [h[3] for h in hs]
-
-    # raw pointers, not the tensors: a closure holding dg / db would make autograd's
-    # AccumulateGrad copy them (use count > 1) instead of taking them over
-    pairs = _ptr_pairs([(part[g], dg[g]) for g in range(G)] + [(part[g], db[g], nblk * N) for g in range(G)])
-
-    def reduce():
-        reduce_rows_ptr(pairs, nblk, 1, N, N, 0)
-    finish = (reduce, part, params, (pairs, nblk, N), list(dg) + list(db))
+    finish = _affine([h[3] for h in hs], dg, db, nblk, N, params)
     if not _LN_AFFINE_SIDE:
-        reduce()
-        params_produced(params)
+        _affine_reduce(finish, defer=False)
         finish = None
     dout = [h[5] for h in hs] if all(h[5] is not None for h in hs) else None
     return [h[2] for h in hs], dg, db, finish, dout
@@ -535,7 +527,7 @@ def _ln_fwd_outputs(xs):
 def _ln_bwd(dys, x, gam, means, rstds, defer_affine=False, params=None):
     """Plain LayerNorm backward (no residual table / post / activation): (dx, dgamma, dbeta,
     finish).  With `defer_affine` the dgamma / dbeta reduction is NOT launched here:
-    `finish` = (launch function, its input tensors) is run by the caller later — inside the
+    `finish` (an _Affine record) is run by the caller later — inside the
     weight-gradient side-stream section (weight_grads(..., extra=finish)), so that the
     parameter-only reduction leaves the critical stream without a fork of its own."""
     G = len(x)
@@ -557,14 +549,10 @@ def _ln_bwd(dys, x, gam, means, rstds, defer_affine=False, params=None):
                                                             part[g].data_ptr()) for g in gs])
         L.check(L.lib().sca_layernorm_bwd(len(gs), arr, rows, N, rows, 0, 0, L.stream_handle()),
                 "sca_layernorm_bwd")
-    finish = None
-    if defer_affine:  # pointers only: see _ln_bwd_or_handoff
-        pairs = _ptr_pairs([(part[g], dg[g]) for g in range(G)] + [(part[g], db[g], nblk * N) for g in range(G)])
-        finish = (lambda: reduce_rows_ptr(pairs, nblk, 1, N, N, 0), part, params or (), (pairs, nblk, N),
-                  list(dg) + list(db))
-    else:
-        params_produced(params or ())
-    return dx, dg, db, finish
+    if defer_affine:
+        return dx, dg, db, _affine(part, dg, db, nblk, N, params or ())
+    params_produced(params or ())
+    return dx, dg, db, None
 
 
 def _ptr_pairs(items):
@@ -601,9 +589,6 @@ _SPLITK_SLOTS = 768  # workgroup slots per round: 3 LDS-DMA 64x64 workgroups per
 
 _TNK_TILES_PER_PROBLEM = 48
 _TNR = os.environ.get("SCA_TNR", "1") != "0"  # A/B switch for variant 46
-_TNR_SK = int(os.environ.get("SCA_TNR_SK", "0"))  # A/B: one split-K for every variant-46 launch
-_TNR_MIXED = os.environ.get("SCA_TNR_MIXED", "0") != "0"  # A/B: mixed-shape variant-46 launches (-0.7 % in step)
-_TNR_MIXED_SK = int(os.environ.get("SCA_TNR_MIXED_SK", "0"))  # A/B: split-K of mixed-shape launches
 
 
 # the 128x128 register-staged weight-gradient kernel with interleaved phases (tile 43) for long
@@ -611,31 +596,6 @@ _TNR_MIXED_SK = int(os.environ.get("SCA_TNR_MIXED_SK", "0"))  # A/B: split-K of 
 # §9R.1): 0.88 of peak with one workgroup per CU, 0.86 with two, against the k-split kernel's
 # 0.74; at config 2 / 3's K <= 2048 it has too few tiles and loses
 _TNB_MIN_K = int(os.environ.get("SCA_TNB_MIN_K", "4096"))  # A/B switch (0: never)
-_TNB_RATE2, _TNB_RATE1, _TNB_EPI = 0.86, 0.88, 3.0
-
-
-_TNB_MODEL = os.environ.get("SCA_TNB_MODEL", "0") != "0"  # A/B: the isolated-speed split model
-
-
-def _tnb_split(K, tiles128):
-    """Split-K for tile 43.  In the step: 1 — one long workgroup per output tile, the fewest
-    workgroups holding CUs beside the critical chain (config 5: +0.5 % over the model below,
-    whose FFN choice of split 4 is faster alone; profiles/r05_misc/tnb_split_cfg5_ab.txt).
-    SCA_TNB_MODEL=1: the split whose estimated per-CU time is least — workgroups dealt over
-    256 CUs, two at a time at _TNB_RATE2, a leftover one at _TNB_RATE1, plus an epilogue cost
-    per workgroup (ties: the smaller split, fewer slabs)."""
-    if not _TNB_MODEL:
-        return 1
-    best, best_sk = None, 1
-    for sk in range(1, _SPLITK_MAX + 1):
-        if sk > 1 and K // sk < 1024:
-            break
-        iters = -(-(-(-K // sk)) // 64)
-        w = -(-tiles128 * sk // 256)
-        cost = (w // 2) * 2 * iters / _TNB_RATE2 + (w % 2) * iters / _TNB_RATE1 + w * _TNB_EPI
-        if best is None or cost < best - 1e-9:
-            best, best_sk = cost, sk
-    return best_sk
 
 
 def _splitk_for(M_red, n_out_tiles):
@@ -710,32 +670,35 @@ def params_produced(ps):
         _GRAD_SINK.produced([p for p in ps if p is not None and not isinstance(p, bool)])
 
 
-# ---- weight-gradient side stream -------------------------------------------------------
+# ---- weight-gradient scheduler -----------------------------------------------------------
 # The weight/bias-gradient GEMMs of a layer do not feed the rest of the backward pass, so
-# they go to a side HIP stream, forked from the point where their inputs are ready
-# (wgrad_ready) and joined into the caller's stream by a callback queued on the autograd
-# engine when backward() completes, so .grad is safe to read afterwards exactly as with a
-# single stream (the same mechanism torch DDP uses).  Captured into the step's hipGraph as
-# fork/join edges: the critical chain stays on one hardware queue and the weight gradients
-# fill the other — in practice behind the chain's second half (the executor's queue lists,
-# DESIGN.md §9).
+# they go to a side HIP stream.  One backward (one autograd graph task, _Backward) goes:
+#   fork     weight_grads forks the side stream from the point where the section's inputs
+#            are ready (wgrad_ready) and launches the section there (_wgrad_section);
+#   hold     in a backward that begins with a holdable section, the first `hold` holdable
+#            sections are only allocated and returned (_Held), not launched;
+#   flush    at the hold-th section's fork — or at the join — the held sections are launched
+#            together, equal shapes across sections sharing launches (_flush_held);
+#   affine   the LayerNorm dgamma / dbeta reductions riding in the sections are collected
+#            (_affine_reduce) and launched once, after everything else (flush_deferred_affine);
+#   join     a callback queued on the autograd engine flushes what is pending and joins the
+#            side stream into the caller's stream when backward() completes, so .grad is safe
+#            to read afterwards exactly as with a single stream (as torch DDP does).
+# Whatever a backward that raised left pending is dropped with its _Backward, never launched.
+# Captured into the step's hipGraph as fork/join edges: the critical chain stays on one
+# hardware queue and the weight gradients fill the other — in practice behind the chain's
+# second half (the executor's queue lists).
 
 _WGRAD_SIDE = True
 _EARLY_FORK = True   # fork the weight gradients before the layer's input-gradient launch
-_side_streams = {}
-_join_pending = {}
-# weight-gradient side streams per device, used round-robin by successive weight_grads calls
-# (SCA_WGRAD_STREAMS, A/B: with 2 the tail of consecutive dW launches can overlap)
-_WGRAD_STREAMS = max(1, int(os.environ.get("SCA_WGRAD_STREAMS", "1")))
+_side_streams = {}   # device -> its weight-gradient side stream
 
 
 def _side_stream(device):
-    ent = _side_streams.get(device)
-    if ent is None:
-        ent = _side_streams[device] = [[torch.cuda.Stream(device=device) for _ in range(_WGRAD_STREAMS)], 0]
-    streams, i = ent
-    ent[1] = (i + 1) % len(streams)
-    return streams[i]
+    st = _side_streams.get(device)
+    if st is None:
+        st = _side_streams[device] = torch.cuda.Stream(device=device)
+    return st
 
 
 class ForkLedger:
@@ -814,18 +777,55 @@ def note_join(into, child):
         _LEDGER.join(into, child)
 
 
+class _Backward:
+    """What one backward (autograd graph task) has pending on the side streams."""
+
+    def __init__(self, task, last_total):
+        self.task = task
+        self.last_total = last_total  # holdable sections of the last backward that had any
+        self.hold = None       # sections this backward holds: set by its first side-stream section
+        self.count = 0         # holdable sections so far
+        self.n_held = 0        # of them held so far (launched or not)
+        self.held = []         # [_Held] not launched yet
+        self.affine = {}       # stream handle -> (stream, [_Affine]) deferred on that stream
+        self.joins = set()     # (main, side) stream handles whose join callback is queued
+        self.flush_queued = False  # a flush_deferred_affine callback is queued
+        self.unsettled = set()  # id(parameter) whose gradient was returned before it was written
+
+
+_bwd = _Backward(None, 0)
+
+
+def _backward():
+    """The state of the current autograd graph task: a fresh one when the task is not the stored
+    one's — so whatever a backward that raised before its final callbacks left pending (its
+    gradients are void) is dropped, and a call outside any backward finds nothing to launch.
+    Only the section count crosses over: the next backward's hold is a fraction of it."""
+    global _bwd
+    task = torch._C._current_graph_task_id()
+    if task != _bwd.task:
+        _bwd = _Backward(task, _bwd.count or _bwd.last_total)
+    return _bwd
+
+
+def flush_pending():
+    """Launch everything the current backward still holds back: the held weight-gradient
+    sections, then the deferred affine reductions (nothing outside a backward)."""
+    flush_held()
+    flush_deferred_affine()
+
+
 def _queue_join(main, side):
+    """Queue, once per backward and (main, side), the final callback that joins `side`."""
+    bw = _backward()
     key = (main.cuda_stream, side.cuda_stream)
-    task = torch._C._current_graph_task_id()  # one join per backward (keyed by the graph task, so
-    if _join_pending.get(key) == task:         # a backward that raised leaves no stale entry)
+    if key in bw.joins:
         return
-    _join_pending[key] = task
+    bw.joins.add(key)
 
     def _join():
-        _join_pending[key] = None
-        if _held["entries"]:
-            _flush_held(main, side)
-        flush_deferred_affine()
+        bw.joins.discard(key)
+        flush_pending()
         main.wait_stream(side)
         note_join(main, side)
 
@@ -855,12 +855,6 @@ def wgrad_ready():
 # reduce_rows launch for all layers instead of one ~5-us launch between every layer's weight
 # gradients.  SCA_AFFINE_DEFER=0: the per-layer launches (A/B).
 _AFFINE_DEFER = os.environ.get("SCA_AFFINE_DEFER", "1") != "0"
-_affine_pending = {}  # side stream handle -> (side stream, [(pairs, nblk, N, keep-alive tensors, params)])
-_affine_task = None  # the autograd graph task the pending entries belong to
-
-
-_flush_queued = [None]  # the autograd graph task whose final callbacks hold a flush
-_side_written = {}  # id(parameter) -> graph task whose side stream wrote its gradient
 _AFFINE_DEFER_MAX = 256 * 512  # partial-row floats per problem up to which a LayerNormAdd defers
 
 
@@ -891,11 +885,7 @@ def _keep(ts):
 def _mark_unsettled(params):
     """Record that this backward returned these parameters' gradients before writing them (side
     stream or deferred reduction)."""
-    task = torch._C._current_graph_task_id()
-    if len(_side_written) > 4096:
-        _side_written.clear()
-    for p in params:
-        _side_written[id(p)] = task
+    _backward().unsettled.update(id(p) for p in params)
 
 
 def _settle_reuse(params):
@@ -903,176 +893,180 @@ def _settle_reuse(params):
     the side stream, or left to a deferred reduction): autograd adds the new gradient into the
     first one on the current stream, so the pending work is launched and joined here first.
     True when that happened (the caller then computes on the current stream)."""
-    task = torch._C._current_graph_task_id()
-    if not any(_side_written.get(id(p)) == task for p in params):
+    unsettled = _backward().unsettled
+    if not any(id(p) in unsettled for p in params):
         return False
-    flush_held()
-    flush_deferred_affine()
+    flush_pending()
     main = torch.cuda.current_stream()
-    for streams, _ in _side_streams.values():
-        for st in streams:
-            main.wait_stream(st)
-            note_join(main, st)
+    for side in _side_streams.values():
+        main.wait_stream(side)
+        note_join(main, side)
     return True
 
 
-def _affine_finish(part, dg, db, nblk, N, params, defer):
-    """dgamma / dbeta = fixed-order sums of the per-block partial rows: now, or (defer) collected
-    on the current stream and launched with the other deferred reductions by
-    flush_deferred_affine, which a final backward callback runs at the latest (the entry keeps
-    the partials and the dgamma / dbeta buffers allocated until then: autograd may drop the
-    gradients it did not ask for)."""
+class _Affine(NamedTuple):
+    """One LayerNorm group's dgamma / dbeta reduction: the fixed-order sums of the per-block
+    partial rows, reduce_rows_ptr(pairs, nblk, 1, N, N, 0).  `pairs` are raw pointers, not
+    tensors: a reference to dgamma / dbeta would make autograd's AccumulateGrad copy them (use
+    count > 1) instead of taking them over.  `grads` are the dgamma / dbeta TENSORS while the
+    record stays inside the backward function that built it; one that outlives it (held,
+    deferred) is `stored()`: it keeps their storages instead (_keep), so that the buffers stay
+    allocated until the launch is enqueued (autograd may drop the gradients it did not ask for)."""
+    pairs: list
+    nblk: int
+    N: int
+    part: list    # the partial-row tensors the reduction reads
+    params: list  # reported produced once the reduction is enqueued
+    grads: list
+
+    def stored(self):
+        return self._replace(grads=_keep(self.grads))
+
+
+def _affine(part, dg, db, nblk, N, params):
     G = len(part)
     pairs = _ptr_pairs([(part[g], dg[g]) for g in range(G)] + [(part[g], db[g], nblk * N) for g in range(G)])
+    return _Affine(pairs, nblk, N, list(part), list(params), list(dg) + list(db))
+
+
+def _affine_reduce(rec, defer):
+    """Launch the reduction on the current stream and report its parameters — or (defer; rec
+    stored()) collect it on the current stream for flush_deferred_affine."""
     if not defer:
-        reduce_rows_ptr(pairs, nblk, 1, N, N, 0)
-        params_produced(params)
+        reduce_rows_ptr(rec.pairs, rec.nblk, 1, rec.N, rec.N, 0)
+        params_produced(rec.params)
         return
-    _affine_defer(torch.cuda.current_stream(), (pairs, nblk, N, list(part) + _keep(list(dg) + list(db)),
-                                                list(params)))
-    task = torch._C._current_graph_task_id()  # one flush callback per backward (a backward that
-    if _flush_queued[0] != task:               # raised before its callbacks leaves no stale flag)
-        _flush_queued[0] = task
+    st = torch.cuda.current_stream()
+    _backward().affine.setdefault(st.cuda_stream, (st, []))[1].append(rec)
+
+
+def _affine_finish(part, dg, db, nblk, N, params, defer):
+    """A LayerNormAdd's own dgamma / dbeta reduction: now, or (defer) launched with the other
+    deferred reductions by flush_deferred_affine, which a final backward callback (one per
+    backward) runs at the latest."""
+    _affine_reduce(_affine(part, dg, db, nblk, N, params).stored(), defer)
+    bw = _backward()
+    if defer and not bw.flush_queued:
+        bw.flush_queued = True
         torch.autograd.Variable._execution_engine.queue_callback(flush_deferred_affine)
 
 
-def _affine_defer(st, entry):
-    """Collect one deferred reduction on stream st.  Entries left by a backward that raised
-    before its final callbacks (their gradients are void) are dropped, never launched later."""
-    global _affine_task
-    task = torch._C._current_graph_task_id()
-    if task != _affine_task:
-        _affine_pending.clear()
-        _affine_task = task
-    _affine_pending.setdefault(st.cuda_stream, (st, []))[1].append(entry)
-
-
 def flush_deferred_affine():
-    """Launch every collected affine reduction on the side stream it was deferred on, grouped
-    by (blocks, width), and report its parameters as produced.  Entries of another backward
-    (one that raised before its final callbacks: its gradients are void) are dropped."""
-    _flush_queued[0] = None
-    if not _affine_pending:
-        return
-    if _affine_task != torch._C._current_graph_task_id():
-        _affine_pending.clear()
-        return
-    pend = list(_affine_pending.values())
-    _affine_pending.clear()
-    for side, entries in pend:
+    """Launch every collected affine reduction on the stream it was deferred on, grouped by
+    (blocks, width), and report its parameters as produced.  Only the current backward's:
+    outside the backward that deferred them there is nothing left to launch (_backward)."""
+    bw = _backward()
+    bw.flush_queued = False
+    pend, bw.affine = list(bw.affine.values()), {}
+    for side, recs in pend:
         with torch.cuda.stream(side):
             groups = {}
-            for pairs, nblk, N, _, params in entries:
-                g = groups.setdefault((nblk, N), ([], []))
-                g[0].extend(pairs)
-                g[1].extend(params)
+            for rec in recs:
+                g = groups.setdefault((rec.nblk, rec.N), ([], []))
+                g[0].extend(rec.pairs)
+                g[1].extend(rec.params)
             for (nblk, N), (pairs, params) in groups.items():
                 reduce_rows_ptr(pairs, nblk, 1, N, N, 0)
                 params_produced(params)
 
 
-def weight_grads(items, M=None, extra=None, ready=None, holdable=False):
+class _WgradItem(NamedTuple):
+    dY: torch.Tensor  # [M, out]
+    X: torch.Tensor   # [M, in]
+    alpha: float
+    W: torch.Tensor   # the parameters: dW like W, db like bias
+    bias: object      # None / False: no bias gradient; True: one without its parameter at hand
+    bias_scale: float
+
+
+class _Held(NamedTuple):
+    """A held section.  It keeps the operands, raw-pointer problems and the gradients' STORAGES
+    only: a reference to a returned gradient tensor would make autograd copy it (unwritten)."""
+    items: list   # [_WgradItem]
+    affine: Optional[_Affine]  # stored()
+    specs: list   # _wgrad_specs
+    grads: list   # storages of the returned (dW, db)
+
+
+def weight_grads(items, extra=None, ready=None, holdable=False):
     """dW_g = alpha_g * dY_g^T X_g  (TN layout, split-K) and db_g = bias_scale_g * colsum(dY_g),
     the bias gradient fused into the same GEMM (its first column tile sums the dY slices).
 
     items: list of (dY[M,out], X[M,in], alpha, W, bias[, bias_scale]) -> [(dW, db)]; W and
     bias are the parameters (bias None / False: no bias gradient; True: a bias gradient
     without its parameter at hand).  bias_scale defaults to alpha; it differs when alpha
-    scales the INPUT X (v from kv/2: dWv = dV^T (kv/2) but dbv = colsum(dV))."""
-    def run(defer=False, sk=0):
-        out = _weight_grads(items, sk)
-        params_produced([p for it in items for p in (it[3], it[4])])
-        _run_extra(extra, defer)
-        return out
-
+    scales the INPUT X (v from kv/2: dWv = dV^T (kv/2) but dbv = colsum(dV)).
+    extra: the _Affine reduction of the layer's LayerNorm, riding in this section."""
+    items = [_WgradItem(*it) if len(it) == 6 else _WgradItem(*it, it[2]) for it in items]
     # a parameter that already holds a .grad gets the new gradient added by autograd as soon
     # as this returns (ordered on the current stream only), and so does a non-leaf parameter
     # view (precision.fp32_compute's p.float(): its cast backward reads the gradient at once):
     # compute on the current stream
-    params = [it[3] for it in items] + [it[4] for it in items if torch.is_tensor(it[4])] + \
-        list(extra[2] if extra is not None else ())
+    params = [it.W for it in items] + [it.bias for it in items if torch.is_tensor(it.bias)] + \
+        list(extra.params if extra is not None else ())
     if _settle_reuse(params) or not _WGRAD_SIDE or _LIBRARY_MODE or not all(_plain_leaf(p) for p in params):
-        return run()
-    dev = items[0][0].device
+        return _wgrad_section(items, extra)
+    dev = items[0].dY.device
     main = torch.cuda.current_stream(dev)
     side = _side_stream(dev)
+    bw = _backward()
     _mark_unsettled(params)
-    if _WGRAD_HOLD_FRAC > 0:
-        task = torch._C._current_graph_task_id()
-        if _held["task"] != task:  # (held sections of a backward that raised are void)
-            if _held["task"] is not None and _held["count"] > 0:
-                _held["last_total"] = _held["count"]
-            # only a backward that begins with the SCA blocks' sections holds (config 2); one that
-            # begins elsewhere (config 3: fusion, residual network) forks every section
-            _held.update(task=task, n=0, count=0, entries=[], hold=_hold_count() if holdable else 0)
-    late_sk = 0
+    if bw.hold is None:
+        # only a backward that begins with the SCA blocks' sections holds (config 2); one that
+        # begins elsewhere (config 3: fusion, residual network) forks every section
+        bw.hold = _hold_count(bw.last_total) if holdable else 0
+    sk_late = 0
     if _WGRAD_HOLD_FRAC > 0 and holdable:
-        _held["count"] += 1
-        hold = _held["hold"]
-        if _WGRAD_LATE_SK and hold > 0 and _held["count"] > _WGRAD_LATE_FROM * _held["last_total"]:
-            late_sk = _WGRAD_LATE_SK
-        if _held["n"] < hold:
+        bw.count += 1
+        if _WGRAD_LATE_SK and bw.hold > 0 and bw.count > _WGRAD_LATE_FROM * bw.last_total:
+            sk_late = _WGRAD_LATE_SK
+        if bw.n_held < bw.hold:
             # held: the gradients are allocated and returned now, their launches issued together
-            # with the following held sections' at the last one's fork (or at the join).  The
-            # entry keeps the operands, raw-pointer problems and the gradients' STORAGES only:
-            # a reference to a returned gradient tensor would make autograd copy it (unwritten)
-            _held["n"] += 1
+            # with the following held sections' at the last one's fork (or at the join)
+            bw.n_held += 1
             out = _wgrad_alloc(items)
-            ex = None if extra is None else (extra[0], extra[1], extra[2], extra[3] if len(extra) > 3 else None,
-                                             _keep(extra[4]))
-            _held["entries"].append((items, ex, _wgrad_specs(items, out),
-                                     _keep([t for o in out for t in o])))
-            if _held["n"] == hold:
+            _record_on(side, items, extra, out)
+            bw.held.append(_Held(items, extra and extra.stored(), _wgrad_specs(items, out),
+                                 _keep([t for o in out for t in o])))
+            if bw.n_held == bw.hold:
                 _flush_held(main, side, ready)
             _queue_join(main, side)
             return out
-    if ready is not None:
-        side.wait_event(ready)  # dY and X were ready at this point of the main stream
-    else:
-        side.wait_stream(main)  # dY and X are ready on the main stream
-    note_fork(side, main, "weight-gradient side stream")
+    _fork(side, main, ready, "weight-gradient side stream")
     _record_on(side, items, extra)
     with torch.cuda.stream(side):
-        out = run(defer=_AFFINE_DEFER, sk=late_sk)
+        out = _wgrad_section(items, extra and extra.stored(), defer=_AFFINE_DEFER, sk_late=sk_late)
     _queue_join(main, side)
     return out
 
 
-def _run_extra(extra, defer):
-    """The LayerNorm affine reduction riding in a weight-gradient section: now, or deferred."""
-    if extra is None:
-        return
-    if defer and len(extra) > 3:
-        pairs, nblk, N = extra[3]
-        _affine_defer(torch.cuda.current_stream(), (pairs, nblk, N, list(extra[1]) + _keep(extra[4]), list(extra[2])))
+def _fork(side, main, ready, name):
+    if ready is not None:
+        side.wait_event(ready)  # dY and X were ready at this point of the main stream
     else:
-        extra[0]()
-        params_produced(extra[2])
+        side.wait_stream(main)  # dY and X are ready on the main stream
+    note_fork(side, main, name)
 
 
-def _record_on(side, items, extra, outs=()):
-    """Keep the section's operands (and gradient buffers written there) from being reused by
-    the main stream before the side stream's launches have run."""
-    for it in items:
-        it[0].record_stream(side)
-        it[1].record_stream(side)
-    for t in (extra[1] if extra is not None else ()):
-        t.record_stream(side)
-    for t in (extra[4] if extra is not None else ()):  # dgamma / dbeta, written on the side stream
-        t.record_stream(side)
-    for dW, db in outs:
-        dW.record_stream(side)
-        if db is not None:
-            db.record_stream(side)
+def _record_on(side, items, affine, outs=()):
+    """Keep the section's operands, and the gradient buffers of the main stream's pool that are
+    written on the side stream, from being reused by the main stream before the side stream's
+    launches have run."""
+    ts = [t for it in items for t in (it.dY, it.X)] + [t for o in outs for t in o]
+    if affine is not None:
+        ts += affine.part + affine.grads
+    for t in ts:
+        if t is not None:
+            t.record_stream(side)
 
 
 # SCA_WGRAD_HOLD=n (A/B): the first n weight-gradient sections of a backward are not forked one
 # by one: their launches are issued together (problems of equal shape across sections in one
 # grouped launch) at the n-th section's fork — one fork marker instead of n, fuller launches
+# (the merge is the gain: held sections keeping their own launches measured 1.001)
 # SCA_WGRAD_HOLD=n (an integer: n sections) or a fraction f < 1 (the first f of the previous
 # backward's sections; the first backward holds none)
 _WGRAD_HOLD_FRAC = float(os.environ.get("SCA_WGRAD_HOLD", "0.5"))
-_WGRAD_HOLD_MERGE = os.environ.get("SCA_WGRAD_HOLD_MERGE", "1") != "0"
 # SCA_WGRAD_LATE_SK=k, SCA_WGRAD_LATE_FROM=f: in a backward that holds (one beginning with the
 # SCA blocks), the sections after the first f of the previous backward's — the ones whose
 # launches end up running alone after the main stream — at split-K k when their rule gave less
@@ -1083,79 +1077,57 @@ _WGRAD_HOLD_MERGE = os.environ.get("SCA_WGRAD_HOLD_MERGE", "1") != "0"
 _WGRAD_LATE_SK = int(os.environ.get("SCA_WGRAD_LATE_SK", "3"))
 _WGRAD_LATE_FROM = float(os.environ.get("SCA_WGRAD_LATE_FROM", "0.55"))
 
-_held = {"task": None, "n": 0, "count": 0, "entries": [], "hold": 0, "last_total": 0}
 
-
-def _hold_count():
+def _hold_count(last_total):
     if _WGRAD_HOLD_FRAC >= 1:
         return int(_WGRAD_HOLD_FRAC)
-    return int(round(_WGRAD_HOLD_FRAC * _held["last_total"]))
+    return int(round(_WGRAD_HOLD_FRAC * last_total))
 
 
 def flush_held():
     """Issue any held weight-gradient sections now (the data-parallel reducer's finish: every
     gradient must have been produced before it reduces the last buckets)."""
-    if _held["entries"]:
-        dev = _held["entries"][0][0][0][0].device
-        main = torch.cuda.current_stream(dev)
-        _flush_held(main, _side_stream(dev))
+    held = _backward().held
+    if held:
+        dev = held[0].items[0].dY.device
+        _flush_held(torch.cuda.current_stream(dev), _side_stream(dev))
 
 
 def _flush_held(main, side, ready=None):
     """Launch the held weight-gradient sections on the side stream, forked at `ready` (else at
-    the main stream's current point)."""
-    ents = _held["entries"]
-    _held["entries"] = []
-    if not ents or _held["task"] != torch._C._current_graph_task_id():
+    the main stream's current point); equal shapes across the sections share launches."""
+    bw = _backward()
+    held, bw.held = bw.held, []
+    if not held:
         return
-    if ready is not None:
-        side.wait_event(ready)
-    else:
-        side.wait_stream(main)
-    note_fork(side, main, "weight-gradient side stream (held sections)")
-    for items, ex, _, stores in ents:
-        _record_on(side, items, None)
-        for t in (ex[1] if ex is not None else ()):
-            t.record_stream(side)
-        for st in stores + (list(ex[4]) if ex is not None else []):  # gradients written on the side stream
-            torch.empty(0, device=items[0][0].device).set_(st).record_stream(side)
+    _fork(side, main, ready, "weight-gradient side stream (held sections)")
     with torch.cuda.stream(side):
-        if _WGRAD_HOLD_MERGE:  # equal shapes across the held sections share launches
-            _wgrad_launch([sp for _, _, specs, _ in ents for sp in specs])
-        else:  # each section's own launches, issued back to back
-            for _, _, specs, _ in ents:
-                _wgrad_launch(specs)
-        for items, ex, _, _ in ents:
-            params_produced([p for it in items for p in (it[3], it[4])])
-            if ex is None:
-                continue
-            if _AFFINE_DEFER and ex[3] is not None:
-                pairs, nblk, N = ex[3]
-                _affine_defer(torch.cuda.current_stream(), (pairs, nblk, N, list(ex[1]) + list(ex[4]), list(ex[2])))
-            else:
-                ex[0]()
-                params_produced(ex[2])
+        _wgrad_launch([sp for h in held for sp in h.specs])
+        for h in held:
+            params_produced([p for it in h.items for p in (it.W, it.bias)])
+            if h.affine is not None:
+                _affine_reduce(h.affine, _AFFINE_DEFER)
 
 
-def _weight_grads(items, sk=0):
-    """Allocate the gradients and launch the grouped split-K TN GEMMs -> [(dW, db)]."""
+def _wgrad_section(items, affine, defer=False, sk_late=0):
+    """One section on the current stream: allocate the gradients, launch the grouped split-K TN
+    GEMMs and the riding affine reduction (now, or deferred) -> [(dW, db)]."""
     out = _wgrad_alloc(items)
-    _wgrad_launch(_wgrad_specs(items, out), sk)
+    _wgrad_launch(_wgrad_specs(items, out), sk_late)
+    params_produced([p for it in items for p in (it.W, it.bias)])
+    if affine is not None:
+        _affine_reduce(affine, defer)
     return out
-
-
-def _norm_items(items):
-    return [it if len(it) == 6 else tuple(it) + (it[2],) for it in items]
 
 
 def _wgrad_alloc(items):
     out = []
-    for dY, X, alpha, W, bias, _ in _norm_items(items):
-        dW = param_grad_empty(W)
-        if torch.is_tensor(bias):
-            db = param_grad_empty(bias)
+    for it in items:
+        dW = param_grad_empty(it.W)
+        if torch.is_tensor(it.bias):
+            db = param_grad_empty(it.bias)
         else:
-            db = torch.empty(W.shape[0], device=W.device, dtype=W.dtype) if bias else None
+            db = torch.empty(it.W.shape[0], device=it.W.device, dtype=it.W.dtype) if it.bias else None
         out.append((dW, db))
     return out
 
@@ -1164,38 +1136,34 @@ def _wgrad_specs(items, out):
     """One (shape key, problem) per item; the problem holds raw pointers only (no tensor
     references: a held section must not raise its gradients' use count)."""
     specs = []
-    for (dY, X, alpha, W, _, bscale), (dW, db) in zip(_norm_items(items), out):
-        n_out, n_in = W.shape
-        Mr = dY.shape[0]
-        specs.append(((n_out, n_in, Mr), _prob([_seg(dY, X, n_out, n_in, Mr, alpha)], dW, n_out, n_in, n_in,
-                                              bias_grad=db, bias_grad_scale=bscale / alpha)))
+    for it, (dW, db) in zip(items, out):
+        n_out, n_in = it.W.shape
+        Mr = it.dY.shape[0]
+        specs.append(((n_out, n_in, Mr), _prob([_seg(it.dY, it.X, n_out, n_in, Mr, it.alpha)], dW, n_out, n_in, n_in,
+                                              bias_grad=db, bias_grad_scale=it.bias_scale / it.alpha)))
     return specs
 
 
-def _wgrad_launch(specs, sk_late=0):
-    """Grouped launches of the weight-gradient problems: equal (out, in, rows) shapes share a
-    launch (up to GEMM_MAX_PROBLEMS), the kernel variant and split-K chosen per launch."""
-    if not specs:
-        return
+def _wgrad_plan(keys, sk_late=0):
+    """The launches of weight-gradient problems of shapes keys = [(n_out, n_in, rows)], in issue
+    order: [(indices into keys, kernel variant, split-K)].  Equal shapes share a launch (up to
+    GEMM_MAX_PROBLEMS); the variant and split-K are chosen per launch.  Policy only: no tensor,
+    no library call."""
     by_shape = {}
-    for key, prob in specs:
-        n_out, n_in, Kr = key
-        # the k-split kernel (variant 46) takes problems of different shapes in one flat grid:
-        # they share a launch by reduction length alone (an FFN's fc1 and fc2 weight gradients)
-        mixed = _TNR_MIXED and _TNR and Kr % 64 == 0 and Kr >= 128 and not (0 < _TNB_MIN_K <= Kr)
-        by_shape.setdefault((0, 0, Kr) if mixed else key, []).append((key, prob))
-    launches = []
-    for (_, _, Kr), allkp in by_shape.items():
-        for c in range(0, len(allkp), L.GEMM_MAX_PROBLEMS):
-            subk = allkp[c:c + L.GEMM_MAX_PROBLEMS]
-            sub = [pr for _, pr in subk]
-            n_out, n_in = max(k[0] for k, _ in subk), max(k[1] for k, _ in subk)
-            tiles = sum(((k[0] + 63) // 64) * ((k[1] + 63) // 64) for k, _ in subk)
-            sk = _splitk_for(Kr, tiles)
-            tile = 0
+    for i, key in enumerate(keys):
+        by_shape.setdefault(key, []).append(i)
+    plan = []
+    for (n_out, n_in, Kr), idx in by_shape.items():
+        for c in range(0, len(idx), L.GEMM_MAX_PROBLEMS):
+            sub = idx[c:c + L.GEMM_MAX_PROBLEMS]
+            tiles = len(sub) * ((n_out + 63) // 64) * ((n_in + 63) // 64)
+            tile, sk = 0, _splitk_for(Kr, tiles)
             if 0 < _TNB_MIN_K <= Kr and Kr % 64 == 0:
-                tile = 43
-                sk = _tnb_split(Kr, len(sub) * -(-n_out // 128) * -(-n_in // 128))
+                # tile 43 at split 1 — one long workgroup per output tile, the fewest workgroups
+                # holding CUs beside the critical chain (config 5: +0.5 % in step over the split
+                # of least estimated per-CU time, whose FFN choice of split 4 is faster alone;
+                # profiles/r05_misc/tnb_split_cfg5_ab.txt)
+                tile, sk = 43, 1
             elif _TNR and Kr % 64 == 0 and Kr >= 128:
                 # the k-split kernel with the register-staged, interleaved operand stream (variant
                 # 46): 6-20 % faster than both the LDS-DMA k-split (36) and the plain LDS-DMA
@@ -1205,12 +1173,8 @@ def _wgrad_launch(specs, sk_late=0):
                 # problems are FFN-sized (config 2's 4 x (768, 256): +0.6 % in step over 2); the
                 # many small problems of config 3's attention (12 x (256, 256)) run better at 2
                 # in step (+1.1 %, profiles/r05_misc/tnr_split_rule_ab.txt) though 4 is faster alone
-                big = all(k[0] * k[1] >= 768 * 256 for k, _ in subk)
+                big = n_out * n_in >= 768 * 256
                 tile, sk = 46, (4 if tiles * 4 == 768 and Kr >= 2048 and big else (2 if Kr >= 512 else 1))
-                if _TNR_MIXED_SK and len({k for k, _ in subk}) > 1 and Kr // _TNR_MIXED_SK >= 256:
-                    sk = _TNR_MIXED_SK
-                if _TNR_SK and Kr // _TNR_SK >= 256:
-                    sk = _TNR_SK
                 if sk_late and sk < sk_late and Kr // sk_late >= 256:  # raise only
                     sk = sk_late
             elif (len(sub) >= 8 and tiles >= 256) or tiles >= _TNK_TILES_PER_PROBLEM * len(sub):
@@ -1220,12 +1184,19 @@ def _wgrad_launch(specs, sk_late=0):
                 # the 64x64 LDS-DMA kernel at split 3; the FFN launches at split 2 instead of 4
                 # write half the partial slabs, same step time; profiles/r04_probe/ab_tnk_ffn.txt)
                 tile, sk = 36, min(sk, 2)
-            wsz = sum(sk * (k[0] * k[1] + k[0]) for k, _ in subk)
-            ws = torch.empty(wsz, device=torch.device("cuda", torch.cuda.current_device()),
-                             dtype=torch.float32) if sk > 1 else None
-            launches.append((sub, sk, ws, tile))
-    for p, k, w, tl in launches:
-        gemm(L.GEMM_TN, p, splitk=k, ws=w, tile=tl)
+            plan.append((sub, tile, sk))
+    return plan
+
+
+def _wgrad_launch(specs, sk_late=0):
+    """Launch the (shape key, problem) specs as _wgrad_plan groups them: every launch's split-K
+    workspace is allocated first, then the launches are issued."""
+    plan = _wgrad_plan([key for key, _ in specs], sk_late)
+    dev = torch.device("cuda", torch.cuda.current_device()) if plan else None
+    ws = [torch.empty(sk * sum(specs[i][0][0] * (specs[i][0][1] + 1) for i in idx), device=dev, dtype=torch.float32)
+          if sk > 1 else None for idx, _, sk in plan]
+    for (idx, tile, sk), w in zip(plan, ws):
+        gemm(L.GEMM_TN, [specs[i][1] for i in idx], splitk=sk, ws=w, tile=tile)
 
 
 def sum_tensors(groups):

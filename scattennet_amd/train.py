@@ -43,8 +43,7 @@ def train_step(model, optimizer, src_input):
         # weight gradients held back for the side stream and deferred LayerNorm-affine
         # reductions are normally launched by the backward's final callback; a backward that
         # left some behind must not reach the update without them
-        ops.flush_held()
-        ops.flush_deferred_affine()
+        ops.flush_pending()
     except BaseException:
         try:
             ops.fork_ledger_end()

@@ -1,7 +1,7 @@
 """A backward that raises before its final callbacks (a user hook throwing at its very end, after
 every weight-gradient section) must not poison the next one: the side-stream join and the
-deferred LayerNorm affine reductions are keyed by the autograd graph task (ops._queue_join,
-ops._affine_defer), so the next backward queues its own join / flush and drops the failed
+deferred LayerNorm affine reductions belong to the autograd graph task's state
+(ops._backward), so the next backward queues its own join / flush and drops the failed
 one's pending reductions.  Checked bitwise against a clean backward (the kernels are
 deterministic)."""
 import pytest
@@ -87,7 +87,7 @@ def test_stale_reductions_are_dropped_when_the_next_backward_defers_nothing():
             p.grad = ref[n].clone()
     held = _grads(model)
     ops.flush_deferred_affine()  # outside any backward: must drop, not launch
-    assert not ops._affine_pending
+    assert not ops._bwd.affine and not ops._bwd.held and not ops._bwd.joins and not ops._bwd.flush_queued
     torch.cuda.synchronize()
     for n, g in _grads(model).items():
         assert torch.equal(g, held[n]), n
@@ -101,13 +101,20 @@ def test_stale_reductions_are_dropped_when_the_next_backward_defers_nothing():
 
 def _reference_grads(model, run):
     """The same backward with every gradient written in place on the calling stream (no side
-    stream, no deferred reductions)."""
+    stream, no deferred reductions) — checked: the fork ledger sees no fork or join, and
+    nothing is left held or deferred."""
     from scattennet_amd import ops
     side, defer = ops._WGRAD_SIDE, ops._AFFINE_DEFER
     ops._WGRAD_SIDE, ops._AFFINE_DEFER = False, False
     try:
         model.zero_grad(set_to_none=True)
-        out = run()
+        ledger = ops.fork_ledger_begin()
+        try:
+            out = run()
+        finally:
+            ops.fork_ledger_end()
+        assert ledger.seq == 0 and not ledger.last_fork and not ledger.last_join
+        assert not ops._bwd.held and not ops._bwd.affine
         torch.cuda.synchronize()
         return _grads(model), out
     finally:
@@ -228,4 +235,50 @@ def test_held_weight_gradient_sections_match_the_in_place_path(hold, monkeypatch
         assert set(got) == set(ref)
         for n, g in got.items():
             assert torch.equal(g, ref[n]), n
-    assert not ops._held["entries"]
+    assert not ops._bwd.held
+
+
+def test_a_backward_that_begins_elsewhere_holds_nothing_and_the_next_one_holds():
+    """Only a backward whose first weight-gradient section is holdable holds.  One that begins
+    with a plain linear head forks every section, and still counts its holdable sections: the
+    next backward, beginning with an SCA block, holds the first half of that count.  Both
+    bitwise equal to the in-place path."""
+    from scattennet_amd import ops
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    model, kp, mask, gout = _setup(seed=7)
+    G, d = len(gout), gout[0].shape[-1]
+    torch.manual_seed(13)
+    head = torch.nn.ModuleList([torch.nn.Linear(d, d) for _ in range(G)]).to(kp.device)
+    both = torch.nn.ModuleList([model, head])
+
+    def run_headed():
+        outs = ops.LinearResidual.apply(G, False, *model(kp, mask), *[h.weight for h in head],
+                                        *[h.bias for h in head])
+        torch.autograd.backward(outs, [gout[g] for g in range(G)])
+
+    def run_plain():
+        outs = model(kp, mask)
+        torch.autograd.backward(outs, [gout[g] for g in range(G)])
+
+    assert 0 < ops._WGRAD_HOLD_FRAC < 1  # the default: a fraction of the previous backward's sections
+    ref_headed, _ = _reference_grads(both, run_headed)
+    ref_plain, _ = _reference_grads(model, run_plain)
+
+    def check(module, ref):
+        torch.cuda.synchronize()
+        got = _grads(module)
+        assert set(got) == set(ref)
+        for n, g in got.items():
+            assert torch.equal(g, ref[n]), n
+        module.zero_grad(set_to_none=True)
+
+    run_headed()
+    check(both, ref_headed)
+    total = ops._bwd.count
+    assert total > 0 and ops._bwd.hold == 0 and ops._bwd.n_held == 0
+    run_plain()
+    check(model, ref_plain)
+    assert ops._bwd.last_total == total and ops._bwd.count == total
+    assert ops._bwd.hold == ops._bwd.n_held == int(round(ops._WGRAD_HOLD_FRAC * total)) > 0
+    assert not ops._bwd.held

@@ -2,7 +2,7 @@
 environment, library / source digests and result recorded.
 
     python tools/ab.py --out r06_x --reps 2 --steps 40 --workload cfg2 \\
-        -v base: -v sk1:SCA_TNR_SK=1 -v prev:SCA_LIB_PATH=tools/lib_prev.so \\
+        -v base: -v late0:SCA_WGRAD_LATE_SK=0 -v prev:SCA_LIB_PATH=tools/lib_prev.so \\
         -v nofan:@ops._FAN_OUT=False
 
 A variant is `name:` followed by comma-separated settings: `KEY=VALUE` sets an environment
