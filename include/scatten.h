@@ -37,6 +37,8 @@
  *   sca_clamp              RecognitionHead logit clamp(+-50) (model/__init__.py:54-58)
  *   sca_lstm_cell_fwd/bwd  AlignmentModule's bidirectional nn.LSTM cell
  *                          (model/alignment_module.py:24-30, :68-69)
+ *   sca_*_valid_fwd/bwd    the softmax, SeqKD and LSTM cell above restricted to a device-side
+ *                          valid-frame count (batches padded to a length bucket)
  *   sca_optim_grad_sqnorm  torch.nn.utils.clip_grad_norm_(model.parameters(), 1.0)
  *   sca_optim_scale_grads  (opt.py:34) and the NaN-loss test of opt.py:32
  *   sca_optim_adam_step    optimizer.step() (opt.py:35) of the torch.optim.Adam built by
@@ -396,6 +398,23 @@ typedef struct {
 int sca_softmax_rows_fwd(int nprob, const sca_softmax_problem* probs, int rows, int N, void* stream);
 int sca_softmax_rows_bwd(int nprob, const sca_softmax_problem* probs, int rows, int N, void* stream);
 
+/* ---- valid-frame variants (length-bucketed batches) ----
+ * A batch padded beyond its own longest clip to a fixed bucket length must not let the extra
+ * frames reach the valid ones.  Three ops would (this softmax, SeqKD, the LSTM's reverse
+ * direction); their *_valid entry points take
+ *   valid_frames  device pointer to ONE int32: the batch's unpooled longest length,
+ *   shift         the number of MaxPool1d(2, 2) stages in front of the op,
+ * and use nv = clamp(*valid_frames >> shift, 1, T) as the valid length at the op (floor-halving
+ * k times is >> k).  The scalar is read on the device: no host read, no allocation, and a
+ * graph replay sees whatever the host last copied there.  With nv == T each variant computes
+ * bitwise what its plain entry point does.
+ *
+ * sca_softmax_rows_valid_fwd: softmax over columns [0, nv) of every row; columns [nv, N) are
+ * written as exact 0.  Its backward is sca_softmax_rows_bwd unchanged: y = 0 gives
+ * dx = y * (dy - sum) = 0 there, and the row sum only collects the valid columns.          */
+int sca_softmax_rows_valid_fwd(int nprob, const sca_softmax_problem* probs, int rows, int N,
+                               const int* valid_frames, int shift, void* stream);
+
 /* Elementwise GELU backward: dz = dy * gelu_erf'(z) over n elements (the pre-activation z
  * is what the GEMM GELU epilogue stored).                                               */
 typedef struct {
@@ -611,6 +630,16 @@ int sca_seqkd_fwd(const float* student, const float* teacher, int R, int C, int 
                   float lo, float hi, float* loss, float* ws, void* stream);
 int sca_seqkd_bwd(const float* student, const float* teacher, int R, int C, int start, float temp,
                   const float* dloss, const float* ws, float* dstudent, float* dteacher, void* stream);
+/* Valid-frame variants (see sca_softmax_rows_valid_fwd): the R rows are (b, t) with t = r % T
+ * (R a multiple of T); only rows with t < nv contribute, the divisor is (R / T) * nv, and the
+ * backward writes exact zeros into the rows with t >= nv.  Same fixed-order reduction (the
+ * skipped rows add exact zeros), same workspace.                                           */
+int sca_seqkd_valid_fwd(const float* student, const float* teacher, int R, int C, int start, float temp,
+                        float weight, float lo, float hi, float* loss, float* ws, int T, const int* valid_frames,
+                        int shift, void* stream);
+int sca_seqkd_valid_bwd(const float* student, const float* teacher, int R, int C, int start, float temp,
+                        const float* dloss, const float* ws, float* dstudent, float* dteacher, int T,
+                        const int* valid_frames, int shift, void* stream);
 
 /* torch.clamp(x, lo, hi) over n elements (dy == NULL; a NaN stays a NaN), or its backward
  * dx = dy * [lo <= x <= hi] */
@@ -629,6 +658,17 @@ int sca_lstm_cell_fwd(const float* gates, float* act, float* c, float* y, float*
                       int step, void* stream);
 int sca_lstm_cell_bwd(const float* dh, const float* dy, const float* act, const float* c, float* dc, float* dg,
                       int B, int T, int H, int ndir, int step, void* stream);
+/* Valid-frame variants (see sca_softmax_rows_valid_fwd).  The caller still issues T steps (the
+ * launch count of a captured graph is fixed).  fwd, frame t >= nv: c = y = 0, zero
+ * activations, and the hp of the frame the direction visits next = 0 — so direction 1 reaches
+ * t = nv-1 with zero state, which is step 0 of an unpadded run (the recurrent GEMM over h = 0
+ * gives b_hh + G_t in both).  bwd, frame t >= nv: dg = 0, dc = 0, the incoming dh is ignored;
+ * at t = nv-1 the step then sees dh = dY_t + 0 and dc = 0, again the unpadded step 0.      */
+int sca_lstm_cell_valid_fwd(const float* gates, float* act, float* c, float* y, float* hp, int B, int T, int H,
+                            int ndir, int step, const int* valid_frames, int shift, void* stream);
+int sca_lstm_cell_valid_bwd(const float* dh, const float* dy, const float* act, const float* c, float* dc,
+                            float* dg, int B, int T, int H, int ndir, int step, const int* valid_frames, int shift,
+                            void* stream);
 
 /* ---- training update: gradient clip + Adam over every parameter tensor in two launches ----
  * Replaces clip_grad_norm_(model.parameters(), max_norm) + optimizer.step() (opt.py:34-35)

@@ -20,6 +20,7 @@ from .decode import (ctc_decode, ctc_decode_device, ctc_greedy_decode_device, de
 from .optim import FusedAdam, WarmupCosineAnnealingScheduler, build_optimizer, clip_grad_norm_  # noqa: F401
 from .model import MSCA_Net, finite_flags, first_error  # noqa: F401
 from .train import read_report, train_step  # noqa: F401
+from .bucketed import BucketedTrainStep, pad_batch  # noqa: F401
 from . import library  # noqa: F401  (torch.ops.scatten.*)
 from .utils import KeyPaddingMask, create_attention_mask, create_causal_attention_mask, key_padding_mask  # noqa: F401
 

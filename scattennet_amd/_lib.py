@@ -166,6 +166,7 @@ EXPORTS = {
     "sca_maxpool_t_bwd": ([c_int, c_void_p, c_int, c_int, c_int, c_void_p], c_int),
     "sca_softmax_rows_fwd": ([c_int, c_void_p, c_int, c_int, c_void_p], c_int),
     "sca_softmax_rows_bwd": ([c_int, c_void_p, c_int, c_int, c_void_p], c_int),
+    "sca_softmax_rows_valid_fwd": ([c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p], c_int),
     "sca_gelu_bwd": ([c_int, c_void_p, c_long, c_void_p], c_int),
     "sca_sum_tensors": ([c_int, c_void_p, c_long, c_void_p], c_int),
     "sca_dropout": ([c_int, c_void_p, c_long, c_int, c_float, c_void_p], c_int),
@@ -187,9 +188,15 @@ EXPORTS = {
                        c_void_p, c_void_p], c_int),
     "sca_seqkd_bwd": ([c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                        c_void_p], c_int),
+    "sca_seqkd_valid_fwd": ([c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_void_p,
+                             c_void_p, c_int, c_void_p, c_int, c_void_p], c_int),
+    "sca_seqkd_valid_bwd": ([c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
+                             c_void_p, c_int, c_void_p, c_int, c_void_p], c_int),
     "sca_clamp": ([c_void_p] * 4 + [c_long, c_float, c_float, c_void_p], c_int),
     "sca_lstm_cell_fwd": ([c_void_p] * 5 + [c_int] * 5 + [c_void_p], c_int),
     "sca_lstm_cell_bwd": ([c_void_p] * 6 + [c_int] * 5 + [c_void_p], c_int),
+    "sca_lstm_cell_valid_fwd": ([c_void_p] * 5 + [c_int] * 5 + [c_void_p, c_int, c_void_p], c_int),
+    "sca_lstm_cell_valid_bwd": ([c_void_p] * 6 + [c_int] * 5 + [c_void_p, c_int, c_void_p], c_int),
     "sca_ctc_decode_workspace_bytes": ([c_int] * 4, c_long),
     "sca_ctc_greedy_decode": ([c_void_p, c_void_p] + [c_int] * 3 + [c_void_p] * 5, c_int),
     "sca_ctc_beam_decode": ([c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 5, c_int),

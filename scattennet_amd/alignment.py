@@ -46,10 +46,16 @@ def _stepper(template, a_step, r_step):
 
 
 class LSTMLayer(Function):
-    """One (bi)directional LSTM layer: x (B, T, In) -> y (B, T, D*H)."""
+    """One (bi)directional LSTM layer: x (B, T, In) -> y (B, T, D*H).
+
+    An optional last argument `valid=(valid_frames, shift)` behind the 4*D parameters (a batch
+    padded to a length bucket): the frames t >= valid_frames >> shift hold zero state, so the reverse direction enters the valid
+    frames as an unpadded run does (`sca_lstm_cell_valid_fwd/bwd`).  The loops still issue T
+    steps: the launch count does not depend on the device scalar."""
 
     @staticmethod
     def forward(ctx, D, x, *params):
+        params, valid = (params[:4 * D], params[4 * D]) if len(params) == 4 * D + 1 else (params, None)
         x = x.contiguous()
         L.require_device(x)
         B, T, In = x.shape
@@ -71,11 +77,18 @@ class LSTMLayer(Function):
             tpl = _prob([_seg(hp[:, t0, d * H:], w_hh[d], T * D * H, H, H)], gt[:, d * 4 * H:], B, 4 * H, D * 4 * H,
                         bias=b_hh[d], resid=G[:, t0, d * 4 * H:], ldr=T * D * 4 * H)
             steppers.append(_stepper(tpl, 4 * dt * D * H, 4 * dt * D * 4 * H))
+        if valid is not None:
+            vf, shift = ops.check_valid(valid)
         for step in range(T):
             gemm(L.GEMM_NT, [f(step) for f in steppers], splitk=_SPLITK_FWD, ws=ws)
-            L.check(lib.sca_lstm_cell_fwd(L.ptr(gt), L.ptr(G), L.ptr(c), L.ptr(y), L.ptr(hp), B, T, H, D, step, st),
-                    "sca_lstm_cell_fwd")
+            if valid is None:
+                L.check(lib.sca_lstm_cell_fwd(L.ptr(gt), L.ptr(G), L.ptr(c), L.ptr(y), L.ptr(hp), B, T, H, D, step,
+                                              st), "sca_lstm_cell_fwd")
+            else:
+                L.check(lib.sca_lstm_cell_valid_fwd(L.ptr(gt), L.ptr(G), L.ptr(c), L.ptr(y), L.ptr(hp), B, T, H, D,
+                                                    step, L.ptr(vf), shift, st), "sca_lstm_cell_valid_fwd")
         ctx.D = D
+        ctx.valid = None if valid is None else (vf, shift)
         ctx.save_for_backward(x, G, c, hp, *params)
         return y
 
@@ -103,8 +116,13 @@ class LSTMLayer(Function):
         for step in range(T):
             if step > 0:
                 gemm(L.GEMM_NN, [f(step - 1) for f in steppers], splitk=_SPLITK_BWD, ws=ws)
-            L.check(lib.sca_lstm_cell_bwd(L.ptr(dh) if step > 0 else None, L.ptr(dy), L.ptr(act), L.ptr(c),
-                                          L.ptr(dc), L.ptr(dG), B, T, H, D, step, st), "sca_lstm_cell_bwd")
+            if ctx.valid is None:
+                L.check(lib.sca_lstm_cell_bwd(L.ptr(dh) if step > 0 else None, L.ptr(dy), L.ptr(act), L.ptr(c),
+                                              L.ptr(dc), L.ptr(dG), B, T, H, D, step, st), "sca_lstm_cell_bwd")
+            else:
+                L.check(lib.sca_lstm_cell_valid_bwd(L.ptr(dh) if step > 0 else None, L.ptr(dy), L.ptr(act), L.ptr(c),
+                                                    L.ptr(dc), L.ptr(dG), B, T, H, D, step, L.ptr(ctx.valid[0]),
+                                                    ctx.valid[1], st), "sca_lstm_cell_valid_bwd")
         dGf = dG.view(B * T, D * 4 * H)
         dx = torch.empty_like(x)
         gemm(L.GEMM_NN, [_prob([_seg(dGf[:, d * 4 * H:], w_ih[d], D * 4 * H, In, 4 * H) for d in range(D)],
@@ -118,18 +136,19 @@ class LSTMLayer(Function):
                                bias_grad=db_ih[d]) for d in range(D)])
         gemm(L.GEMM_TN, [_prob([_seg(dGf[:, d * 4 * H:], hpf[:, d * H:], D * 4 * H, D * H, B * T)], dw_hh[d], 4 * H,
                                H, H, bias_grad=db_hh[d]) for d in range(D)])
-        return (None, dx, *dw_ih, *dw_hh, *db_ih, *db_hh)
+        return (None, dx, *dw_ih, *dw_hh, *db_ih, *db_hh) + ((None,) if ctx.valid is not None else ())
 
 
-def lstm(rnn, x):
-    """nn.LSTM(batch_first=False) semantics on batch-major x (B, T, In) -> (B, T, D*H)."""
+def lstm(rnn, x, valid=None):
+    """nn.LSTM(batch_first=False) semantics on batch-major x (B, T, In) -> (B, T, D*H).
+    `valid=(valid_frames, shift)`: see LSTMLayer."""
     if rnn.proj_size or not rnn.bias:
         raise NotImplementedError("scattennet_amd LSTM: proj_size / bias=False are not used by the reference")
     D = 2 if rnn.bidirectional else 1
     for layer in range(rnn.num_layers):
         sfx = [f"_l{layer}", f"_l{layer}_reverse"][:D]
         ps = [getattr(rnn, f"{n}{s}") for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh") for s in sfx]
-        x = LSTMLayer.apply(D, x, *ps)
+        x = LSTMLayer.apply(D, x, *ps, *(() if valid is None else (valid,)))
         if layer < rnn.num_layers - 1 and rnn.training and rnn.dropout > 0:
             x = ops.dropout_grouped([x], float(rnn.dropout))[0]
     return x
@@ -153,8 +172,8 @@ class AlignmentModule(nn.Module):
         self.gloss_layer = nn.Linear(hidden_size, cls_num)
 
     @fp32_compute()
-    def forward(self, x):
+    def forward(self, x, valid=None):
         # the caller's (T, B, C) is the permute(1, 0, 2) view of a batch-major tensor
         # (model/__init__.py:52): permuting back is free
-        y = lstm(self.rnn, x.permute(1, 0, 2).contiguous())
+        y = lstm(self.rnn, x.permute(1, 0, 2).contiguous(), valid=valid)
         return ops.LinearResidual.apply(1, False, y, self.gloss_layer.weight, self.gloss_layer.bias)[0]

@@ -258,13 +258,34 @@ struct KdArgs {
   const float *s, *q;
   int R, C, start;
   float inv_temp, weight_t2, lo, hi;
+  int T;             // VALID kernels only: rows are (b, t), t = row % T, and only t < nv take part,
+  const int* valid;  // nv = clamp(*valid >> shift, 1, T) read on the device
+  int shift;
 };
 
+// the valid length of the *_valid entry points: a device scalar (a graph replay sees what the
+// host last copied there), clamped so a bad value stays in bounds
+__device__ __forceinline__ int valid_len(const int* valid, int shift, int T) {
+  const int nv = *valid >> shift;
+  return nv < 1 ? 1 : (nv > T ? T : nv);
+}
+
 // ws layout: row_loss[R] | stats[4R] (student max, log-sum, teacher max, log-sum) | dscale[1]
+// VALID: a row with t >= nv leaves a zero row loss (the fixed-order sum of the finalize kernel
+// then adds exact zeros) and zero statistics.
+template <bool VALID>
 __global__ __launch_bounds__(256) void kd_row_kernel(KdArgs a, float* ws) {
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= a.R) return;
+  if (VALID && (int)(row % a.T) >= valid_len(a.valid, a.shift, a.T)) {
+    if (lane == 0) {
+      ws[row] = 0.0f;
+      float* st = ws + a.R + 4 * row;
+      st[0] = 0.0f; st[1] = 0.0f; st[2] = 0.0f; st[3] = 0.0f;
+    }
+    return;
+  }
   const float* sr = a.s + row * a.C;
   const float* qr = a.q + row * a.C;
   float ms = NEG_INF, mq = NEG_INF;
@@ -297,6 +318,7 @@ __global__ __launch_bounds__(256) void kd_row_kernel(KdArgs a, float* ws) {
   }
 }
 
+template <bool VALID>
 __global__ __launch_bounds__(256) void kd_finalize_kernel(KdArgs a, float* ws, float* loss) {
   __shared__ float red[4];
   const int tid = threadIdx.x;
@@ -306,18 +328,28 @@ __global__ __launch_bounds__(256) void kd_finalize_kernel(KdArgs a, float* ws, f
   if ((tid & 63) == 0) red[tid >> 6] = s;
   __syncthreads();
   if (tid == 0) {
-    // batchmean over the R = B*T rows of the .view(-1, C') (loss.py:13-19), * T^2 * weight
-    const float v = (red[0] + red[1] + red[2] + red[3]) / (float)a.R * a.weight_t2;
+    // batchmean over the R = B*T rows of the .view(-1, C') (loss.py:13-19), * T^2 * weight;
+    // VALID: over the B*nv rows that took part
+    const float rows = VALID ? (float)((a.R / a.T) * valid_len(a.valid, a.shift, a.T)) : (float)a.R;
+    const float v = (red[0] + red[1] + red[2] + red[3]) / rows * a.weight_t2;
     loss[0] = fminf(fmaxf(v, a.lo), a.hi);
-    ws[5L * a.R] = (v >= a.lo && v <= a.hi) ? a.weight_t2 / (float)a.R : 0.0f;
+    ws[5L * a.R] = (v >= a.lo && v <= a.hi) ? a.weight_t2 / rows : 0.0f;
   }
 }
 
+template <bool VALID>
 __global__ __launch_bounds__(256) void kd_grad_kernel(KdArgs a, const float* ws, const float* dloss, float* ds,
                                                       float* dq) {
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= a.R) return;
+  if (VALID && (int)(row % a.T) >= valid_len(a.valid, a.shift, a.T)) {  // exact zeros behind the valid frames
+    for (int c = lane; c < a.C; c += 64) {
+      if (ds) ds[row * a.C + c] = 0.0f;
+      if (dq) dq[row * a.C + c] = 0.0f;
+    }
+    return;
+  }
   const float k = dloss[0] * ws[5L * a.R] * a.inv_temp;
   const float* st = ws + a.R + 4 * row;
   const float ms = st[0], lss = st[1], mq = st[2], lsq = st[3];
@@ -373,10 +405,15 @@ struct LstmArgs {
   const float *dh, *dy;
   float *dc, *dg;
   int B, T, H, D, step;
+  const int* valid;  // VALID kernels only: frames t >= clamp(*valid >> shift, 1, T) hold zero state
+  int shift;
 };
 
 __device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+// VALID: a step whose frame t >= nv writes c = y = 0, zero activations and a zero hp for the
+// next frame, so direction 1 reaches t = nv-1 with zero state — step 0 of an unpadded run.
+template <bool VALID>
 __global__ __launch_bounds__(256) void lstm_cell_fwd_kernel(LstmArgs a) {
   const int dir = blockIdx.y;
   const int idx = blockIdx.x * 256 + threadIdx.x;
@@ -385,6 +422,14 @@ __global__ __launch_bounds__(256) void lstm_cell_fwd_kernel(LstmArgs a) {
   const int t = dir ? a.T - 1 - a.step : a.step;
   const int tp = dir ? t + 1 : t - 1, tn = dir ? t - 1 : t + 1;
   const long row = (long)b * a.T + t;
+  if (VALID && t >= valid_len(a.valid, a.shift, a.T)) {
+    a.c[row * DH + dir * H + j] = 0.0f;
+    a.y[row * DH + dir * H + j] = 0.0f;
+    if (tn >= 0 && tn < a.T) a.hp[((long)b * a.T + tn) * DH + dir * H + j] = 0.0f;
+    float* az = a.act + row * 4 * DH + dir * 4 * H;
+    az[j] = 0.0f; az[H + j] = 0.0f; az[2 * H + j] = 0.0f; az[3 * H + j] = 0.0f;
+    return;
+  }
   const float* g = a.gates + (long)b * 4 * DH + dir * 4 * H;
   const float gi = sigm(g[j]), gf = sigm(g[H + j]), gg = tanhf(g[2 * H + j]), go = sigm(g[3 * H + j]);
   const float cp = (tp >= 0 && tp < a.T) ? a.c[((long)b * a.T + tp) * DH + dir * H + j] : 0.0f;
@@ -399,6 +444,9 @@ __global__ __launch_bounds__(256) void lstm_cell_fwd_kernel(LstmArgs a) {
 
 // backward step `step` walks t = T-1-step (dir 0) / t = step (dir 1); dh holds
 // dY_t + dG_{t'} W_hh (GEMM with the dY row as residual) except at step 0, where it is dY_t
+// VALID: a frame t >= nv writes dg = 0 and dc = 0 whatever dh holds; the step at t = nv-1 then
+// sees dh = dY_t + 0 W_hh and dc = 0, the unpadded run's step 0.
+template <bool VALID>
 __global__ __launch_bounds__(256) void lstm_cell_bwd_kernel(LstmArgs a) {
   const int dir = blockIdx.y;
   const int idx = blockIdx.x * 256 + threadIdx.x;
@@ -407,6 +455,12 @@ __global__ __launch_bounds__(256) void lstm_cell_bwd_kernel(LstmArgs a) {
   const int t = dir ? a.step : a.T - 1 - a.step;
   const int tp = dir ? t + 1 : t - 1;
   const long row = (long)b * a.T + t;
+  if (VALID && t >= valid_len(a.valid, a.shift, a.T)) {
+    float* dz = a.dg + row * 4 * DH + dir * 4 * H;
+    dz[j] = 0.0f; dz[H + j] = 0.0f; dz[2 * H + j] = 0.0f; dz[3 * H + j] = 0.0f;
+    a.dc[(long)b * DH + dir * H + j] = 0.0f;
+    return;
+  }
   const float dh = a.step == 0 ? a.dy[row * DH + dir * H + j] : a.dh[(long)b * DH + dir * H + j];
   const float dcn = a.step == 0 ? 0.0f : a.dc[(long)b * DH + dir * H + j];
   const float* ac = a.act + row * 4 * DH + dir * 4 * H;
@@ -471,33 +525,102 @@ extern "C" int sca_ctc_loss_bwd(const float* logits, const int* labels, const in
 
 extern "C" long sca_seqkd_workspace_floats(int R) { return 5L * R + 1; }
 
-extern "C" int sca_seqkd_fwd(const float* student, const float* teacher, int R, int C, int start, float temp,
-                             float weight, float lo, float hi, float* loss, float* ws, void* stream) {
-  if (R < 1 || C < 1 || start < 0 || start >= C || !(temp > 0.0f) || !student || !teacher || !loss || !ws) {
-    sca_set_error("sca_seqkd_fwd: bad arguments");
+namespace {
+
+bool valid_args_ok(int T, const int* valid, int shift) { return T >= 1 && valid && shift >= 0 && shift <= 30; }
+
+template <bool VALID>
+int seqkd_fwd(const float* student, const float* teacher, int R, int C, int start, float temp, float weight,
+              float lo, float hi, float* loss, float* ws, int T, const int* valid, int shift, void* stream,
+              const char* bad, const char* failed) {
+  if (R < 1 || C < 1 || start < 0 || start >= C || !(temp > 0.0f) || !student || !teacher || !loss || !ws ||
+      (VALID && (!valid_args_ok(T, valid, shift) || R % T != 0))) {
+    sca_set_error(bad);
     return SCA_ERR_ARG;
   }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const KdArgs a{student, teacher, R, C, start, 1.0f / temp, weight * temp * temp, lo, hi};
-  hipLaunchKernelGGL(kd_row_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, st, a, ws);
-  hipLaunchKernelGGL(kd_finalize_kernel, dim3(1), dim3(256), 0, st, a, ws, loss);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_seqkd_fwd: launch failed"); return SCA_ERR_LAUNCH; }
+  const KdArgs a{student, teacher, R, C, start, 1.0f / temp, weight * temp * temp, lo, hi, T, valid, shift};
+  hipLaunchKernelGGL(kd_row_kernel<VALID>, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, st, a, ws);
+  hipLaunchKernelGGL(kd_finalize_kernel<VALID>, dim3(1), dim3(256), 0, st, a, ws, loss);
+  if (hipGetLastError() != hipSuccess) { sca_set_error(failed); return SCA_ERR_LAUNCH; }
   return SCA_OK;
+}
+
+template <bool VALID>
+int seqkd_bwd(const float* student, const float* teacher, int R, int C, int start, float temp, const float* dloss,
+              const float* ws, float* dstudent, float* dteacher, int T, const int* valid, int shift, void* stream,
+              const char* bad, const char* failed) {
+  if (R < 1 || C < 1 || start < 0 || start >= C || !(temp > 0.0f) || !student || !teacher || !dloss || !ws ||
+      (!dstudent && !dteacher) || (VALID && (!valid_args_ok(T, valid, shift) || R % T != 0))) {
+    sca_set_error(bad);
+    return SCA_ERR_ARG;
+  }
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const KdArgs a{student, teacher, R, C, start, 1.0f / temp, 0.0f, 0.0f, 0.0f, T, valid, shift};
+  hipLaunchKernelGGL(kd_grad_kernel<VALID>, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, st, a, ws, dloss, dstudent,
+                     dteacher);
+  if (hipGetLastError() != hipSuccess) { sca_set_error(failed); return SCA_ERR_LAUNCH; }
+  return SCA_OK;
+}
+
+template <bool VALID>
+int lstm_cell_fwd(const float* gates, float* act, float* c, float* y, float* hp, int B, int T, int H, int ndir,
+                  int step, const int* valid, int shift, void* stream, const char* bad, const char* failed) {
+  if (B < 1 || T < 1 || H < 1 || ndir < 1 || ndir > 2 || step < 0 || step >= T || !gates || !act || !c || !y ||
+      !hp || (VALID && !valid_args_ok(T, valid, shift))) {
+    sca_set_error(bad);
+    return SCA_ERR_ARG;
+  }
+  LstmArgs a{gates, act, c, y, hp, nullptr, nullptr, nullptr, nullptr, B, T, H, ndir, step, valid, shift};
+  hipLaunchKernelGGL(lstm_cell_fwd_kernel<VALID>, dim3((B * H + 255) / 256, ndir), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), a);
+  if (hipGetLastError() != hipSuccess) { sca_set_error(failed); return SCA_ERR_LAUNCH; }
+  return SCA_OK;
+}
+
+template <bool VALID>
+int lstm_cell_bwd(const float* dh, const float* dy, const float* act, const float* c, float* dc, float* dg, int B,
+                  int T, int H, int ndir, int step, const int* valid, int shift, void* stream, const char* bad,
+                  const char* failed) {
+  if (B < 1 || T < 1 || H < 1 || ndir < 1 || ndir > 2 || step < 0 || step >= T || !dy || !act || !c || !dc ||
+      !dg || (step > 0 && !dh) || (VALID && !valid_args_ok(T, valid, shift))) {
+    sca_set_error(bad);
+    return SCA_ERR_ARG;
+  }
+  LstmArgs a{nullptr, const_cast<float*>(act), const_cast<float*>(c), nullptr, nullptr, dh, dy, dc, dg,
+             B, T, H, ndir, step, valid, shift};
+  hipLaunchKernelGGL(lstm_cell_bwd_kernel<VALID>, dim3((B * H + 255) / 256, ndir), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), a);
+  if (hipGetLastError() != hipSuccess) { sca_set_error(failed); return SCA_ERR_LAUNCH; }
+  return SCA_OK;
+}
+
+}  // namespace
+
+extern "C" int sca_seqkd_fwd(const float* student, const float* teacher, int R, int C, int start, float temp,
+                             float weight, float lo, float hi, float* loss, float* ws, void* stream) {
+  return seqkd_fwd<false>(student, teacher, R, C, start, temp, weight, lo, hi, loss, ws, 1, nullptr, 0, stream,
+                          "sca_seqkd_fwd: bad arguments", "sca_seqkd_fwd: launch failed");
+}
+
+extern "C" int sca_seqkd_valid_fwd(const float* student, const float* teacher, int R, int C, int start, float temp,
+                                   float weight, float lo, float hi, float* loss, float* ws, int T,
+                                   const int* valid_frames, int shift, void* stream) {
+  return seqkd_fwd<true>(student, teacher, R, C, start, temp, weight, lo, hi, loss, ws, T, valid_frames, shift,
+                         stream, "sca_seqkd_valid_fwd: bad arguments", "sca_seqkd_valid_fwd: launch failed");
 }
 
 extern "C" int sca_seqkd_bwd(const float* student, const float* teacher, int R, int C, int start, float temp,
                              const float* dloss, const float* ws, float* dstudent, float* dteacher, void* stream) {
-  if (R < 1 || C < 1 || start < 0 || start >= C || !(temp > 0.0f) || !student || !teacher || !dloss || !ws ||
-      (!dstudent && !dteacher)) {
-    sca_set_error("sca_seqkd_bwd: bad arguments");
-    return SCA_ERR_ARG;
-  }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const KdArgs a{student, teacher, R, C, start, 1.0f / temp, 0.0f, 0.0f, 0.0f};
-  hipLaunchKernelGGL(kd_grad_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, st, a, ws, dloss, dstudent,
-                     dteacher);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_seqkd_bwd: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return seqkd_bwd<false>(student, teacher, R, C, start, temp, dloss, ws, dstudent, dteacher, 1, nullptr, 0, stream,
+                          "sca_seqkd_bwd: bad arguments", "sca_seqkd_bwd: launch failed");
+}
+
+extern "C" int sca_seqkd_valid_bwd(const float* student, const float* teacher, int R, int C, int start, float temp,
+                                   const float* dloss, const float* ws, float* dstudent, float* dteacher, int T,
+                                   const int* valid_frames, int shift, void* stream) {
+  return seqkd_bwd<true>(student, teacher, R, C, start, temp, dloss, ws, dstudent, dteacher, T, valid_frames, shift,
+                         stream, "sca_seqkd_valid_bwd: bad arguments", "sca_seqkd_valid_bwd: launch failed");
 }
 
 extern "C" int sca_clamp(const float* x, float* y, const float* dy, float* dx, long n, float lo, float hi,
@@ -516,29 +639,25 @@ extern "C" int sca_clamp(const float* x, float* y, const float* dy, float* dx, l
 
 extern "C" int sca_lstm_cell_fwd(const float* gates, float* act, float* c, float* y, float* hp, int B, int T, int H,
                                  int ndir, int step, void* stream) {
-  if (B < 1 || T < 1 || H < 1 || ndir < 1 || ndir > 2 || step < 0 || step >= T || !gates || !act || !c || !y ||
-      !hp) {
-    sca_set_error("sca_lstm_cell_fwd: bad arguments");
-    return SCA_ERR_ARG;
-  }
-  LstmArgs a{gates, act, c, y, hp, nullptr, nullptr, nullptr, nullptr, B, T, H, ndir, step};
-  hipLaunchKernelGGL(lstm_cell_fwd_kernel, dim3((B * H + 255) / 256, ndir), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), a);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_lstm_cell_fwd: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return lstm_cell_fwd<false>(gates, act, c, y, hp, B, T, H, ndir, step, nullptr, 0, stream,
+                              "sca_lstm_cell_fwd: bad arguments", "sca_lstm_cell_fwd: launch failed");
+}
+
+extern "C" int sca_lstm_cell_valid_fwd(const float* gates, float* act, float* c, float* y, float* hp, int B, int T,
+                                       int H, int ndir, int step, const int* valid_frames, int shift, void* stream) {
+  return lstm_cell_fwd<true>(gates, act, c, y, hp, B, T, H, ndir, step, valid_frames, shift, stream,
+                             "sca_lstm_cell_valid_fwd: bad arguments", "sca_lstm_cell_valid_fwd: launch failed");
 }
 
 extern "C" int sca_lstm_cell_bwd(const float* dh, const float* dy, const float* act, const float* c, float* dc,
                                  float* dg, int B, int T, int H, int ndir, int step, void* stream) {
-  if (B < 1 || T < 1 || H < 1 || ndir < 1 || ndir > 2 || step < 0 || step >= T || !dy || !act || !c || !dc ||
-      !dg || (step > 0 && !dh)) {
-    sca_set_error("sca_lstm_cell_bwd: bad arguments");
-    return SCA_ERR_ARG;
-  }
-  LstmArgs a{nullptr, const_cast<float*>(act), const_cast<float*>(c), nullptr, nullptr, dh, dy, dc, dg,
-             B, T, H, ndir, step};
-  hipLaunchKernelGGL(lstm_cell_bwd_kernel, dim3((B * H + 255) / 256, ndir), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), a);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_lstm_cell_bwd: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return lstm_cell_bwd<false>(dh, dy, act, c, dc, dg, B, T, H, ndir, step, nullptr, 0, stream,
+                              "sca_lstm_cell_bwd: bad arguments", "sca_lstm_cell_bwd: launch failed");
+}
+
+extern "C" int sca_lstm_cell_valid_bwd(const float* dh, const float* dy, const float* act, const float* c, float* dc,
+                                       float* dg, int B, int T, int H, int ndir, int step, const int* valid_frames,
+                                       int shift, void* stream) {
+  return lstm_cell_bwd<true>(dh, dy, act, c, dc, dg, B, T, H, ndir, step, valid_frames, shift, stream,
+                             "sca_lstm_cell_valid_bwd: bad arguments", "sca_lstm_cell_valid_bwd: launch failed");
 }

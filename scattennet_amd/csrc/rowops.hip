@@ -290,9 +290,20 @@ int launch_reduce(const ReduceArgs& a, int nprob, hipStream_t st) {
 struct SoftmaxArgs {
   sca_softmax_problem p[SCA_SOFTMAX_MAX_PROBLEMS];
   int rows, N;
+  const int* valid;  // VALID kernels only: device scalar, columns [0, clamp(*valid >> shift, 1, N)) take part
+  int shift;
 };
 
-template <int NV>
+// the valid column count of the *_valid entry points, read on the device (a graph replay sees
+// what the host last copied there) and clamped so a bad value stays in bounds
+__device__ __forceinline__ int valid_cols(const int* valid, int shift, int N) {
+  const int nv = *valid >> shift;
+  return nv < 1 ? 1 : (nv > N ? N : nv);
+}
+
+// VALID: softmax over columns [0, nv) only, exact 0 in [nv, N).  With nv == N every predicate
+// is true and the arithmetic (and its order) is that of the plain kernel: bitwise equal.
+template <int NV, bool VALID>
 __global__ __launch_bounds__(256) void softmax_fwd_kernel(const SoftmaxArgs a) {
   using RM = RowMap<NV>;
   constexpr int V = RM::kVals;
@@ -301,17 +312,18 @@ __global__ __launch_bounds__(256) void softmax_fwd_kernel(const SoftmaxArgs a) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= a.rows) return;
   const int N = a.N;
+  const int nv = VALID ? valid_cols(a.valid, a.shift, N) : N;
   float v[V];
   load_row<NV>(v, P.x + (long)row * N, lane, N);
   float m = -INFINITY;
 #pragma unroll
   for (int i = 0; i < V; ++i)
-    if (NV > 0 || RM::col(lane, i) < N) m = fmaxf(m, v[i]);
+    if ((NV > 0 && !VALID) || RM::col(lane, i) < nv) m = fmaxf(m, v[i]);
   m = wave_max(m);
   float s = 0.f;
 #pragma unroll
   for (int i = 0; i < V; ++i) {
-    const bool in = NV > 0 || RM::col(lane, i) < N;
+    const bool in = (NV > 0 && !VALID) || RM::col(lane, i) < nv;
     v[i] = in ? __expf(v[i] - m) : 0.f;
     s += v[i];
   }
@@ -437,21 +449,26 @@ __global__ __launch_bounds__(256) void ln_bwd_wide_kernel(const LnBwdArgs a) {
 }
 
 // Wide-row softmax (N > 1024): one wave per row, max / sum / output passes over the row.
+// VALID: the passes stop at column nv, the columns behind it are written as 0.
+template <bool VALID>
 __global__ __launch_bounds__(256) void softmax_fwd_wide_kernel(const SoftmaxArgs a) {
   const sca_softmax_problem& P = a.p[blockIdx.y];
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= a.rows) return;
   const int N = a.N;
+  const int nv = VALID ? valid_cols(a.valid, a.shift, N) : N;
   const float* x = P.x + (long)row * N;
   float m = -INFINITY;
-  for (int c = lane; c < N; c += 64) m = fmaxf(m, x[c]);
+  for (int c = lane; c < nv; c += 64) m = fmaxf(m, x[c]);
   m = wave_max(m);
   float s = 0.f;
-  for (int c = lane; c < N; c += 64) s += __expf(x[c] - m);
+  for (int c = lane; c < nv; c += 64) s += __expf(x[c] - m);
   const float inv = 1.0f / wave_sum(s);
   float* o = P.out + (long)row * N;
-  for (int c = lane; c < N; c += 64) o[c] = __expf(x[c] - m) * inv;
+  for (int c = lane; c < nv; c += 64) o[c] = __expf(x[c] - m) * inv;
+  if (VALID)
+    for (int c = nv + lane; c < N; c += 64) o[c] = 0.f;
 }
 
 __global__ __launch_bounds__(256) void softmax_bwd_wide_kernel(const SoftmaxArgs a) {
@@ -952,9 +969,11 @@ extern "C" int sca_maxpool_t_bwd(int nprob, const sca_pool_problem* probs, int B
   return SCA_OK;
 }
 
-template <bool BWD>
-int launch_softmax(int nprob, const sca_softmax_problem* probs, int rows, int N, void* stream, const char* what) {
-  if (nprob < 1 || nprob > SCA_SOFTMAX_MAX_PROBLEMS || rows < 0 || N < 1) {
+template <bool BWD, bool VALID = false>
+int launch_softmax(int nprob, const sca_softmax_problem* probs, int rows, int N, void* stream, const char* what,
+                   const int* valid = nullptr, int shift = 0) {
+  if (nprob < 1 || nprob > SCA_SOFTMAX_MAX_PROBLEMS || rows < 0 || N < 1 ||
+      (VALID && (!valid || shift < 0 || shift > 30))) {
     sca_set_error(what);
     return SCA_ERR_ARG;
   }
@@ -963,15 +982,17 @@ int launch_softmax(int nprob, const sca_softmax_problem* probs, int rows, int N,
   for (int i = 0; i < nprob; ++i) a.p[i] = probs[i];
   a.rows = rows;
   a.N = N;
+  a.valid = valid;
+  a.shift = shift;
   dim3 grid((rows + 3) / 4, nprob);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int nv = N % 256 == 0 ? N / 256 : 0;
 #define SCA_SM(NVV)                                                                   \
   if (BWD) hipLaunchKernelGGL(softmax_bwd_kernel<NVV>, grid, dim3(256), 0, st, a);   \
-  else hipLaunchKernelGGL(softmax_fwd_kernel<NVV>, grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((softmax_fwd_kernel<NVV, VALID>), grid, dim3(256), 0, st, a);
   if (N > 64 * LN_MAXV) {
     if (BWD) hipLaunchKernelGGL(softmax_bwd_wide_kernel, grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(softmax_fwd_wide_kernel, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(softmax_fwd_wide_kernel<VALID>, grid, dim3(256), 0, st, a);
   } else switch (nv) {
     case 1: SCA_SM(1) break;
     case 2: SCA_SM(2) break;
@@ -990,6 +1011,12 @@ extern "C" int sca_softmax_rows_fwd(int nprob, const sca_softmax_problem* probs,
 
 extern "C" int sca_softmax_rows_bwd(int nprob, const sca_softmax_problem* probs, int rows, int N, void* stream) {
   return launch_softmax<true>(nprob, probs, rows, N, stream, "sca_softmax_rows_bwd: bad arguments");
+}
+
+extern "C" int sca_softmax_rows_valid_fwd(int nprob, const sca_softmax_problem* probs, int rows, int N,
+                                          const int* valid_frames, int shift, void* stream) {
+  return launch_softmax<false, true>(nprob, probs, rows, N, stream, "sca_softmax_rows_valid_fwd: bad arguments",
+                                     valid_frames, shift);
 }
 
 extern "C" int sca_gelu_bwd(int nprob, const sca_gelu_bwd_problem* probs, long n, void* stream) {

@@ -9,6 +9,12 @@ from .keypoint_module import KeypointModule, joint_index_tensors, keypoint_strea
 from .precision import fp32_compute
 
 
+def n_pool_of(cfg):
+    """MaxPool1d(2, 2) stages of the residual network: its downsampling blocks are the even
+    indices of cfg["residual_blocks"] (residual.py)."""
+    return (len(cfg["residual_blocks"]) + 1) // 2
+
+
 class SCAEncoder(nn.Module):
     def __init__(self, cfg):
         super().__init__()
@@ -23,8 +29,13 @@ class SCAEncoder(nn.Module):
     def forward(self, keypoints, mask):
         return self.encode(keypoints, mask)
 
-    def encode(self, keypoints, mask):
+    def n_pool(self):
+        return n_pool_of(self.cfg)
+
+    def encode(self, keypoints, mask, valid=None):
         """keypoints (B, T, K_all, 2), mask (B, T) -> (fuse, left, right, body) embeddings.
+        `valid=(valid_frames, n_pool)`: the batch is padded to a length bucket; the fusion
+        softmax leaves the added frames out (CoordinatesFusion).
         The three streams run in lock-step (one launch per stage), their joint slicing
         (model/__init__.py:133-142) fused into the mapping kernel's gather.  (MSCA_Net, a
         subclass with a forward of its own, calls this directly.)"""
@@ -33,5 +44,5 @@ class SCAEncoder(nn.Module):
         if idx is None or idx[0].device != keypoints.device:
             idx = self._idx = joint_index_tensors(mods, keypoints.device)
         body, left, right = keypoint_streams_forward(mods, idx, keypoints, mask, with_residual=True)
-        fuse = self.coordinates_fusion(left, right, body)
+        fuse = self.coordinates_fusion(left, right, body, valid=valid)
         return fuse, left, right, body

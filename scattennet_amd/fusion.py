@@ -20,7 +20,11 @@ class CoordinatesFusion(nn.Module):
 
     l, r, b = GELU(Linear_in->out(.)) (one grouped launch); A = softmax(r l^T) per clip —
     no 1/sqrt(d) scale and no mask, so padded frames take part, as in the reference;
-    f = LayerNorm(out_proj(A b)); out = InvertedResidual(f)."""
+    f = LayerNorm(out_proj(A b)); out = InvertedResidual(f).
+
+    `valid=(valid_frames, shift)` (a batch padded to a length bucket, see
+    scattennet_amd/bucketed.py): the softmax runs over the first valid_frames >> shift key
+    frames only, so the frames added by the bucket get no weight."""
 
     def __init__(self, in_feat, out_feat, drop_rate=0.0):
         super().__init__()
@@ -34,11 +38,11 @@ class CoordinatesFusion(nn.Module):
         self.drop_rate = drop_rate
 
     @fp32_compute()
-    def forward(self, left_embed, right_embed, body_embed):
+    def forward(self, left_embed, right_embed, body_embed, valid=None):
         p = drop_p([self], "drop_rate")
         lo, ro, bo = _lin([self.left_se, self.right_se, self.body_se], [left_embed, right_embed, body_embed],
                           gelu=True)
-        attn = library.softmax_rows_apply(library.clip_matmul_apply(True, ro, lo))
+        attn = library.softmax_rows_apply(library.clip_matmul_apply(True, ro, lo), valid)
         if p > 0:  # fusion.py:48
             attn = ops.dropout_grouped([attn], p)[0]
         fuse = library.clip_matmul_apply(False, attn, bo)

@@ -163,8 +163,11 @@ def compute_loss(labels, tgt_lengths, logits, input_lengths, return_per_sample=F
 
 
 class SeqKDOp(Function):
+    """`valid_frames`, `shift` (a batch padded to a length bucket): the logits are (B, T, C) and
+    only the frames t < valid_frames >> shift take part (`sca_seqkd_valid_fwd/bwd`)."""
+
     @staticmethod
-    def forward(ctx, student, teacher, start, temp, weight, lo, hi):
+    def forward(ctx, student, teacher, start, temp, weight, lo, hi, valid_frames=None, shift=0):
         s, q = student.contiguous(), teacher.contiguous()
         L.require_device(s, q)
         if s.shape != q.shape:
@@ -174,8 +177,19 @@ class SeqKDOp(Function):
         lib = L.lib()
         ws = s.new_empty(lib.sca_seqkd_workspace_floats(R))
         loss = s.new_empty(())
-        L.check(lib.sca_seqkd_fwd(L.ptr(s), L.ptr(q), R, C, start, temp, weight, lo, hi, L.ptr(loss), L.ptr(ws),
-                                  L.stream_handle()), "sca_seqkd_fwd")
+        if valid_frames is None:
+            L.check(lib.sca_seqkd_fwd(L.ptr(s), L.ptr(q), R, C, start, temp, weight, lo, hi, L.ptr(loss), L.ptr(ws),
+                                      L.stream_handle()), "sca_seqkd_fwd")
+            ctx.valid = None
+        else:
+            if s.dim() < 2:
+                raise ValueError("SeqKD: valid_frames needs logits of shape (..., T, C)")
+            valid_frames, shift = ops.check_valid((valid_frames, shift))
+            T = s.shape[-2]
+            L.check(lib.sca_seqkd_valid_fwd(L.ptr(s), L.ptr(q), R, C, start, temp, weight, lo, hi, L.ptr(loss),
+                                            L.ptr(ws), T, L.ptr(valid_frames), shift, L.stream_handle()),
+                    "sca_seqkd_valid_fwd")
+            ctx.valid = (T, valid_frames, shift)  # not a saved tensor: an input the host rewrites between replays
         ctx.save_for_backward(s, q, ws)
         ctx.args = (R, C, start, temp)
         return loss
@@ -187,10 +201,15 @@ class SeqKDOp(Function):
         need_s, need_q = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         ds = torch.empty_like(s) if need_s else None
         dq = torch.empty_like(q) if need_q else None
-        if need_s or need_q:
+        if (need_s or need_q) and ctx.valid is None:
             L.check(L.lib().sca_seqkd_bwd(L.ptr(s), L.ptr(q), R, C, start, temp, L.ptr(dloss.contiguous()), L.ptr(ws),
                                           L.ptr(ds), L.ptr(dq), L.stream_handle()), "sca_seqkd_bwd")
-        return ds, dq, None, None, None, None, None
+        elif need_s or need_q:
+            T, valid_frames, shift = ctx.valid
+            L.check(L.lib().sca_seqkd_valid_bwd(L.ptr(s), L.ptr(q), R, C, start, temp, L.ptr(dloss.contiguous()),
+                                                L.ptr(ws), L.ptr(ds), L.ptr(dq), T, L.ptr(valid_frames), shift,
+                                                L.stream_handle()), "sca_seqkd_valid_bwd")
+        return ds, dq, None, None, None, None, None, None, None
 
 
 class SeqKD(nn.Module):
@@ -201,14 +220,17 @@ class SeqKD(nn.Module):
         self.T = T
 
     @fp32_compute()
-    def forward(self, prediction_logits, ref_logits, use_blank=True):
+    def forward(self, prediction_logits, ref_logits, use_blank=True, valid=None):
         return SeqKDOp.apply(prediction_logits, ref_logits, 0 if use_blank else 1, float(self.T), 1.0,
-                             float("-inf"), float("inf"))
+                             float("-inf"), float("inf"), *(valid or ()))
 
 
-def distillation_loss(student_logits, teacher_logits, weight, T=1.0):
-    """model/__init__.py:203-214: clamp(weight * SeqKD(T)(student, teacher.detach(), use_blank=False), -100, 100)."""
-    return SeqKDOp.apply(student_logits, teacher_logits.detach(), 1, float(T), float(weight), -100.0, 100.0)
+def distillation_loss(student_logits, teacher_logits, weight, T=1.0, valid=None):
+    """model/__init__.py:203-214: clamp(weight * SeqKD(T)(student, teacher.detach(), use_blank=False), -100, 100).
+    `valid=(valid_frames, shift)`: logits (B, T, C) of a batch padded to a length bucket; only
+    the frames t < valid_frames >> shift take part and the mean is over those rows."""
+    return SeqKDOp.apply(student_logits, teacher_logits.detach(), 1, float(T), float(weight), -100.0, 100.0,
+                         *(valid or ()))
 
 
 class RecognitionHead(nn.Module):
@@ -230,7 +252,7 @@ class RecognitionHead(nn.Module):
                 nn.init.constant_(m.bias, 0)
 
     @fp32_compute()
-    def forward(self, left_output, right_output, fuse_output, body_output):
+    def forward(self, left_output, right_output, fuse_output, body_output, valid=None):
         heads = [self.left_gloss_classifier, self.right_gloss_classifier, self.body_gloss_classifier]
         zs = list(ops.LinearResidual.apply(3, False, left_output, right_output, body_output,
                                            *[h.weight for h in heads], *[h.bias for h in heads]))
@@ -239,5 +261,5 @@ class RecognitionHead(nn.Module):
         left, right, body, fuse = [clamp_logits(z) for z in zs]
         out = {"left": left, "right": right, "body": body, "fuse_coord_gloss_logits": fuse}
         if self.fuse_alignment_head is not None:
-            out["alignment_gloss_logits"] = clamp_logits(self.fuse_alignment_head(fuse_output.permute(1, 0, 2)))
+            out["alignment_gloss_logits"] = clamp_logits(self.fuse_alignment_head(fuse_output.permute(1, 0, 2), valid=valid))
         return out

@@ -669,6 +669,48 @@ def _sm_bwd(ctx, dy):
 softmax_rows.register_autograd(_sm_bwd, setup_context=_sm_setup)
 
 
+@torch.library.custom_op(f"{_LIB}::softmax_rows_valid", mutates_args=())
+def softmax_rows_valid(x: Tensor, valid_frames: Tensor, shift: int) -> Tensor:
+    """softmax over the first clamp(valid_frames >> shift, 1, N) columns of the last dimension,
+    zeros behind them; `valid_frames` is an int32 device tensor of one element, read on the
+    device (a batch padded to a length bucket: the padded frames must not take part)."""
+    L.require_device(x)
+    with ops.library_mode():
+        return ops.SoftmaxRowsValid.forward(_Ctx(), x, valid_frames, shift)
+
+
+@softmax_rows_valid.register_fake
+def _(x, valid_frames, shift):
+    return torch.empty_like(x)
+
+
+@torch.library.custom_op(f"{_LIB}::softmax_rows_valid_backward", mutates_args=())
+def softmax_rows_valid_backward(dy: Tensor, y: Tensor) -> Tensor:
+    """dx = y * (dy - sum_j dy_j y_j): the row-softmax backward, exact for a y with zero
+    columns (they get dx = 0 and add nothing to the row sum)."""
+    ctx = _Ctx()
+    ctx.saved_tensors = (y,)
+    with ops.library_mode():
+        return ops.SoftmaxRows.backward(ctx, dy)
+
+
+@softmax_rows_valid_backward.register_fake
+def _(dy, y):
+    return torch.empty_like(y)
+
+
+def _smv_setup(ctx, inputs, output):
+    ctx.save_for_backward(output)
+
+
+def _smv_bwd(ctx, dy):
+    (y,) = ctx.saved_tensors
+    return softmax_rows_valid_backward(dy, y), None, None
+
+
+softmax_rows_valid.register_autograd(_smv_bwd, setup_context=_smv_setup)
+
+
 # --------------------------------------------------------------------------- grouped front-ends
 # Same signatures as the `ops` Functions' .apply: eager -> the grouped launch; while
 # torch.compile traces -> the operators above, one stream at a time (dropout active: the
@@ -757,7 +799,12 @@ def clip_matmul_apply(trans_b, a, b):
     return clip_matmul(a, b, bool(trans_b))
 
 
-def softmax_rows_apply(x):
+def softmax_rows_apply(x, valid=None):
+    if valid is not None:
+        if compiling():
+            raise NotImplementedError("scattennet_amd: valid_frames (length-bucketed batches) is not supported "
+                                      "while torch.compile traces; run the bucketed step eagerly or captured")
+        return ops.SoftmaxRowsValid.apply(x, *ops.check_valid(valid))
     if not compiling():
         return ops.SoftmaxRows.apply(x)
     return softmax_rows(x)

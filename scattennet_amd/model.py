@@ -18,6 +18,13 @@ tests on the device.  `model.check` selects what the host does with it:
 * ``"defer"``: no host read; `model.raise_if_nonfinite(outputs)` reads and raises later.
 * ``"off"``: no scan; the report holds zero flag words.
 
+Length buckets.  `src_input` may carry `"valid_frames"`: an int32 device tensor of shape (1,)
+holding the batch's own longest length when keypoints and mask are padded beyond it to a fixed
+bucket (`pad_batch`, `BucketedTrainStep`).  The three ops through which frames behind that
+length would reach the valid ones — the fusion softmax, the SeqKD terms and the BiLSTM's
+reverse direction — then read it on the device, so the valid frames' outputs, the losses and
+every parameter gradient are those of the unpadded batch.
+
 The model computes in fp32 (`.half()` of the whole model is not supported; the submodules keep
 their own reduced-precision paths).
 
@@ -32,7 +39,7 @@ from torch import nn
 from torch.autograd import Function
 
 from . import _lib as L
-from . import heads
+from . import heads, ops
 from .encoder import SCAEncoder
 
 FLAG_NAN, FLAG_INF = 1, 2
@@ -187,9 +194,15 @@ class MSCA_Net(SCAEncoder):
             src_input = {k: v.cuda() if isinstance(v, torch.Tensor) else v for k, v in src_input.items()}
         keypoints = src_input["keypoints"]
         mask = src_input["mask"]
+        valid = None
+        if src_input.get("valid_frames") is not None:
+            if torch.compiler.is_compiling():
+                raise NotImplementedError("MSCA_Net: valid_frames (length-bucketed batches) is not supported while "
+                                          "torch.compile traces; run the bucketed step eagerly or captured")
+            valid = ops.check_valid((src_input["valid_frames"], self.n_pool()))
 
-        fuse_embed, left_embed, right_embed, body_embed = self.encode(keypoints, mask)
-        head_outputs = self.recognition_head(left_embed, right_embed, fuse_embed, body_embed)
+        fuse_embed, left_embed, right_embed, body_embed = self.encode(keypoints, mask, valid=valid)
+        head_outputs = self.recognition_head(left_embed, right_embed, fuse_embed, body_embed, valid=valid)
         outputs = {k: head_outputs[k] for k in _LOGITS if k in head_outputs}
         outputs["input_lengths"] = src_input["valid_len_in"]
 
@@ -202,7 +215,7 @@ class MSCA_Net(SCAEncoder):
         students = self._students()
         for student in students:
             outputs[f"{student}_distill_loss"] = heads.distillation_loss(
-                outputs[student], fuse_logits, self.cfg["distillation_weight"][student])
+                outputs[student], fuse_logits, self.cfg["distillation_weight"][student], valid=valid)
 
         names = self.flag_names()
         flags = None

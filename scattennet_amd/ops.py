@@ -2206,3 +2206,40 @@ class SoftmaxRows(Function):
         arr = (L.SoftmaxProblem * 1)(L.SoftmaxProblem(None, y.data_ptr(), dy.data_ptr(), dx.data_ptr()))
         L.check(L.lib().sca_softmax_rows_bwd(1, arr, y.numel() // N, N, L.stream_handle()), "sca_softmax_rows_bwd")
         return dx
+
+
+def check_valid(valid):
+    """`valid=(tensor, shift)` of the bucketed path: an int32 device tensor holding one
+    element (the batch's unpooled longest length) and the number of pooling stages in front
+    of the op.  Returns (tensor, shift)."""
+    t, shift = valid
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.int32 or t.numel() != 1:
+        raise ValueError("valid_frames must be an int32 device tensor with one element, got "
+                         f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))} on "
+                         f"{getattr(t, 'device', 'the host')}")
+    if not 0 <= int(shift) <= 30:
+        raise ValueError(f"valid_frames shift must lie in [0, 30], got {shift}")
+    return t, int(shift)
+
+
+class SoftmaxRowsValid(Function):
+    """softmax over the first nv = clamp(valid_frames >> shift, 1, N) columns of the last dim,
+    exact zeros behind them (`sca_softmax_rows_valid_fwd`); nv is read on the device.  The
+    backward is the plain row-softmax backward: y = 0 gives dx = 0."""
+
+    @staticmethod
+    def forward(ctx, x, valid_frames, shift):
+        x = x.contiguous()
+        L.require_device(x)
+        valid_frames, shift = check_valid((valid_frames, shift))
+        N = x.shape[-1]
+        y = torch.empty_like(x)
+        arr = (L.SoftmaxProblem * 1)(L.SoftmaxProblem(x.data_ptr(), None, None, y.data_ptr()))
+        L.check(L.lib().sca_softmax_rows_valid_fwd(1, arr, x.numel() // N, N, L.ptr(valid_frames), shift,
+                                                   L.stream_handle()), "sca_softmax_rows_valid_fwd")
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        return SoftmaxRows.backward(ctx, dy), None, None

@@ -19,7 +19,8 @@ The kernels are driven by tables in device memory:
 
 Table upkeep.  An eager `step()` compares every `p.grad.data_ptr()` with the table it last
 uploaded and rebuilds only on change.  Under stream capture the step always uploads a table
-of its own, taken from a small pool allocated beforehand (`SPARE_TABLES`), with an
+of its own, taken from a small pool allocated beforehand (`capture_slots`, by default
+`SPARE_TABLES`; one per captured step, e.g. one per length bucket), with an
 asynchronous copy from a pinned host buffer that is never written again and lives as long
 as the optimizer: replaying the copy node is harmless, and no eager step ever touches a
 table a graph reads.  The group table is not part of that upload: `sync_hyperparameters()`
@@ -44,7 +45,7 @@ from torch.optim.lr_scheduler import _LRScheduler
 from . import _lib
 
 CHUNK = 8192        # elements per chunk (tools/optim_bench.py --chunk measures others)
-SPARE_TABLES = 2    # tables a stream capture can take (one per captured step())
+SPARE_TABLES = 2    # tables a stream capture can take (one per captured step()): the default capture_slots
 _ALIGN = 64         # floats: every moment slot starts on a 256-byte boundary
 
 _TENSOR_DT = np.dtype([("p", "<u8"), ("g", "<u8"), ("exp_avg", "<u8"), ("exp_avg_sq", "<u8"),
@@ -160,10 +161,12 @@ _UNSUPPORTED = ("maximize", "foreach", "capturable", "differentiable", "fused", 
 class FusedAdam(Optimizer):
     """torch.optim.Adam (L2 weight decay, optional amsgrad) with clip_grad_norm_ folded in
     (`max_grad_norm`, None: no clipping) and the non-finite-loss skip of opt.py:32-37 on the
-    device (`step(loss=...)`).  See the module docstring for the capture protocol."""
+    device (`step(loss=...)`).  See the module docstring for the capture protocol;
+    `capture_slots` is the number of captured `step()` calls the optimizer can take part in
+    (one per graph, e.g. one per length bucket of `BucketedTrainStep`)."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False,
-                 max_grad_norm=None, *, max_blocks=0, chunk=CHUNK):
+                 max_grad_norm=None, *, max_blocks=0, chunk=CHUNK, capture_slots=SPARE_TABLES):
         if isinstance(lr, torch.Tensor):
             raise ValueError("FusedAdam: lr must be a float (a tensor lr is torch's capturable path)")
         if not 0.0 <= lr:
@@ -180,6 +183,9 @@ class FusedAdam(Optimizer):
             raise ValueError(f"Invalid max_grad_norm: {max_grad_norm}")
         if max_blocks < 0 or chunk < 1:
             raise ValueError("FusedAdam: max_blocks must be >= 0 and chunk >= 1")
+        if int(capture_slots) != capture_slots or capture_slots < 0:
+            raise ValueError(f"FusedAdam: capture_slots must be a non-negative integer, got {capture_slots!r}")
+        self.capture_slots = int(capture_slots)  # captured step() calls this optimizer can take part in
         self.max_grad_norm = max_grad_norm
         self.max_blocks = int(max_blocks)
         self.chunk = int(chunk)
@@ -257,7 +263,7 @@ class FusedAdam(Optimizer):
         self._hyper = None
         self._eager = _Tables(capacity[0], capacity[1], dev, pinned=False)
         self._key = None
-        self._spare = [_Tables(capacity[0], capacity[1], dev) for _ in range(SPARE_TABLES)]
+        self._spare = [_Tables(capacity[0], capacity[1], dev) for _ in range(self.capture_slots)]
         self._capacity = capacity
 
     def _moment(self, p, name):
@@ -300,6 +306,11 @@ class FusedAdam(Optimizer):
         return [(float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
                  float(g["weight_decay"])) for g in self.param_groups]
 
+    def hyperparameters_changed(self):
+        """True when lr, betas, eps or weight decay of a param_group differ from the device
+        group table (a scheduler stepped): a replay needs `sync_hyperparameters()` first."""
+        return self._hyper != self._hyper_values()
+
     def sync_hyperparameters(self):
         """Copy lr, betas, eps and weight decay of every param_group to the device group table
         (on the current stream).  Call it outside a captured graph, between replays, after a
@@ -337,8 +348,9 @@ class FusedAdam(Optimizer):
                 raise RuntimeError("FusedAdam: hyper-parameters changed since the last eager step; call "
                                    "sync_hyperparameters() before capturing")
             if not self._spare:
-                raise RuntimeError(f"FusedAdam: no spare table left for this capture ({SPARE_TABLES} captured "
-                                   "steps per optimizer: scattennet_amd.optim.SPARE_TABLES)")
+                raise RuntimeError(f"FusedAdam: no spare table left for this capture ({self.capture_slots} captured "
+                                   "steps per optimizer: scattennet_amd.optim.SPARE_TABLES); construct it with "
+                                   "a larger capture_slots")
             tab = self._spare.pop()
             self._frozen.append(tab)  # its pinned image is never written again
             tab.upload(*self._build(entries))

@@ -18,6 +18,9 @@ Capture.  For a fixed (B, T, S) the step is capturable into one hipGraph:
    the same tensors;
 4. between replays, call `optimizer.sync_hyperparameters()` after a scheduler step, and
    `read_report` whenever the host wants the numbers.
+
+Batches whose T varies: `scattennet_amd.BucketedTrainStep` (bucketed.py) follows these rules
+once per length bucket and replays the bucket's graph on padded batches.
 """
 import math
 

@@ -15,6 +15,19 @@ tensors of the step's shapes (they stay cache-resident between calls: the figure
 kernel's rate on 25.6 MB it re-reads, not an HBM stream).  Prints one JSON line.
 
 Usage: python tools/model_bench.py [--B 8] [--T 256] [--C 1124] [--steps 10] [--windows 7]
+
+--mixed: a stream of batches whose length varies, as a training collator produces it.  A fixed
+seeded sequence of `--batches` (20) batches of B clips; every clip's length is drawn with
+select_frames' training rule (a target in [0.5 n, 1.5 n] capped at max_len = T) from a source
+length n ~ U[40, 240], the batch is padded to its longest clip.  Two ways to train on it:
+  eager      train_step per batch at the batch's own T        (what a varying T costs today)
+  bucketed   BucketedTrainStep, buckets --buckets (64,128,192,256), every graph captured before
+Both are timed over whole passes of the stream (host clock around the pass, ending in a device
+synchronise; no report read in either) in alternated windows; ms/step as median and range over
+`--windows`.  Then, per bucket, the padding overhead: the bucket's replay with a batch just
+above the previous bucket against a hipGraph captured at exactly that T (alternated windows of
+`--steps` steps).  `--eager-only` times the eager pass alone and `--root DIR` imports the
+package from another checkout (the same eager measurement on an earlier commit).  One JSON line.
 """
 import argparse
 import json
@@ -25,7 +38,17 @@ import time
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+def _root():
+    for i, arg in enumerate(sys.argv):
+        if arg == "--root" and i + 1 < len(sys.argv):
+            return os.path.abspath(sys.argv[i + 1])
+        if arg.startswith("--root="):
+            return os.path.abspath(arg.split("=", 1)[1])
+    return os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+sys.path.insert(0, _root())
 
 
 def build(a, dev):
@@ -97,6 +120,105 @@ def scan_alone(a, w, t4, dev):
     return nbytes, us
 
 
+def mixed_batches(a, w, dev, n_pool):
+    """The seeded stream: [(src_input on the device, T_max)]."""
+    import random
+    import numpy as np
+    from scattennet_amd.data import select_frames
+    random.seed(a.seed)
+    np.random.seed(a.seed)
+    g = torch.Generator().manual_seed(a.seed)
+    out = []
+    for _ in range(a.batches):
+        source = np.random.randint(40, 241, size=a.B)
+        lens = [min(len(select_frames(int(n), True, a.T)), a.T) for n in source]  # the rule can draw max_len + 1
+        out.append(_batch(a, w, dev, g, lens, n_pool))
+    return out
+
+
+def _batch(a, w, dev, g, lens, n_pool):
+    T = max(lens)
+    lens_t = torch.tensor(lens)
+    mask = (torch.arange(T)[None, :] < lens_t[:, None]).to(torch.int64)
+    kp = torch.rand(a.B, T, w["K_all"], 2, generator=g) * mask[:, :, None, None]  # the collator pads with zeros
+    vl = lens_t >> n_pool
+    gl = torch.minimum((vl // 2).clamp(min=1), torch.randint(a.S // 2, a.S + 1, (a.B,), generator=g))
+    src = {"keypoints": kp, "mask": mask, "valid_len_in": vl, "gloss_lengths": gl,
+           "gloss_labels": torch.randint(1, a.C, (a.B, a.S), generator=g)}
+    return {k: v.to(dev) for k, v in src.items()}, T
+
+
+def _spread(v):
+    return {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4),
+            "windows": [round(x, 4) for x in v]}
+
+
+def _pass(fn, batches):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for src, _ in batches:
+        fn(src)
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / len(batches)
+
+
+def mixed(a, dev):
+    import scattennet_amd as S
+    adam = dict(lr=1e-4, betas=(0.9, 0.998), weight_decay=1e-3, max_grad_norm=1.0)
+    model, _, w, _ = build(a, dev)
+    model.check = "defer"
+    n_pool = (len(w["residual_blocks"]) + 1) // 2
+    batches = mixed_batches(a, w, dev, n_pool)
+    lengths = [T for _, T in batches]
+    opt = S.FusedAdam(model.parameters(), **adam)
+    eager = lambda src: S.train_step(model, opt, src)  # noqa: E731
+    _pass(eager, batches)  # every shape once
+    res = {"workload": "MSCA_Net train_step over a mixed-length stream, eval mode, no report read",
+           "B": a.B, "max_len": a.T, "C": a.C, "S": a.S, "seed": a.seed, "batch_lengths": lengths}
+    if a.eager_only:
+        res["eager_ms_per_step"] = _spread([_pass(eager, batches) for _ in range(a.windows)])
+        print(json.dumps(res))
+        return
+    buckets = tuple(int(b) for b in a.buckets.split(","))
+    twin, _, _, _ = build(a, dev)
+    twin.check = "defer"
+    twin_opt = S.FusedAdam(twin.parameters(), capture_slots=len(buckets), **adam)
+    bts = S.BucketedTrainStep(twin, twin_opt, a.B, buckets, a.S)
+    g = torch.Generator().manual_seed(a.seed + 1)
+    for _ in range(2):  # warm-up pass, capture pass
+        _pass(bts.step, batches)
+    for f in buckets:  # a bucket the stream visits less than twice (or never) is captured here
+        while bts._buckets[f].graph is None:
+            bts.step(_batch(a, w, dev, g, [f] * a.B, n_pool)[0])
+    assert bts.graphs_captured == len(buckets)
+    ms = {"eager": [], "bucketed": []}
+    for _ in range(a.windows):  # alternated windows
+        ms["eager"].append(_pass(eager, batches))
+        ms["bucketed"].append(_pass(bts.step, batches))
+    res.update({"buckets": list(buckets),
+                "bucket_of_batch": [bts.bucket_for(T) for T in lengths],
+                "eager_ms_per_step": _spread(ms["eager"]), "bucketed_ms_per_step": _spread(ms["bucketed"]),
+                "bucketed_median_below_eager_range": statistics.median(ms["bucketed"]) < min(ms["eager"])})
+    # padding overhead per bucket: a batch just above the previous bucket, through the bucket's
+    # graph, against a graph captured at exactly that length
+    rows, prev = [], 0
+    for f in buckets:
+        T = prev + 1 if prev else f // 2 + 1
+        src, _ = _batch(a, w, dev, g, [T] * a.B, n_pool)
+        graph, out, _ = capture(model, src, "defer", dev)
+        bts.step(src)
+        t = {"bucket_replay": [], "fixed_shape_graph": []}
+        for _ in range(a.windows):
+            t["fixed_shape_graph"].append(window(graph, a.steps))
+            t["bucket_replay"].append(_pass(bts.step, [(src, T)] * a.steps))
+        rows.append({"bucket": f, "T": T, "bucket_replay_ms": _spread(t["bucket_replay"]),
+                     "fixed_shape_graph_ms": _spread(t["fixed_shape_graph"])})
+        del graph, out
+        prev = f
+    res["padding_overhead"] = rows
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=8)
@@ -106,11 +228,19 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--scan-reps", type=int, default=50)
+    ap.add_argument("--mixed", action="store_true", help="the mixed-length stream: eager against BucketedTrainStep")
+    ap.add_argument("--eager-only", action="store_true", help="with --mixed: time the eager pass alone")
+    ap.add_argument("--batches", type=int, default=20)
+    ap.add_argument("--buckets", default="64,128,192,256")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--root", default=None, help="import scattennet_amd from this checkout")
     a = ap.parse_args()
     import scattennet_amd as S
     if not torch.cuda.is_available():
         raise SystemExit("model_bench needs a GPU: there is no CPU path to time")
     dev = torch.device("cuda:0")
+    if a.mixed:
+        return mixed(a, dev)
     model, src, w, t4 = build(a, dev)
     graphs = {k: capture(model, src, k, dev) for k in ("off", "defer")}
     ms = {k: [] for k in graphs}
