@@ -47,6 +47,11 @@
  *   sca_ctc_beam_decode    on the host) as evaluate_fn calls it (opt.py:84-89)
  *   sca_wer_counts         metrics.wer_single / edit_distance / get_alignment
  *                          (metrics.py:2793-2907)
+ *   sca_ctc_*_decode_heads the decode loop of evaluate_fn over every evaluated head of one
+ *                          forward (opt.py:76-89), one grouped call
+ *   sca_eval_accumulate    wer_single per (head, clip), the totals wer_list needs, the loss
+ *                          meters' sums and the hypothesis log of evaluate_fn (opt.py:77-119),
+ *                          kept in device memory across the steps of a pass
  *   sca_finite_scan        the isnan().any() / isinf().any() tests of MSCA_Net.forward
  *                          (model/__init__.py:130-235), all tensors in one launch
  *   sca_step_report        total_loss (model/__init__.py:207,237), the loss terms the
@@ -618,6 +623,27 @@ int sca_ctc_beam_decode(const float* logits, const int* in_len, int B, int T, in
 int sca_wer_counts(const int* ref, const int* ref_len, const int* hyp, const int* hyp_len, int N, int Rmax,
                    int Hmax, int* counts, void* stream);
 
+/* ---- evaluation step: grouped decoding and device-side totals (opt.py:50-128) -------------
+ * The decoders above over G logit tensors at once, 1 <= G <= SCA_EVAL_MAX_HEADS: the heads of
+ * one forward, all of shape (B, T, C), all decoded with the same in_len (B).  The G device
+ * pointers travel by value in `heads` (as sca_finite_scan's tensors do: no device table,
+ * nothing to upload, capturable).  tokens (G, B, T), out_len (G, B), score (G, B); ws:
+ * sca_ctc_decode_heads_workspace_bytes(G, B, T, C, W) bytes (0 for unsupported sizes), 8-byte
+ * aligned.  The row statistics and the per-frame best labels of all G B T rows are one launch
+ * each, the frame recursion runs on a (B, G) grid, and every (head, clip) has its own arena
+ * slice and cls / clp rows: head g's results are bitwise those of the single-head entry point
+ * called on heads->logits[g].                                                              */
+#define SCA_EVAL_MAX_HEADS 8
+typedef struct {
+  const float* logits[SCA_EVAL_MAX_HEADS]; /* entries [G, 8) are ignored */
+} sca_decode_heads;
+long sca_ctc_decode_heads_workspace_bytes(int G, int B, int T, int C, int W);
+int sca_ctc_greedy_decode_heads(const sca_decode_heads* heads, int G, const int* in_len, int B, int T, int C,
+                                int* tokens, int* out_len, float* score, void* ws, void* stream);
+int sca_ctc_beam_decode_heads(const sca_decode_heads* heads, int G, const int* in_len, int B, int T, int C,
+                              int beam_width, int collapse_repeats, int* tokens, int* out_len, float* score,
+                              void* ws, void* stream);
+
 /* SeqKD over R rows of C logits (student, teacher): columns [start, C) only (use_blank=False
  * -> start 1), temperature temp:
  *   loss = clamp(weight * temp^2 * (1/R) * sum_rows KL(softmax(q/temp) || log_softmax(s/temp)),
@@ -741,7 +767,7 @@ int sca_optim_upload(void* dst, const void* src, long bytes, void* stream);
 /* ---- finite guard: the NaN / Inf checks of MSCA_Net.forward without their host reads ----
  * sca_finite_scan: ntensors (0..16) contiguous fp32 tensors, given as HOST arrays ptrs /
  * numels (copied into the kernel arguments: no device table).  flags: ntensors 32-bit words in
- * device memory; the call clears them on `stream` (a memset node under capture) and one
+ * device memory; the call clears them on `stream` (a one-wave launch, not a memset node) and one
  * launch ORs into word t  bit 0 when tensor t holds a NaN,  bit 1 when it holds +-Inf.
  * Elements are classified from their exponent / mantissa bits.  Workgroups stride over
  * SCA_GUARD_CHUNK-element chunks (no chunk spans two tensors), with 16-byte loads between the
@@ -767,6 +793,43 @@ int sca_finite_scan(int ntensors, const float* const* ptrs, const long* numels, 
 #define SCA_REPORT_MAX_DISTILL 8
 int sca_step_report(const unsigned* flags, int nflags, const float* alignment_loss, const float* fuse_coord_loss,
                     int ndistill, const float* const* distill, float* total_loss, void* report, void* stream);
+
+/* ---- evaluation step: device-side totals of a whole pass (opt.py:50-128) ----------------- */
+/* The state of one evaluation pass, in device memory; all zero = empty (clear it with a memset
+ * on the stream).  Only sca_eval_accumulate writes it, so a replayed graph appends where the
+ * previous replay stopped.                                                                  */
+#define SCA_EVAL_MAX_LOSSES (SCA_REPORT_MAX_DISTILL + 3)
+#define SCA_EVAL_LOG_DROPPED 1   /* overflow bit: a clip arrived at or beyond the log's capacity */
+#define SCA_EVAL_LOG_TRUNCATED 2 /* overflow bit: a hypothesis was longer than log_width         */
+typedef struct {
+  int cursor;        /* clips accumulated so far = the log row of the next step's clip 0        */
+  int steps;         /* calls accumulated so far                                                */
+  int overflow;      /* SCA_EVAL_LOG_* bits                                                     */
+  int first_flagged; /* 1 + the index of the first step with a non-zero flag word, 0 = none     */
+  int totals[SCA_EVAL_MAX_HEADS][4];      /* per head: sums of (num_del, num_ins, num_sub, num_ref) */
+  unsigned flags[SCA_REPORT_MAX_FLAGS];   /* OR of every step's flag words                      */
+  double loss_sum[SCA_EVAL_MAX_LOSSES];   /* per loss word, the float64 sum in step order       */
+} sca_eval_state;
+
+/* sca_eval_accumulate: one step's hypotheses scored and added to the state, two launches.
+ *   tokens (G, B, Hmax) / hyp_len (G, B): the grouped decoders' output (Hmax = their T)
+ *   ref (B, Rmax) / ref_len (B): the references, shared by all heads (indexed by clip)
+ *   report: the step's sca_step_report buffer: nflags flag words, then nloss fp32 loss words
+ *           (alignment_loss, fuse_coord_loss, the distillation terms, total_loss)
+ * Launch 1, one workgroup per (head, clip): the counts of sca_wer_counts into counts (G, B, 4)
+ * and, with integer atomic adds (they commute: deterministic), into state->totals[g]; when
+ * hyp_log is given, clip b's hypothesis goes to log row r = state->cursor + b:
+ * hyp_log[r][g][0 .. log_width) int32 zero-padded, hyp_len_log[r][g] its length.  Rows
+ * r >= capacity are not written and set SCA_EVAL_LOG_DROPPED; a hypothesis longer than
+ * log_width is cut and sets SCA_EVAL_LOG_TRUNCATED.
+ * Launch 2, one wave: loss_sum[i] += (double)loss word i, flags[i] |= flag word i,
+ * first_flagged, then cursor += B and steps += 1.
+ * 1 <= G <= 8, B >= 1, 0 <= Rmax, Hmax <= 128, nflags <= 64, nloss <= 11, capacity >= 0
+ * (0: no log; else hyp_log, hyp_len_log and log_width >= 1 are required).                  */
+int sca_eval_accumulate(const int* tokens, const int* hyp_len, int G, int B, int Hmax, const int* ref,
+                        const int* ref_len, int Rmax, const void* report, int nflags, int nloss, int* counts,
+                        sca_eval_state* state, int* hyp_log, int* hyp_len_log, int capacity, int log_width,
+                        void* stream);
 
 const char* sca_last_error(void);
 int sca_version(void);

@@ -30,6 +30,9 @@ DROPOUT_MAX_PROBLEMS = 12
 ACT_NONE, ACT_RELU = 0, 1
 GUARD_MAX_TENSORS, GUARD_CHUNK = 16, 4096
 REPORT_MAX_FLAGS, REPORT_MAX_DISTILL = 64, 8
+EVAL_MAX_HEADS, EVAL_MAX_LOSSES = 8, REPORT_MAX_DISTILL + 3
+EVAL_LOG_DROPPED, EVAL_LOG_TRUNCATED = 1, 2
+WER_MAX_LEN = 128
 
 
 class GemmSeg(ctypes.Structure):
@@ -141,6 +144,16 @@ class OptimState(ctypes.Structure):
     _fields_ = [("step", c_int), ("skipped", c_int), ("grad_norm", c_float), ("clip_coef", c_float)]
 
 
+class DecodeHeads(ctypes.Structure):
+    _fields_ = [("logits", c_void_p * EVAL_MAX_HEADS)]
+
+
+class EvalState(ctypes.Structure):
+    _fields_ = [("cursor", c_int), ("steps", c_int), ("overflow", c_int), ("first_flagged", c_int),
+                ("totals", (c_int * 4) * EVAL_MAX_HEADS), ("flags", ctypes.c_uint * REPORT_MAX_FLAGS),
+                ("loss_sum", ctypes.c_double * EVAL_MAX_LOSSES)]
+
+
 EXPORTS = {
     "sca_gemm": ([c_int, c_int, c_void_p, c_int, c_void_p, c_void_p], c_int),
     "sca_gemm_partial": ([c_int, c_int, c_void_p, c_int, c_void_p, c_void_p], c_int),
@@ -201,6 +214,11 @@ EXPORTS = {
     "sca_ctc_greedy_decode": ([c_void_p, c_void_p] + [c_int] * 3 + [c_void_p] * 5, c_int),
     "sca_ctc_beam_decode": ([c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 5, c_int),
     "sca_wer_counts": ([c_void_p] * 4 + [c_int] * 3 + [c_void_p, c_void_p], c_int),
+    "sca_ctc_decode_heads_workspace_bytes": ([c_int] * 5, c_long),
+    "sca_ctc_greedy_decode_heads": ([c_void_p, c_int, c_void_p] + [c_int] * 3 + [c_void_p] * 5, c_int),
+    "sca_ctc_beam_decode_heads": ([c_void_p, c_int, c_void_p] + [c_int] * 5 + [c_void_p] * 5, c_int),
+    "sca_eval_accumulate": ([c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                             c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p], c_int),
     "sca_optim_blocks": ([c_int, c_int], c_int),
     "sca_optim_grad_sqnorm": ([c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
     "sca_optim_adam_step": ([c_void_p, c_void_p, c_int, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p],

@@ -30,15 +30,30 @@ struct DecDims {
   int B, T, C, W;
 };
 
-// workspace layout: rowstat float[2 BT] | cls int[BT (W+1)] | clp float[BT (W+1)] |
-// arena u64[B (T W + 1)] (dec_pl words).  The greedy path keeps its per-frame arg-max in cls.
+// The logit tensors of the G heads decoded by one launch, by value in the kernel arguments.
+// A (head, clip) pair is "clip" n = g B + b of the workspace and of the outputs, so the
+// single-head entry points are the case G = 1.
+struct DecHeads {
+  const float* x[SCA_EVAL_MAX_HEADS];
+};
+
+// head g's tensor: a uniform select chain, so the by-value table stays in scalar registers
+__device__ __forceinline__ const float* dec_head(const DecHeads& h, int g) {
+  const float* p = h.x[0];
+#pragma unroll
+  for (int i = 1; i < SCA_EVAL_MAX_HEADS; ++i) p = g == i ? h.x[i] : p;
+  return p;
+}
+
+// workspace layout, N = G B clips: rowstat float[2 NT] | cls int[NT (W+1)] | clp float[NT (W+1)] |
+// arena u64[N (T W + 1)] (dec_pl words).  The greedy path keeps its per-frame arg-max in cls.
 struct DecWs {
   float* rowstat;
   int* cls;
   float* clp;
   unsigned long long* arena;
-  __host__ __device__ DecWs(void* ws, DecDims d) {
-    const long BT = (long)d.B * d.T, K = d.W + 1;
+  __host__ __device__ DecWs(void* ws, DecDims d, int G = 1) {
+    const long BT = (long)G * d.B * d.T, K = d.W + 1;
     rowstat = static_cast<float*>(ws);
     cls = reinterpret_cast<int*>(rowstat + 2 * BT);
     clp = reinterpret_cast<float*>(cls + BT * K);
@@ -84,17 +99,39 @@ __device__ __forceinline__ unsigned long long dec_pl(int par, int lab) {
 __device__ __forceinline__ int dec_par(unsigned long long v) { return (int)(v >> 32); }
 __device__ __forceinline__ int dec_lab(unsigned long long v) { return (int)(v & 0xffffffffull); }
 
-// One wave per (b, t) row: the K = min(W + 1, C - 1) labels (c != 0) with the largest
-// log-probability, in descending order, ties to the lower class.  Round k takes the best
-// element strictly after round k - 1's pick in that order, so nothing is marked as taken.
-__global__ __launch_bounds__(256) void ctc_topk_kernel(const float* __restrict__ x, const int* __restrict__ in_len,
-                                                       DecDims d, DecWs w) {
+// One wave per (g, b, t) row: max and log-sum-exp of the logits row, the arithmetic of the
+// CTC loss's row pass (heads.hip, ctc_rowstat_kernel) over the rows of G tensors.
+__global__ __launch_bounds__(256) void ctc_rowstat_heads_kernel(DecHeads hx, float* __restrict__ rowstat, long rows,
+                                                                long rows_per_head, int C) {
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
-  if (row >= (long)d.B * d.T) return;
-  const int b = (int)(row / d.T), t = (int)(row - (long)b * d.T);
+  if (row >= rows) return;
+  const int g = (int)(row / rows_per_head);
+  const float* xr = dec_head(hx, g) + (row - g * rows_per_head) * C;
+  float m = NEG_INF;
+  for (int c = lane; c < C; c += 64) m = fmaxf(m, xr[c]);
+  m = wave_max(m);
+  float s = 0.0f;
+  for (int c = lane; c < C; c += 64) s += __expf(xr[c] - m);
+  s = wave_sum(s);
+  if (lane == 0) {
+    rowstat[2 * row] = m;
+    rowstat[2 * row + 1] = __logf(s);
+  }
+}
+
+// One wave per (g, b, t) row: the K = min(W + 1, C - 1) labels (c != 0) with the largest
+// log-probability, in descending order, ties to the lower class.  Round k takes the best
+// element strictly after round k - 1's pick in that order, so nothing is marked as taken.
+__global__ __launch_bounds__(256) void ctc_topk_kernel(DecHeads hx, int G, const int* __restrict__ in_len, DecDims d,
+                                                       DecWs w) {
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= (long)G * d.B * d.T) return;
+  const int n = (int)(row / d.T), t = (int)(row - (long)n * d.T);  // n = g B + b
+  const int g = n / d.B, b = n - g * d.B;
   if (t >= clampi(in_len[b], 0, d.T)) return;
-  const float* xr = x + row * d.C;
+  const float* xr = dec_head(hx, g) + ((long)b * d.T + t) * d.C;
   const float m = w.rowstat[2 * row], ls = w.rowstat[2 * row + 1];
   const int K = min(d.W + 1, d.C - 1);
   float pv = 0.0f;
@@ -117,8 +154,8 @@ __global__ __launch_bounds__(256) void ctc_topk_kernel(const float* __restrict__
   }
 }
 
-// One workgroup (one wave) per clip.  Beam slot state lives in LDS, double-buffered; slots
-// are kept sorted by total, so slot 0 is the best beam.  A prefix is a node (parent, label)
+// One workgroup (one wave) per (clip, head): grid (B, G).  Beam slot state lives in LDS,
+// double-buffered; slots are kept sorted by total, so slot 0 is the best beam.  A prefix is a node (parent, label)
 // of the clip's arena; a candidate whose (parent, label) pair already has a node (a pruned
 // prefix that comes back) takes that node again, so a prefix has one node for good and
 // "is this prefix an active beam" is a comparison of node ids.  Log-probabilities are kept
@@ -134,8 +171,8 @@ __global__ __launch_bounds__(256) void ctc_topk_kernel(const float* __restrict__
 // that leave those loads in flight.  The beam_width best of the M <= W (W + 2) items are
 // found by counting, for each item, the items in front of it (M LDS broadcast reads per
 // item, no cross-lane traffic).
-__global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ x, const int* __restrict__ in_len,
-                                                      DecDims d, int collapse, int* __restrict__ tokens,
+__global__ __launch_bounds__(64) void ctc_beam_kernel(DecHeads hx, const int* __restrict__ in_len, DecDims d,
+                                                      int collapse, int* __restrict__ tokens,
                                                       int* __restrict__ out_len, float* __restrict__ score,
                                                       DecWs w) {
   __shared__ int s_node[2][DEC_MAX_W], s_lab[2][DEC_MAX_W], s_par[2][DEC_MAX_W];
@@ -152,20 +189,22 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
   __shared__ unsigned long long want[DEC_MAX_W];     // the node a fresh beam looks for, else ~0
   __shared__ unsigned long long a_lds[DEC_ARENA_LDS];
   __shared__ int s_len;
-  const int b = blockIdx.x, lane = threadIdx.x;
+  const int lane = threadIdx.x;
+  const int slot = (int)blockIdx.y * d.B + (int)blockIdx.x;  // the (head, clip)'s place in workspace and outputs
   const int T = d.T, C = d.C, W = d.W, KS = W + 1, K = min(W + 1, C - 1);
-  const int Tb = clampi(in_len[b], 0, T);
-  unsigned long long* arena = w.arena + (long)b * ((long)T * W + 1);
+  const int Tb = clampi(in_len[blockIdx.x], 0, T);
+  const float* __restrict__ x = dec_head(hx, blockIdx.y) + (long)blockIdx.x * T * C;  // the clip's (T, C) logits
+  unsigned long long* arena = w.arena + (long)slot * ((long)T * W + 1);
   int nn = 1, nb = 1, cur = 0;  // arena nodes, active beams, state buffer (all wave-uniform)
   double offset = 0.0;
   // the frame's beam-independent inputs, loaded one frame ahead
   float pm = 0.0f, pls = 0.0f, px0 = 0.0f, pclp = NEG_INF;
   int pcls = 0;
   auto prefetch = [&](int t) {
-    const long row = (long)b * T + t;
+    const long row = (long)slot * T + t;
     pm = w.rowstat[2 * row];
     pls = w.rowstat[2 * row + 1];
-    px0 = x[row * C];
+    px0 = x[(long)t * C];
     if (lane < K) {
       pcls = w.cls[row * KS + lane];
       pclp = w.clp[row * KS + lane];
@@ -186,7 +225,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
     if (lane < W) sel[lane] = -1;
     float nxc = 0.0f, nxb = 0.0f;
     if (t + 1 < Tb) {  // wave-uniform
-      const float* xn = x + ((long)b * T + t + 1) * C;
+      const float* xn = x + (long)(t + 1) * C;
       if (lane < K) nxc = xn[pcls];
       if (lane < nb) nxb = xn[s_lab[cur][lane]];
       prefetch(t + 1);
@@ -320,7 +359,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
   }
   __syncthreads();
   // slot 0 is the best beam (ties to the lower slot); walk its prefix back to the root
-  int* tok = tokens + (long)b * T;
+  int* tok = tokens + (long)slot * T;
   if (lane == 0) {
     const int leaf = s_node[cur][0];
     int len = 0;
@@ -341,32 +380,34 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
       len = o;
     }
     s_len = len;
-    out_len[b] = len;
-    score[b] = (float)(offset + (double)s_tot[cur][0]);
+    out_len[slot] = len;
+    score[slot] = (float)(offset + (double)s_tot[cur][0]);
   }
   __syncthreads();
   for (int i = s_len + lane; i < T; i += 64) tok[i] = 0;
 }
 
-// One workgroup of 16 waves per clip: each wave takes every 16th frame's arg-max (ties to the
-// lowest class; a frame is a chain of dependent loads, so frames run side by side), then
-// wave 0 collapses repeats and drops blanks with a ballot scan.
+// One workgroup of 16 waves per (clip, head), grid (B, G): each wave takes every 16th frame's
+// arg-max (ties to the lowest class; a frame is a chain of dependent loads, so frames run side
+// by side), then wave 0 collapses repeats and drops blanks with a ballot scan.
 constexpr int GREEDY_WAVES = 16;
-__global__ __launch_bounds__(64 * GREEDY_WAVES) void ctc_greedy_kernel(const float* __restrict__ x,
+__global__ __launch_bounds__(64 * GREEDY_WAVES) void ctc_greedy_kernel(DecHeads hx,
                                                                         const int* __restrict__ in_len, DecDims d,
                                                                         int* __restrict__ tokens,
                                                                         int* __restrict__ out_len,
                                                                         float* __restrict__ score, DecWs w) {
   __shared__ float part[GREEDY_WAVES];
   __shared__ int s_len;
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int slot = (int)blockIdx.y * d.B + (int)blockIdx.x;
   const int T = d.T, C = d.C;
-  const int Tb = clampi(in_len[b], 0, T);
-  int* amax = w.cls + (long)b * T;
+  const int Tb = clampi(in_len[blockIdx.x], 0, T);
+  const float* __restrict__ x = dec_head(hx, blockIdx.y) + (long)blockIdx.x * T * C;
+  int* amax = w.cls + (long)slot * T;
   float acc = 0.0f;
   for (int t = wave; t < Tb; t += GREEDY_WAVES) {
-    const long row = (long)b * T + t;
-    const float* xr = x + row * C;
+    const long row = (long)slot * T + t;
+    const float* xr = x + (long)t * C;
     float bv = NEG_INF;
     int bc = NONE;
     for (int c = lane; c < C; c += 64) {
@@ -380,7 +421,7 @@ __global__ __launch_bounds__(64 * GREEDY_WAVES) void ctc_greedy_kernel(const flo
   }
   if (lane == 0) part[wave] = acc;
   __syncthreads();
-  int* tok = tokens + (long)b * T;
+  int* tok = tokens + (long)slot * T;
   if (wave == 0) {
     int count = 0;
     for (int base = 0; base < Tb; base += 64) {
@@ -394,10 +435,10 @@ __global__ __launch_bounds__(64 * GREEDY_WAVES) void ctc_greedy_kernel(const flo
     }
     if (lane == 0) {
       s_len = count;
-      out_len[b] = count;
+      out_len[slot] = count;
       float sum = 0.0f;
       for (int i = 0; i < GREEDY_WAVES; ++i) sum += part[i];
-      score[b] = sum;
+      score[slot] = sum;
     }
   }
   __syncthreads();
@@ -407,17 +448,18 @@ __global__ __launch_bounds__(64 * GREEDY_WAVES) void ctc_greedy_kernel(const flo
 constexpr int WER_LD = SCA_WER_MAX_LEN + 3;  // odd dword stride along an anti-diagonal
 constexpr int WER_DEL = 3, WER_INS = 3, WER_SUB = 4;
 
-// One workgroup per (reference, hypothesis) pair; thread i owns matrix row i + 1 and the
-// matrix is filled one anti-diagonal per barrier.  Lane 0 walks the alignment back.
-__global__ __launch_bounds__(128) void wer_kernel(const int* __restrict__ ref, const int* __restrict__ ref_len,
-                                                  const int* __restrict__ hyp, const int* __restrict__ hyp_len,
-                                                  int Rmax, int Hmax, int* __restrict__ counts) {
+// One workgroup (128 threads) per (reference, hypothesis) pair; thread i owns matrix row i + 1
+// and the matrix is filled one anti-diagonal per barrier.  Thread 0 walks the alignment back
+// and writes out[0..4) = (num_del, num_ins, num_sub, num_ref); the other threads' `out` is
+// not touched.  R <= SCA_WER_MAX_LEN tokens at r, H <= SCA_WER_MAX_LEN at h (both clamped by
+// the caller).  Ends with the hypothesis still in h_s for thread-parallel readers.
+__device__ __forceinline__ void wer_pair(const int* __restrict__ r, int R, const int* __restrict__ h, int H,
+                                         int* __restrict__ out) {
   __shared__ unsigned short dm[(SCA_WER_MAX_LEN + 1) * WER_LD];
   __shared__ int r_s[SCA_WER_MAX_LEN], h_s[SCA_WER_MAX_LEN];
-  const int n = blockIdx.x, tid = threadIdx.x;
-  const int R = clampi(ref_len[n], 0, Rmax), H = clampi(hyp_len[n], 0, Hmax);
-  if (tid < R) r_s[tid] = ref[(long)n * Rmax + tid];
-  if (tid < H) h_s[tid] = hyp[(long)n * Hmax + tid];
+  const int tid = threadIdx.x;
+  if (tid < R) r_s[tid] = r[tid];
+  if (tid < H) h_s[tid] = h[tid];
   for (int j = tid; j <= H; j += 128) dm[j] = (unsigned short)(j * WER_INS);
   for (int i = tid; i <= R; i += 128) dm[i * WER_LD] = (unsigned short)(i * WER_DEL);
   __syncthreads();
@@ -446,13 +488,98 @@ __global__ __launch_bounds__(128) void wer_kernel(const int* __restrict__ ref, c
         ++nd; xx = max(xx - 1, 0);
       }
     }
-    int* out = counts + 4L * n;
     out[0] = nd; out[1] = ni; out[2] = ns; out[3] = R;
+  }
+}
+
+__global__ __launch_bounds__(128) void wer_kernel(const int* __restrict__ ref, const int* __restrict__ ref_len,
+                                                  const int* __restrict__ hyp, const int* __restrict__ hyp_len,
+                                                  int Rmax, int Hmax, int* __restrict__ counts) {
+  const int n = blockIdx.x;
+  const int R = clampi(ref_len[n], 0, Rmax), H = clampi(hyp_len[n], 0, Hmax);
+  wer_pair(ref + (long)n * Rmax, R, hyp + (long)n * Hmax, H, counts + 4L * n);
+}
+
+struct EvalLog {
+  int* hyp;      // (capacity, G, width) or NULL
+  int* hyp_len;  // (capacity, G)
+  int capacity, width;
+};
+
+// Launch 1 of sca_eval_accumulate, grid (B, G): the pair (reference b, head g's hypothesis of
+// clip b).  The references are indexed by clip, not tiled over the heads.  cursor is read
+// here and advanced by launch 2, which the stream orders behind every workgroup of this one.
+__global__ __launch_bounds__(128) void eval_score_kernel(const int* __restrict__ tokens,
+                                                         const int* __restrict__ hyp_len, int Hmax,
+                                                         const int* __restrict__ ref, const int* __restrict__ ref_len,
+                                                         int Rmax, int* __restrict__ counts, sca_eval_state* state,
+                                                         EvalLog log) {
+  const int b = blockIdx.x, g = blockIdx.y, B = gridDim.x, G = gridDim.y, tid = threadIdx.x;
+  const long n = (long)g * B + b;
+  const int R = clampi(ref_len[b], 0, Rmax), H = clampi(hyp_len[n], 0, Hmax);
+  const int* hrow = tokens + n * Hmax;
+  int* out = counts + 4 * n;
+  wer_pair(ref + (long)b * Rmax, R, hrow, H, out);
+  if (tid == 0) {  // integer adds commute: the totals do not depend on the order of arrival
+#pragma unroll
+    for (int k = 0; k < 4; ++k) atomicAdd(&state->totals[g][k], out[k]);
+  }
+  if (log.hyp) {
+    const long row = (long)state->cursor + b;
+    if (row < log.capacity) {
+      int* dst = log.hyp + (row * G + g) * log.width;
+      for (int i = tid; i < log.width; i += 128) dst[i] = i < H ? hrow[i] : 0;
+      if (tid == 0) log.hyp_len[row * G + g] = min(H, log.width);
+      if (tid == 0 && H > log.width) atomicOr(&state->overflow, SCA_EVAL_LOG_TRUNCATED);
+    } else if (tid == 0) {
+      atomicOr(&state->overflow, SCA_EVAL_LOG_DROPPED);
+    }
+  }
+}
+
+// Launch 2, one wave: the step's report into the pass's sums, then the cursor moves on.
+__global__ __launch_bounds__(64) void eval_advance_kernel(const unsigned* __restrict__ report, int nflags, int nloss,
+                                                          int B, sca_eval_state* state) {
+  const int lane = threadIdx.x;
+  unsigned any = 0;
+  for (int i = lane; i < nflags; i += 64) {
+    const unsigned f = report[i];
+    if (f) state->flags[i] |= f;
+    any |= f;
+  }
+  const bool flagged = __any(any != 0);
+  if (lane < nloss) state->loss_sum[lane] += (double)__uint_as_float(report[nflags + lane]);
+  if (lane == 0) {
+    const int steps = state->steps;
+    if (flagged && state->first_flagged == 0) state->first_flagged = steps + 1;
+    state->steps = steps + 1;
+    state->cursor += B;
   }
 }
 
 bool dec_dims_ok(int B, int T, int C, int W) {
   return B >= 1 && T >= 1 && C >= 1 && C <= SCA_CTC_MAX_C && W >= 1 && W <= SCA_CTC_MAX_BEAM;
+}
+
+// G B clips must stay countable in an int (the kernels' slot index)
+bool dec_heads_ok(const sca_decode_heads* heads, int G, int B, int T, int C, int W) {
+  if (G < 1 || G > SCA_EVAL_MAX_HEADS || !dec_dims_ok(B, T, C, W) || (long)G * B > 0x7fffffffL / 4 || !heads)
+    return false;
+  for (int g = 0; g < G; ++g)
+    if (!heads->logits[g]) return false;
+  return true;
+}
+
+DecHeads dec_heads_of(const sca_decode_heads* heads, int G) {
+  DecHeads h = {};
+  for (int g = 0; g < SCA_EVAL_MAX_HEADS; ++g) h.x[g] = heads->logits[g < G ? g : 0];
+  return h;
+}
+
+DecHeads dec_one_head(const float* logits) {
+  DecHeads h = {};
+  for (int g = 0; g < SCA_EVAL_MAX_HEADS; ++g) h.x[g] = logits;
+  return h;
 }
 
 }  // namespace
@@ -461,6 +588,12 @@ extern "C" long sca_ctc_decode_workspace_bytes(int B, int T, int C, int W) {
   if (!dec_dims_ok(B, T, C, W)) return 0;
   const long BT = (long)B * T;
   return 4 * (2 * BT + 2 * BT * (W + 1)) + 8 * (long)B * ((long)T * W + 1);
+}
+
+extern "C" long sca_ctc_decode_heads_workspace_bytes(int G, int B, int T, int C, int W) {
+  if (G < 1 || G > SCA_EVAL_MAX_HEADS || !dec_dims_ok(B, T, C, W)) return 0;
+  const long N = (long)G * B, NT = N * T;  // the single-head layout over N = G B clips
+  return 4 * (2 * NT + 2 * NT * (W + 1)) + 8 * N * ((long)T * W + 1);
 }
 
 extern "C" int sca_ctc_greedy_decode(const float* logits, const int* in_len, int B, int T, int C, int* tokens,
@@ -473,8 +606,8 @@ extern "C" int sca_ctc_greedy_decode(const float* logits, const int* in_len, int
   const DecDims d{B, T, C, 1};
   const DecWs w(ws, d);
   sca_ctc_rowstat_launch(logits, w.rowstat, (long)B * T, C, st);
-  hipLaunchKernelGGL(ctc_greedy_kernel, dim3(B), dim3(64 * GREEDY_WAVES), 0, st, logits, in_len, d, tokens, out_len,
-                     score, w);
+  hipLaunchKernelGGL(ctc_greedy_kernel, dim3(B), dim3(64 * GREEDY_WAVES), 0, st, dec_one_head(logits), in_len, d,
+                     tokens, out_len, score, w);
   if (hipGetLastError() != hipSuccess) { sca_set_error("sca_ctc_greedy_decode: launch failed"); return SCA_ERR_LAUNCH; }
   return SCA_OK;
 }
@@ -489,12 +622,61 @@ extern "C" int sca_ctc_beam_decode(const float* logits, const int* in_len, int B
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const DecDims d{B, T, C, beam_width};
   const DecWs w(ws, d);
+  const DecHeads hx = dec_one_head(logits);
   const long rows = (long)B * T;
   sca_ctc_rowstat_launch(logits, w.rowstat, rows, C, st);
-  hipLaunchKernelGGL(ctc_topk_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, logits, in_len, d, w);
-  hipLaunchKernelGGL(ctc_beam_kernel, dim3(B), dim3(64), 0, st, logits, in_len, d, collapse_repeats != 0, tokens,
-                     out_len, score, w);
+  hipLaunchKernelGGL(ctc_topk_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, hx, 1, in_len, d, w);
+  hipLaunchKernelGGL(ctc_beam_kernel, dim3(B), dim3(64), 0, st, hx, in_len, d, collapse_repeats != 0, tokens, out_len,
+                     score, w);
   if (hipGetLastError() != hipSuccess) { sca_set_error("sca_ctc_beam_decode: launch failed"); return SCA_ERR_LAUNCH; }
+  return SCA_OK;
+}
+
+extern "C" int sca_ctc_greedy_decode_heads(const sca_decode_heads* heads, int G, const int* in_len, int B, int T,
+                                           int C, int* tokens, int* out_len, float* score, void* ws, void* stream) {
+  if (!dec_heads_ok(heads, G, B, T, C, 1) || !in_len || !tokens || !out_len || !score || !ws) {
+    sca_set_error("sca_ctc_greedy_decode_heads: bad arguments (1 <= G <= 8 non-null tensors, B, T >= 1, "
+                  "1 <= C <= 8192)");
+    return SCA_ERR_ARG;
+  }
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const DecDims d{B, T, C, 1};
+  const DecWs w(ws, d, G);
+  const DecHeads hx = dec_heads_of(heads, G);
+  const long rows = (long)G * B * T;
+  hipLaunchKernelGGL(ctc_rowstat_heads_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, hx, w.rowstat, rows,
+                     (long)B * T, C);
+  hipLaunchKernelGGL(ctc_greedy_kernel, dim3(B, G), dim3(64 * GREEDY_WAVES), 0, st, hx, in_len, d, tokens, out_len,
+                     score, w);
+  if (hipGetLastError() != hipSuccess) {
+    sca_set_error("sca_ctc_greedy_decode_heads: launch failed");
+    return SCA_ERR_LAUNCH;
+  }
+  return SCA_OK;
+}
+
+extern "C" int sca_ctc_beam_decode_heads(const sca_decode_heads* heads, int G, const int* in_len, int B, int T, int C,
+                                         int beam_width, int collapse_repeats, int* tokens, int* out_len, float* score,
+                                         void* ws, void* stream) {
+  if (!dec_heads_ok(heads, G, B, T, C, beam_width) || !in_len || !tokens || !out_len || !score || !ws) {
+    sca_set_error("sca_ctc_beam_decode_heads: bad arguments (1 <= G <= 8 non-null tensors, B, T >= 1, "
+                  "1 <= C <= 8192, 1 <= beam_width <= 32)");
+    return SCA_ERR_ARG;
+  }
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const DecDims d{B, T, C, beam_width};
+  const DecWs w(ws, d, G);
+  const DecHeads hx = dec_heads_of(heads, G);
+  const long rows = (long)G * B * T;
+  const dim3 row_grid((unsigned)((rows + 3) / 4));
+  hipLaunchKernelGGL(ctc_rowstat_heads_kernel, row_grid, dim3(256), 0, st, hx, w.rowstat, rows, (long)B * T, C);
+  hipLaunchKernelGGL(ctc_topk_kernel, row_grid, dim3(256), 0, st, hx, G, in_len, d, w);
+  hipLaunchKernelGGL(ctc_beam_kernel, dim3(B, G), dim3(64), 0, st, hx, in_len, d, collapse_repeats != 0, tokens,
+                     out_len, score, w);
+  if (hipGetLastError() != hipSuccess) {
+    sca_set_error("sca_ctc_beam_decode_heads: launch failed");
+    return SCA_ERR_LAUNCH;
+  }
   return SCA_OK;
 }
 
@@ -508,5 +690,28 @@ extern "C" int sca_wer_counts(const int* ref, const int* ref_len, const int* hyp
   hipLaunchKernelGGL(wer_kernel, dim3(N), dim3(128), 0, reinterpret_cast<hipStream_t>(stream), ref, ref_len, hyp,
                      hyp_len, Rmax, Hmax, counts);
   if (hipGetLastError() != hipSuccess) { sca_set_error("sca_wer_counts: launch failed"); return SCA_ERR_LAUNCH; }
+  return SCA_OK;
+}
+
+extern "C" int sca_eval_accumulate(const int* tokens, const int* hyp_len, int G, int B, int Hmax, const int* ref,
+                                   const int* ref_len, int Rmax, const void* report, int nflags, int nloss,
+                                   int* counts, sca_eval_state* state, int* hyp_log, int* hyp_len_log, int capacity,
+                                   int log_width, void* stream) {
+  const bool log = capacity > 0;
+  if (G < 1 || G > SCA_EVAL_MAX_HEADS || B < 1 || Rmax < 0 || Rmax > SCA_WER_MAX_LEN || Hmax < 0 ||
+      Hmax > SCA_WER_MAX_LEN || nflags < 0 || nflags > SCA_REPORT_MAX_FLAGS || nloss < 0 ||
+      nloss > SCA_EVAL_MAX_LOSSES || capacity < 0 || !hyp_len || !ref_len || (Rmax > 0 && !ref) ||
+      (Hmax > 0 && !tokens) || !report || !counts || !state || (log && (!hyp_log || !hyp_len_log || log_width < 1))) {
+    sca_set_error("sca_eval_accumulate: bad arguments (1 <= G <= 8, B >= 1, 0 <= Rmax, Hmax <= 128, "
+                  "nflags <= 64, nloss <= 11, a log needs hyp_log, hyp_len_log and log_width >= 1)");
+    return SCA_ERR_ARG;
+  }
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const EvalLog lg{log ? hyp_log : nullptr, log ? hyp_len_log : nullptr, capacity, log_width};
+  hipLaunchKernelGGL(eval_score_kernel, dim3(B, G), dim3(128), 0, st, tokens, hyp_len, Hmax, ref, ref_len, Rmax, counts,
+                     state, lg);
+  hipLaunchKernelGGL(eval_advance_kernel, dim3(1), dim3(64), 0, st, static_cast<const unsigned*>(report), nflags, nloss,
+                     B, state);
+  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_eval_accumulate: launch failed"); return SCA_ERR_LAUNCH; }
   return SCA_OK;
 }

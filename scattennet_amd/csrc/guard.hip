@@ -73,6 +73,10 @@ __global__ __launch_bounds__(GUARD_THREADS) void finite_scan_kernel(ScanArgs a, 
   if ((int)threadIdx.x < a.ntensors && found[threadIdx.x]) atomicOr(flags + threadIdx.x, found[threadIdx.x]);
 }
 
+__global__ __launch_bounds__(64) void flags_clear_kernel(uint32_t* __restrict__ flags, int n) {
+  if ((int)threadIdx.x < n) flags[threadIdx.x] = 0u;  // n <= SCA_GUARD_MAX_TENSORS
+}
+
 struct ReportArgs {
   const float* distill[SCA_REPORT_MAX_DISTILL];
   int ndistill;
@@ -135,13 +139,14 @@ extern "C" int sca_finite_scan(int ntensors, const float* const* ptrs, const lon
     }
   }
   for (int t = ntensors; t <= SCA_GUARD_MAX_TENSORS; ++t) a.first_chunk[t] = (int)chunks;
-  // the flag words are cleared on the stream (a memset node under capture), then OR-ed into
-  if (hipMemsetAsync(flags, 0, sizeof(unsigned) * ntensors, (hipStream_t)stream) != hipSuccess) {
-    (void)hipGetLastError();
-    sca_set_error("sca_finite_scan: hipMemsetAsync failed");
-    return SCA_ERR_LAUNCH;
+  // the flag words are cleared on the stream, then OR-ed into.  A kernel, not hipMemsetAsync: a
+  // memset node of a replayed graph was seen to fill the words with a stale 16-byte pattern
+  // once the host had made enough pageable copies in between (evaluation step)
+  hipLaunchKernelGGL(flags_clear_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, flags, ntensors);
+  if (chunks == 0) {
+    if (hipGetLastError() != hipSuccess) { sca_set_error("sca_finite_scan: launch failed"); return SCA_ERR_LAUNCH; }
+    return SCA_OK;
   }
-  if (chunks == 0) return SCA_OK;
   const int grid = chunks < GUARD_MAX_BLOCKS ? (int)chunks : GUARD_MAX_BLOCKS;
   hipLaunchKernelGGL(finite_scan_kernel, dim3(grid), dim3(GUARD_THREADS), 0, (hipStream_t)stream, a, flags);
   if (hipGetLastError() != hipSuccess) { sca_set_error("sca_finite_scan: launch failed"); return SCA_ERR_LAUNCH; }

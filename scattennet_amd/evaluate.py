@@ -1,0 +1,392 @@
+"""The evaluation step of evaluate_fn (opt.py:50-128) on the device: forward, CTC decoding of
+every evaluated head in one grouped launch, WER counts and the pass's totals, with no host
+read until the pass is over.
+
+* `ctc_decode_heads_device` — `sca_ctc_beam_decode_heads` / `sca_ctc_greedy_decode_heads`: the
+  G logit tensors of one forward decoded together, bitwise what `ctc_decode_device` gives per
+  head.
+* `EvalState` — the pass's device state (`sca_eval_state`, include/scatten.h): per-head WER
+  totals, float64 loss sums, the OR of the finite guard's flag words, and an optional log of
+  every hypothesis.  `read()` is the single host read and returns the dict `evaluate_fn`
+  returns; `hypotheses()` returns the logged token ids.
+* `eval_step(model, src_input, state, beam_size=5)` — forward (finite check deferred), grouped
+  decode, `sca_eval_accumulate`.  No host read; capturable for a fixed (B, T, S) by the rules
+  of `train.py`.  It does NOT touch the model's `training` flag: call `model.eval()` first, as
+  `evaluate_fn` does (opt.py:62) — a model left in training mode is evaluated with dropout.
+* `BucketedEvalStep` — `BucketedTrainStep`'s scheme for evaluation: batches of any length are
+  padded to a frame bucket, each bucket's step is captured on its second use and replayed
+  after, and all buckets append to one `EvalState`.
+
+`{name}wer` keys use the reference's `logits_name` (the output key without "gloss_logits":
+"alignment_", "fuse_coord_").  Hypotheses are class ids; the tokenizer, the results JSON and
+the logging of `evaluate_fn` stay with the caller.
+"""
+import ctypes
+
+import numpy as np
+import torch
+from torch import nn
+
+from . import _lib as L
+from . import heads as _heads
+from .bucketed import _Bucket, check_buckets, pad_batch, pick_bucket
+from .decode import MAX_BEAM, WER_MAX_LEN, _check_device, _check_lengths, _check_logits, wer_from_counts
+from .encoder import n_pool_of
+from .heads import _dev_i32
+from .model import _LOGITS, _students_of, first_error, flag_names
+from .precision import fp32_compute
+
+MAX_HEADS = L.EVAL_MAX_HEADS
+
+
+def logits_name(key):
+    """opt.py:82: the output key without "gloss_logits"."""
+    return key.replace("gloss_logits", "")
+
+
+def default_heads():
+    """The keys evaluate_fn decodes (opt.py:80): those containing "gloss_logits"."""
+    return tuple(k for k in _LOGITS if "gloss_logits" in k)
+
+
+def loss_names(students=()):
+    """The loss words of `finite_report` that a pass sums, in report order."""
+    return ["alignment_loss", "fuse_coord_loss"] + [f"{s}_distill_loss" for s in students] + ["total_loss"]
+
+
+# ------------------------------------------------------------------------ grouped decoding
+class _HeadsDecoder(nn.Module):
+    """Parameter-free module, so that fp16 / bf16 logits take the fp32 view of fp32_compute."""
+
+    @fp32_compute()
+    def forward(self, in_len, beam, collapse, *logits):
+        xs = [x.detach().contiguous() for x in logits]
+        L.require_device(*xs)
+        G = len(xs)
+        B, T, C = xs[0].shape
+        lib = L.lib()
+        nbytes = lib.sca_ctc_decode_heads_workspace_bytes(G, B, T, C, max(beam, 1))
+        dev = xs[0].device
+        tokens = torch.empty(G, B, T, dtype=torch.int32, device=dev)
+        lengths = torch.empty(G, B, dtype=torch.int32, device=dev)
+        scores = xs[0].new_empty(G, B)
+        ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.int64, device=dev)
+        hx = L.DecodeHeads()
+        for g, x in enumerate(xs):
+            hx.logits[g] = x.data_ptr()
+        if beam == 0:
+            L.check(lib.sca_ctc_greedy_decode_heads(ctypes.byref(hx), G, L.ptr(in_len), B, T, C, L.ptr(tokens),
+                                                    L.ptr(lengths), L.ptr(scores), L.ptr(ws), L.stream_handle()),
+                    "sca_ctc_greedy_decode_heads")
+        else:
+            L.check(lib.sca_ctc_beam_decode_heads(ctypes.byref(hx), G, L.ptr(in_len), B, T, C, beam, int(collapse),
+                                                  L.ptr(tokens), L.ptr(lengths), L.ptr(scores), L.ptr(ws),
+                                                  L.stream_handle()), "sca_ctc_beam_decode_heads")
+        return tokens, lengths, scores
+
+
+_heads_decoder = _HeadsDecoder()
+
+
+def _check_heads(logits_list):
+    xs = list(logits_list)
+    if not 1 <= len(xs) <= MAX_HEADS:
+        raise ValueError(f"ctc_decode_heads: between 1 and {MAX_HEADS} logit tensors, got {len(xs)}")
+    for x in xs:
+        _check_logits(x)
+    first = xs[0]
+    for x in xs[1:]:
+        if x.shape != first.shape or x.dtype != first.dtype or x.device != first.device:
+            raise ValueError("ctc_decode_heads: every head must have the same shape, dtype and device; got "
+                             f"{tuple(first.shape)} {first.dtype} {first.device} and {tuple(x.shape)} {x.dtype} "
+                             f"{x.device}")
+    return xs
+
+
+def ctc_decode_heads_device(logits_list, input_lengths, beam_size=1, collapse_repeats=True):
+    """`ctc_decode_device` over the G heads of one forward in one grouped call
+    (`sca_ctc_beam_decode_heads`; `beam_size=0`: `sca_ctc_greedy_decode_heads`).  `logits_list`:
+    1..8 tensors of one shape (B, T, C), all decoded with `input_lengths` (B).  Returns (tokens
+    (G, B, T) int32 padded with 0, lengths (G, B) int32, scores (G, B)) on the device: row g is
+    bitwise what the single-head call returns for `logits_list[g]`.  No host sync; capturable."""
+    xs = _check_heads(logits_list)
+    beam = int(beam_size)
+    if beam and not 1 <= beam <= MAX_BEAM:
+        raise ValueError(f"ctc_decode: beam_size must lie in [1, {MAX_BEAM}], got {beam}")
+    B, T, _ = xs[0].shape
+    il = _check_lengths(input_lengths, B, T)
+    _check_device(xs[0])
+    return _heads_decoder(_dev_i32(il, xs[0].device), beam, bool(collapse_repeats), *xs)
+
+
+# ------------------------------------------------------------------------------ the state
+def results_from_state(raw, head_keys, loss_keys, flag_keys):
+    """The dict evaluate_fn returns (opt.py:101-128), from the raw state of a pass.  Pure host
+    function.  `raw`: {"steps", "overflow", "first_flagged", "flags" [>= len(flag_keys)],
+    "totals" [>= len(head_keys)][4], "loss_sum" [>= len(loss_keys)] float64}.
+
+    * every loss key: sum of the steps' values / steps (MetricLogger's global_avg over
+      `update(k=value)` once per step); `loss`: the same for `total_loss` (opt.py:101)
+    * `{logits_name}wer`: metrics.wer_list over all clips of the pass (a zero total counts as 1)
+    * `wer`: the minimum over the heads, starting from 200 (opt.py:104, 116-118)
+
+    Raises the reference's ValueError (model/__init__.py:130-235) for the first flagged tensor
+    when any step was flagged, RuntimeError when the hypothesis log overflowed."""
+    msg = first_error(list(raw["flags"])[:len(flag_keys)], flag_keys)
+    if msg is not None:  # raw["first_flagged"] - 1 is the step that was flagged first
+        raise ValueError(msg)
+    over = int(raw["overflow"])
+    if over & L.EVAL_LOG_DROPPED:
+        raise RuntimeError("EvalState: the hypothesis log overflowed: more clips arrived than `capacity` rows")
+    if over & L.EVAL_LOG_TRUNCATED:
+        raise RuntimeError("EvalState: a hypothesis was longer than `log_width` and was cut in the log")
+    steps = int(raw["steps"])
+    if steps < 1:
+        raise RuntimeError("EvalState.read: no step has been accumulated")
+    out = {k: float(raw["loss_sum"][i]) / steps for i, k in enumerate(loss_keys)}
+    out["loss"] = out["total_loss"]
+    out["wer"] = 200
+    for g, key in enumerate(head_keys):
+        rate = wer_from_counts(torch.as_tensor(np.asarray(raw["totals"][g], dtype=np.int64)).reshape(1, 4))["wer"]
+        out[logits_name(key) + "wer"] = rate
+        out["wer"] = min(rate, out["wer"])
+    return out
+
+
+class EvalState:
+    """The device state of one evaluation pass (`sca_eval_state`, include/scatten.h), shared by
+    every `eval_step` of the pass.
+
+    `heads`: the output keys to decode and score, any subset of the five logit keys; default
+    the keys evaluate_fn decodes (`alignment_gloss_logits`, `fuse_coord_gloss_logits`).
+    `capacity` > 0 attaches a log of `capacity` clips: `hyp_log` (capacity, G, log_width) int32
+    zero-padded and `hyp_len_log` (capacity, G); `log_width` is then required (the longest
+    hypothesis: the pooled frame count).  `reset()` clears everything on the current stream."""
+
+    def __init__(self, model, heads=None, capacity=0, log_width=None):
+        keys = default_heads() if heads is None else tuple(heads)
+        if not 1 <= len(keys) <= MAX_HEADS or len(set(keys)) != len(keys):
+            raise ValueError(f"EvalState: heads must be 1..{MAX_HEADS} distinct keys, got {keys!r}")
+        for k in keys:
+            if k not in _LOGITS:
+                raise ValueError(f"EvalState: unknown head {k!r}; the logit keys are {_LOGITS}")
+        capacity = int(capacity)
+        if capacity < 0:
+            raise ValueError("EvalState: capacity must not be negative")
+        if capacity and (log_width is None or not 1 <= int(log_width) <= WER_MAX_LEN):
+            raise ValueError(f"EvalState: a log needs log_width in [1, {WER_MAX_LEN}], got {log_width!r}")
+        self.heads = keys
+        self.students = list(model._students())
+        self.flag_names = flag_names(self.students)
+        self.loss_names = loss_names(self.students)
+        self.capacity, self.log_width = capacity, int(log_width) if capacity else 0
+        self.device = next(model.parameters()).device
+        G = len(keys)
+        self.state = torch.zeros(ctypes.sizeof(L.EvalState) // 8, dtype=torch.int64, device=self.device)
+        self.hyp_log = self.hyp_len_log = None
+        if capacity:
+            self.hyp_log = torch.zeros(capacity, G, self.log_width, dtype=torch.int32, device=self.device)
+            self.hyp_len_log = torch.zeros(capacity, G, dtype=torch.int32, device=self.device)
+
+    def reset(self):
+        self.state.zero_()
+        if self.capacity:
+            self.hyp_log.zero_()
+            self.hyp_len_log.zero_()
+
+    def raw(self):
+        """The state as host arrays (one device-to-host copy)."""
+        st = L.EvalState.from_buffer_copy(self.state.cpu().numpy().tobytes())
+        return {"cursor": st.cursor, "steps": st.steps, "overflow": st.overflow, "first_flagged": st.first_flagged,
+                "totals": np.ctypeslib.as_array(st.totals).copy(), "flags": list(st.flags),
+                "loss_sum": np.ctypeslib.as_array(st.loss_sum).copy()}
+
+    def read(self):
+        """The pass's single host read: `results_from_state` of the state."""
+        return results_from_state(self.raw(), self.heads, self.loss_names, self.flag_names)
+
+    def hypotheses(self):
+        """Per clip, in arrival order: {logits_name: [class ids]} (needs a log: capacity > 0)."""
+        if not self.capacity:
+            raise RuntimeError("EvalState.hypotheses: no log attached (capacity = 0)")
+        n = min(self.raw()["cursor"], self.capacity)
+        packed = torch.cat([self.hyp_len_log[:n].unsqueeze(-1), self.hyp_log[:n]], dim=-1).cpu().numpy()
+        return [{logits_name(k): packed[r, g, 1:1 + packed[r, g, 0]].tolist() for g, k in enumerate(self.heads)}
+                for r in range(n)]
+
+
+def _references(src_input, B, device):
+    lab = torch.as_tensor(src_input["gloss_labels"])
+    if lab.dim() == 1:
+        lab = _heads._pad_concatenated(lab, src_input["gloss_lengths"], B)
+    if lab.dim() != 2 or lab.shape[0] != B:
+        raise ValueError(f"eval_step: gloss_labels must be (B, S) or 1-D concatenated, got {tuple(lab.shape)}")
+    if lab.shape[1] > WER_MAX_LEN:
+        raise ValueError(f"eval_step: references of {lab.shape[1]} tokens exceed the WER kernel's {WER_MAX_LEN}")
+    ref_len = torch.as_tensor(src_input["gloss_lengths"]).reshape(-1)
+    if ref_len.numel() != B:
+        raise ValueError(f"eval_step: gloss_lengths must have {B} entries, got {ref_len.numel()}")
+    return _dev_i32(lab, device), _dev_i32(ref_len, device)
+
+
+def accumulate(state, tokens, lengths, ref, ref_len, report):
+    """`sca_eval_accumulate`: tokens (G, B, Hmax) / lengths (G, B) scored against ref (B, Rmax) /
+    ref_len (B) (int32, device) and added to `state` with the step's `finite_report`.  Returns
+    the step's counts (G, B, 4) int32."""
+    G, B, Hmax = tokens.shape
+    if G != len(state.heads):
+        raise ValueError(f"accumulate: {G} heads decoded, the state holds {len(state.heads)}")
+    if ref.dim() != 2 or ref.shape[0] != B:
+        raise ValueError(f"accumulate: ref must be ({B}, Rmax), got {tuple(ref.shape)}")
+    if Hmax > WER_MAX_LEN or ref.shape[1] > WER_MAX_LEN:
+        raise ValueError(f"accumulate: rows of {Hmax} / {ref.shape[1]} tokens exceed the WER kernel's {WER_MAX_LEN}")
+    nflags, nloss = len(state.flag_names), len(state.loss_names)
+    if report.numel() != nflags + nloss + 1:
+        raise ValueError(f"accumulate: a report of {report.numel()} words does not fit the state's {nflags} flags "
+                         f"and {nloss} losses")
+    for t in (tokens, lengths, ref, ref_len, report):
+        if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous():
+            raise RuntimeError("accumulate: contiguous int32 ROCm tensors only.  There is no CPU fallback.")
+    counts = torch.empty(G, B, 4, dtype=torch.int32, device=tokens.device)
+    L.check(L.lib().sca_eval_accumulate(L.ptr(tokens), L.ptr(lengths), G, B, Hmax, L.ptr(ref), L.ptr(ref_len),
+                                        ref.shape[1], L.ptr(report), nflags, nloss, L.ptr(counts), L.ptr(state.state),
+                                        L.ptr(state.hyp_log), L.ptr(state.hyp_len_log), state.capacity,
+                                        state.log_width, L.stream_handle()), "sca_eval_accumulate")
+    return counts
+
+
+def eval_step(model, src_input, state, beam_size=5):
+    """One evaluation step of MSCA_Net, enqueued on the current stream without a host read:
+    forward under no_grad with the finite check deferred (a `model.check` of "off" is kept),
+    the grouped decode of `state.heads` with outputs["input_lengths"] (`beam_size=0`: greedy),
+    and `sca_eval_accumulate` against gloss_labels / gloss_lengths.  Returns the forward's
+    outputs plus `tokens` (G, B, T') / `lengths` (G, B) / `counts` (G, B, 4) of this step.
+
+    The model's `training` flag is left as it is: put the model in `eval()` first."""
+    with torch.no_grad():
+        check, model.check = model.check, ("off" if model.check == "off" else "defer")
+        try:
+            outputs = model(src_input)
+        finally:
+            model.check = check
+        if _students_of(outputs) != state.students:
+            raise ValueError("eval_step: the model's distillation terms differ from the state's")
+        logits = [outputs[k] for k in state.heads]
+        tokens, lengths, _ = ctc_decode_heads_device(logits, outputs["input_lengths"], beam_size)
+        ref, ref_len = _references(src_input, tokens.shape[1], tokens.device)
+        outputs["tokens"], outputs["lengths"] = tokens, lengths
+        outputs["counts"] = accumulate(state, tokens, lengths, ref, ref_len, outputs["finite_report"])
+    return outputs
+
+
+# ------------------------------------------------------------------------------- buckets
+def check_eval_buckets(cfg, frame_buckets, label_bucket):
+    """Constructor validation of BucketedEvalStep (host only): the sorted bucket tuple."""
+    frame_buckets = tuple(frame_buckets)
+    buckets = check_buckets(cfg, frame_buckets, len(frame_buckets))  # no optimizer: no capture slots to run out of
+    n_pool = n_pool_of(cfg)
+    for f in buckets:
+        if f >> n_pool > WER_MAX_LEN:
+            raise ValueError(f"BucketedEvalStep: bucket {f} has {f >> n_pool} pooled frames, more than the "
+                             f"{WER_MAX_LEN} tokens the WER matrix holds")
+    if label_bucket > WER_MAX_LEN:
+        raise ValueError(f"BucketedEvalStep: label_bucket {label_bucket} exceeds the {WER_MAX_LEN} tokens the WER "
+                         "matrix holds")
+    return buckets
+
+
+class BucketedEvalStep:
+    """`eval_step` for batches of varying length, `BucketedTrainStep`'s scheme without an
+    optimizer: `step(src_input)` pads the batch to the smallest of `frame_buckets` that holds it
+    and to `label_bucket` labels per clip (`pad_batch`, `valid_frames`), copies it into the
+    bucket's static device tensors and runs the bucket's step.  The first use of a bucket runs
+    eagerly on a side stream, the second captures the step into a hipGraph (a private pool per
+    bucket) and replays it, later uses replay.  A batch whose B differs from `batch_size` runs
+    the eager `eval_step` unpadded.  All buckets append to one `EvalState` (`.state`); with
+    `capacity` > 0 it logs the hypotheses, `log_width` being the largest bucket's pooled length.
+
+    Returns the step's outputs, the logits and `tokens` trimmed (views) to the batch's own
+    T >> n_pool frames; they are views of the bucket's static outputs, valid until the next
+    `step`.  The model must be in `eval()`; a bucket's pooled length and `label_bucket` may not
+    exceed 128 (the WER matrix)."""
+
+    def __init__(self, model, batch_size, frame_buckets, label_bucket, beam_size=5, heads=None, capacity=0):
+        self.frame_buckets = check_eval_buckets(model.cfg, frame_buckets, label_bucket)
+        if batch_size < 1 or label_bucket < 1:
+            raise ValueError("BucketedEvalStep: batch_size and label_bucket must be positive")
+        self.model, self.beam_size = model, int(beam_size)
+        self.batch_size, self.label_bucket = int(batch_size), int(label_bucket)
+        self.n_pool = n_pool_of(model.cfg)
+        self.state = EvalState(model, heads, capacity, self.frame_buckets[-1] >> self.n_pool)
+        self._buckets = {f: _Bucket(f) for f in self.frame_buckets}
+        self._stream = None
+        self.eager_fallbacks = 0
+
+    @property
+    def graphs_captured(self):
+        return sum(b.graph is not None for b in self._buckets.values())
+
+    def bucket_for(self, T):
+        return pick_bucket(self.frame_buckets, T)
+
+    def read(self):
+        return self.state.read()
+
+    def hypotheses(self):
+        return self.state.hypotheses()
+
+    def _fill(self, bucket, padded, device):
+        keys = ("keypoints", "mask", "valid_len_in", "gloss_labels", "gloss_lengths", "valid_frames")
+        if bucket.static is None:
+            bucket.static = {}
+            for k in keys:
+                t = torch.as_tensor(padded[k])
+                bucket.static[k] = torch.empty(t.shape, dtype=t.dtype, device=device)
+        for k in keys:
+            t = torch.as_tensor(padded[k])
+            if t.shape != bucket.static[k].shape or t.dtype != bucket.static[k].dtype:
+                raise ValueError(f"BucketedEvalStep: {k} changed from {tuple(bucket.static[k].shape)} "
+                                 f"{bucket.static[k].dtype} to {tuple(t.shape)} {t.dtype} between batches")
+            bucket.static[k].copy_(t, non_blocking=True)
+        extra = {k: v for k, v in padded.items() if k not in keys}
+        return {**extra, **bucket.static}
+
+    def _trim(self, outputs, T):
+        n = T >> self.n_pool
+        out = dict(outputs)
+        for k in _LOGITS:
+            if k in out:
+                out[k] = out[k][:, :n]
+        out["tokens"] = out["tokens"][:, :, :n]
+        return out
+
+    def step(self, src_input):
+        kp = src_input["keypoints"]
+        B, T = kp.shape[0], kp.shape[1]
+        if B != self.batch_size:
+            self.eager_fallbacks += 1
+            return self._trim(eval_step(self.model, src_input, self.state, self.beam_size), T)
+        bucket = self._buckets[self.bucket_for(T)]
+        src = self._fill(bucket, pad_batch(src_input, bucket.frames, self.label_bucket), self.state.device)
+        bucket.uses += 1
+        if bucket.graph is not None:
+            bucket.graph.replay()
+            return self._trim(bucket.outputs, T)
+        if bucket.uses == 1:  # warm-up: a real eager step, on a side stream as capture will be
+            if self._stream is None:
+                self._stream = torch.cuda.Stream(device=self.state.device)
+            self._stream.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(self._stream):
+                outputs = eval_step(self.model, src, self.state, self.beam_size)
+            torch.cuda.current_stream().wait_stream(self._stream)
+            return self._trim(outputs, T)
+        # second use: capture, then the replay is this batch's step
+        torch.cuda.synchronize()
+        bucket.pool = torch.cuda.graph_pool_handle()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, pool=bucket.pool):
+            outputs = eval_step(self.model, src, self.state, self.beam_size)
+        bucket.outputs = outputs
+        bucket.graph = graph
+        graph.replay()
+        return self._trim(bucket.outputs, T)

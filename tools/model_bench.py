@@ -28,6 +28,16 @@ synchronise; no report read in either) in alternated windows; ms/step as median 
 above the previous bucket against a hipGraph captured at exactly that T (alternated windows of
 `--steps` steps).  `--eager-only` times the eager pass alone and `--root DIR` imports the
 package from another checkout (the same eager measurement on an earlier commit).  One JSON line.
+
+--eval (with --mixed): an evaluation pass over the same stream, beam --beam (5), two ways:
+  loop       what a user can write without the evaluation step: per batch a no-grad eager forward
+             (check "defer"), decode_outputs' two halves per "gloss_logits" head (ctc_decode_device,
+             then one packed device-to-host copy of tokens, lengths and total_loss: the batch's one
+             host read) with wer_counts on the device between them
+  bucketed   BucketedEvalStep (buckets --buckets, every graph captured before), read() at the end
+Whole passes on the host clock, each ending in a device synchronise, alternated windows; ms per
+batch.  `--eager-only` times the loop alone; with `--root DIR` that is the same loop on another
+checkout's package (it uses nothing the parent commit lacks).
 """
 import argparse
 import json
@@ -219,6 +229,66 @@ def mixed(a, dev):
     print(json.dumps(res))
 
 
+def eval_loop(S, model, beam):
+    """One batch of the loop a user writes from the parts: returns what it read."""
+    def step(src):
+        with torch.no_grad():
+            out = model(src)
+        ref = src["gloss_labels"].to(torch.int32)
+        packed = [out["total_loss"].reshape(1).view(torch.int32)]
+        for k, v in out.items():
+            if "gloss_logits" not in k:
+                continue
+            tokens, lengths, _ = S.ctc_decode_device(v, out["input_lengths"], beam)
+            counts = S.wer_counts(ref, src["gloss_lengths"], tokens, lengths)
+            packed += [lengths, tokens.reshape(-1), counts.reshape(-1)]
+        return torch.cat(packed).cpu()  # the batch's one host read
+    return step
+
+
+def eval_mixed(a, dev):
+    import scattennet_amd as S
+    model, _, w, _ = build(a, dev)
+    model.check = "defer"
+    n_pool = (len(w["residual_blocks"]) + 1) // 2
+    batches = mixed_batches(a, w, dev, n_pool)
+    lengths = [T for _, T in batches]
+    loop = eval_loop(S, model, a.beam)
+    _pass(loop, batches)  # every shape once
+    res = {"workload": "MSCA_Net evaluation pass over a mixed-length stream (forward, beam decode of the "
+                       "gloss heads, WER counts)", "B": a.B, "max_len": a.T, "C": a.C, "S": a.S, "beam": a.beam,
+           "seed": a.seed, "batch_lengths": lengths}
+    if a.eager_only:
+        res["loop_ms_per_batch"] = _spread([_pass(loop, batches) for _ in range(a.windows)])
+        print(json.dumps(res))
+        return
+    buckets = tuple(int(b) for b in a.buckets.split(","))
+    bes = S.BucketedEvalStep(model, a.B, buckets, a.S, beam_size=a.beam)
+    g = torch.Generator().manual_seed(a.seed + 1)
+    for _ in range(2):  # warm-up pass, capture pass
+        _pass(bes.step, batches)
+    for f in buckets:  # a bucket the stream visits less than twice (or never) is captured here
+        while bes._buckets[f].graph is None:
+            bes.step(_batch(a, w, dev, g, [f] * a.B, n_pool)[0])
+    assert bes.graphs_captured == len(buckets)
+
+    def bucketed_pass():
+        bes.state.reset()
+        ms = _pass(bes.step, batches)
+        return ms, bes.read()  # the pass's one host read (after the timed window's synchronise)
+
+    ms = {"loop": [], "bucketed": []}
+    for _ in range(a.windows):  # alternated windows
+        ms["loop"].append(_pass(loop, batches))
+        t, results = bucketed_pass()
+        ms["bucketed"].append(t)
+    res.update({"buckets": list(buckets), "bucket_of_batch": [bes.bucket_for(T) for T in lengths],
+                "loop_ms_per_batch": _spread(ms["loop"]), "bucketed_ms_per_batch": _spread(ms["bucketed"]),
+                "bucketed_median_below_loop_range": statistics.median(ms["bucketed"]) < min(ms["loop"]),
+                "results": {k: round(v, 4) for k, v in results.items()}})
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=8)
@@ -230,6 +300,9 @@ def main():
     ap.add_argument("--scan-reps", type=int, default=50)
     ap.add_argument("--mixed", action="store_true", help="the mixed-length stream: eager against BucketedTrainStep")
     ap.add_argument("--eager-only", action="store_true", help="with --mixed: time the eager pass alone")
+    ap.add_argument("--eval", action="store_true", help="with --mixed: an evaluation pass, loop against "
+                                                        "BucketedEvalStep")
+    ap.add_argument("--beam", type=int, default=5)
     ap.add_argument("--batches", type=int, default=20)
     ap.add_argument("--buckets", default="64,128,192,256")
     ap.add_argument("--seed", type=int, default=0)
@@ -240,7 +313,7 @@ def main():
         raise SystemExit("model_bench needs a GPU: there is no CPU path to time")
     dev = torch.device("cuda:0")
     if a.mixed:
-        return mixed(a, dev)
+        return eval_mixed(a, dev) if a.eval else mixed(a, dev)
     model, src, w, t4 = build(a, dev)
     graphs = {k: capture(model, src, k, dev) for k in ("off", "defer")}
     ms = {k: [] for k in graphs}
