@@ -52,7 +52,9 @@
  *   sca_eval_accumulate    wer_single per (head, clip), the totals wer_list needs, the loss
  *                          meters' sums and the hypothesis log of evaluate_fn (opt.py:77-119),
  *                          kept in device memory across the steps of a pass
- *   sca_finite_scan        the isnan().any() / isinf().any() tests of MSCA_Net.forward
+ *   sca_ctc_align_heads    (no counterpart: the reference has no forced alignment) gloss spans
+ *   sca_eval_log_alignments  and confidences of given label sequences, and their log in a pass
+ *   sca_finite_scan       the isnan().any() / isinf().any() tests of MSCA_Net.forward
  *                          (model/__init__.py:130-235), all tensors in one launch
  *   sca_step_report        total_loss (model/__init__.py:207,237), the loss terms the
  *                          training loop logs (opt.py:39-42) and the device-side form of
@@ -644,6 +646,45 @@ int sca_ctc_beam_decode_heads(const sca_decode_heads* heads, int G, const int* i
                               int beam_width, int collapse_repeats, int* tokens, int* out_len, float* score,
                               void* ws, void* stream);
 
+/* ---- evaluation: CTC forced alignment (gloss spans and confidences) -----------------------
+ * The best single path of G heads' logits through given label sequences: for every (head g,
+ * clip b) the frames at which each label is emitted.  Logits as for the decoders (fp32
+ * (B, T, C) per head, by value in `heads`, blank = class 0); in_len (B) int32, clamped
+ * in-kernel to [0, T].  labels_per_head = 0: labels (B, S) int32 / lab_len (B) are shared by
+ * all heads (the references); labels_per_head = 1: labels (G, B, S) / lab_len (G, B) (each
+ * head's own hypotheses: the grouped decoders' tokens / out_len as they are).  lab_len is
+ * clamped to [0, S]; label values are clamped into [1, C) only to stay in bounds (the caller
+ * validates).  1 <= G <= SCA_EVAL_MAX_HEADS, B >= 1, any T >= 1, C <= SCA_CTC_MAX_C,
+ * 0 <= S <= SCA_CTC_MAX_S.
+ *
+ * Per (g, b), T_b / S_b the clamped lengths, lp = log_softmax(logits[b, t]) (no clamp):
+ * L = 2 S_b + 1 extended states, blank at the even states and label j at state 2 j + 1.
+ * Viterbi in log space: v_0[0] = lp_0[0], v_0[1] = lp_0[l_0], every other state -inf;
+ *   v_t[s] = lp_t[ext(s)] + max(v_{t-1}[s], v_{t-1}[s-1], v_{t-1}[s-2])
+ * the third term only for odd s >= 3 whose label differs from the label of state s - 2.
+ * Ties: the predecessor is s unless s - 1 is strictly greater, and s - 2 only if it is strictly
+ * greater than both.  The path ends in state L - 1 only if v[L-1] > v[L-2], otherwise in L - 2
+ * (L = 1: state 0).  The clip is infeasible when that value is -inf: T_b < S_b + the number of
+ * adjacent equal labels, or T_b = 0 with S_b > 0.
+ *
+ * Outputs, every element written by every call:
+ *   frame_label (G, B, T) int32  the index j of the label emitted at frame t; -1 at blank
+ *                                frames and at t >= T_b
+ *   spans (G, B, S, 2) int32     [start, end) frames of label j; (0, 0) for j >= S_b
+ *   conf (G, B, S) fp32          the mean of exp(lp_t[l_j]) over the span's frames; 0 for j >= S_b
+ *   score (G, B) fp32            the path's log-probability; 0 for T_b = S_b = 0
+ * An infeasible clip has score = -inf, frame_label = -1 and spans and conf zero.
+ *
+ * ws: sca_ctc_align_workspace_bytes(G, B, T, S) bytes (0 for unsupported sizes), 8-byte
+ * aligned: the row statistics and two bits of back-pointer per (frame, state).  Two launches
+ * whatever G and B are: the row statistics of all G B T rows, then one workgroup per
+ * (head, clip); no allocation, copy or synchronisation (capturable).  Head g's results are
+ * bitwise those of a G = 1 call on heads->logits[g] with its labels.                        */
+long sca_ctc_align_workspace_bytes(int G, int B, int T, int S);
+int sca_ctc_align_heads(const sca_decode_heads* heads, int G, const int* in_len, const int* labels,
+                        const int* lab_len, int labels_per_head, int B, int T, int C, int S, int* frame_label,
+                        int* spans, float* conf, float* score, void* ws, void* stream);
+
 /* SeqKD over R rows of C logits (student, teacher): columns [start, C) only (use_blank=False
  * -> start 1), temperature temp:
  *   loss = clamp(weight * temp^2 * (1/R) * sum_rows KL(softmax(q/temp) || log_softmax(s/temp)),
@@ -830,6 +871,19 @@ int sca_eval_accumulate(const int* tokens, const int* hyp_len, int G, int B, int
                         const int* ref_len, int Rmax, const void* report, int nflags, int nloss, int* counts,
                         sca_eval_state* state, int* hyp_log, int* hyp_len_log, int capacity, int log_width,
                         void* stream);
+
+/* sca_eval_log_alignments: one step's alignments (sca_ctc_align_heads: spans (G, B, S, 2),
+ * conf (G, B, S), score (G, B)) appended to a pass's alignment log, one launch.  It reads
+ * state->cursor on the device and writes clip b to row r = cursor + b of
+ * span_log (capacity, G, log_width, 2) int32, conf_log (capacity, G, log_width) fp32 (columns
+ * [S, log_width) zero) and score_log (capacity, G) fp32.  It only READS the state: enqueue it
+ * BEFORE the step's sca_eval_accumulate, which advances the cursor, so that a replayed graph
+ * appends where the hypothesis log does.  Rows r >= capacity and columns >= log_width are
+ * dropped; sca_eval_accumulate raises the overflow bits for the same clips.
+ * 1 <= G <= 8, B >= 1, S >= 0, capacity >= 1, log_width >= 1.                               */
+int sca_eval_log_alignments(const int* spans, const float* conf, const float* score, int G, int B, int S,
+                            const sca_eval_state* state, int* span_log, float* conf_log, float* score_log,
+                            int capacity, int log_width, void* stream);
 
 const char* sca_last_error(void);
 int sca_version(void);

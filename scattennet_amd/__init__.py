@@ -17,6 +17,8 @@ from .alignment import AlignmentModule  # noqa: F401
 from .heads import RecognitionHead, SeqKD, compute_loss, distillation_loss  # noqa: F401
 from .decode import (ctc_decode, ctc_decode_device, ctc_greedy_decode_device, decode_outputs, wer_counts,  # noqa: F401
                      wer_from_counts)
+from .align import (align_outputs, alignment_lists, ctc_align, ctc_align_device,  # noqa: F401
+                    ctc_align_heads_device)
 from .optim import FusedAdam, WarmupCosineAnnealingScheduler, build_optimizer, clip_grad_norm_  # noqa: F401
 from .model import MSCA_Net, finite_flags, first_error  # noqa: F401
 from .train import read_report, train_step  # noqa: F401

@@ -219,6 +219,9 @@ EXPORTS = {
     "sca_ctc_beam_decode_heads": ([c_void_p, c_int, c_void_p] + [c_int] * 5 + [c_void_p] * 5, c_int),
     "sca_eval_accumulate": ([c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
                              c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p], c_int),
+    "sca_ctc_align_workspace_bytes": ([c_int] * 4, c_long),
+    "sca_ctc_align_heads": ([c_void_p, c_int, c_void_p, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 6, c_int),
+    "sca_eval_log_alignments": ([c_void_p] * 3 + [c_int] * 3 + [c_void_p] * 4 + [c_int, c_int, c_void_p], c_int),
     "sca_optim_blocks": ([c_int, c_int], c_int),
     "sca_optim_grad_sqnorm": ([c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
     "sca_optim_adam_step": ([c_void_p, c_void_p, c_int, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p],

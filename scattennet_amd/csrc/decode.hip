@@ -584,6 +584,15 @@ DecHeads dec_one_head(const float* logits) {
 
 }  // namespace
 
+// the grouped row pass for align.hip (which validates heads and G): rowstat (G, rows_per_head, 2)
+__attribute__((visibility("hidden"))) void sca_ctc_rowstat_heads_launch(const sca_decode_heads* heads, int G,
+                                                                        float* rowstat, long rows_per_head, int C,
+                                                                        hipStream_t st) {
+  const long rows = (long)G * rows_per_head;
+  hipLaunchKernelGGL(ctc_rowstat_heads_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st,
+                     dec_heads_of(heads, G), rowstat, rows, rows_per_head, C);
+}
+
 extern "C" long sca_ctc_decode_workspace_bytes(int B, int T, int C, int W) {
   if (!dec_dims_ok(B, T, C, W)) return 0;
   const long BT = (long)B * T;

@@ -8,7 +8,8 @@ read until the pass is over.
 * `EvalState` — the pass's device state (`sca_eval_state`, include/scatten.h): per-head WER
   totals, float64 loss sums, the OR of the finite guard's flag words, and an optional log of
   every hypothesis.  `read()` is the single host read and returns the dict `evaluate_fn`
-  returns; `hypotheses()` returns the logged token ids.
+  returns; `hypotheses()` returns the logged token ids and, with `align=True`, `alignments()`
+  each hypothesis's gloss spans and confidences (align.py).
 * `eval_step(model, src_input, state, beam_size=5)` — forward (finite check deferred), grouped
   decode, `sca_eval_accumulate`.  No host read; capturable for a fixed (B, T, S) by the rules
   of `train.py`.  It does NOT touch the model's `training` flag: call `model.eval()` first, as
@@ -30,6 +31,7 @@ from torch import nn
 from . import _lib as L
 from . import heads as _heads
 from .bucketed import _Bucket, check_buckets, pad_batch, pick_bucket
+from .align import alignment_lists, ctc_align_heads_device
 from .decode import MAX_BEAM, WER_MAX_LEN, _check_device, _check_lengths, _check_logits, wer_from_counts
 from .encoder import n_pool_of
 from .heads import _dev_i32
@@ -161,9 +163,12 @@ class EvalState:
     the keys evaluate_fn decodes (`alignment_gloss_logits`, `fuse_coord_gloss_logits`).
     `capacity` > 0 attaches a log of `capacity` clips: `hyp_log` (capacity, G, log_width) int32
     zero-padded and `hyp_len_log` (capacity, G); `log_width` is then required (the longest
-    hypothesis: the pooled frame count).  `reset()` clears everything on the current stream."""
+    hypothesis: the pooled frame count).  `align=True` (needs a log) makes `eval_step` force-align
+    every head's hypothesis and attaches `span_log` (capacity, G, log_width, 2) int32, `conf_log`
+    (capacity, G, log_width) and `score_log` (capacity, G) fp32, read by `alignments()`.
+    `reset()` clears everything on the current stream."""
 
-    def __init__(self, model, heads=None, capacity=0, log_width=None):
+    def __init__(self, model, heads=None, capacity=0, log_width=None, align=False):
         keys = default_heads() if heads is None else tuple(heads)
         if not 1 <= len(keys) <= MAX_HEADS or len(set(keys)) != len(keys):
             raise ValueError(f"EvalState: heads must be 1..{MAX_HEADS} distinct keys, got {keys!r}")
@@ -175,7 +180,10 @@ class EvalState:
             raise ValueError("EvalState: capacity must not be negative")
         if capacity and (log_width is None or not 1 <= int(log_width) <= WER_MAX_LEN):
             raise ValueError(f"EvalState: a log needs log_width in [1, {WER_MAX_LEN}], got {log_width!r}")
+        if align and not capacity:
+            raise ValueError("EvalState: align=True needs a log (capacity > 0) to keep the alignments in")
         self.heads = keys
+        self.align = bool(align)
         self.students = list(model._students())
         self.flag_names = flag_names(self.students)
         self.loss_names = loss_names(self.students)
@@ -187,12 +195,21 @@ class EvalState:
         if capacity:
             self.hyp_log = torch.zeros(capacity, G, self.log_width, dtype=torch.int32, device=self.device)
             self.hyp_len_log = torch.zeros(capacity, G, dtype=torch.int32, device=self.device)
+        self.span_log = self.conf_log = self.score_log = None
+        if self.align:
+            self.span_log = torch.zeros(capacity, G, self.log_width, 2, dtype=torch.int32, device=self.device)
+            self.conf_log = torch.zeros(capacity, G, self.log_width, dtype=torch.float32, device=self.device)
+            self.score_log = torch.zeros(capacity, G, dtype=torch.float32, device=self.device)
 
     def reset(self):
         self.state.zero_()
         if self.capacity:
             self.hyp_log.zero_()
             self.hyp_len_log.zero_()
+        if self.align:
+            self.span_log.zero_()
+            self.conf_log.zero_()
+            self.score_log.zero_()
 
     def raw(self):
         """The state as host arrays (one device-to-host copy)."""
@@ -213,6 +230,29 @@ class EvalState:
         packed = torch.cat([self.hyp_len_log[:n].unsqueeze(-1), self.hyp_log[:n]], dim=-1).cpu().numpy()
         return [{logits_name(k): packed[r, g, 1:1 + packed[r, g, 0]].tolist() for g, k in enumerate(self.heads)}
                 for r in range(n)]
+
+    def alignments(self, frame_scale=1):
+        """Per clip, in arrival order: {logits_name: [(class id, start, end, confidence), ...]}, the
+        forced alignment of each head's own hypothesis (`align=True`); spans in logit frames times
+        `frame_scale`.  One device-to-host copy, like `hypotheses()`."""
+        if not self.align:
+            raise RuntimeError("EvalState.alignments: the state was built without align=True")
+        n = min(self.raw()["cursor"], self.capacity)
+        G, W = len(self.heads), self.log_width
+        packed = torch.cat([self.hyp_len_log[:n].unsqueeze(-1).double(), self.hyp_log[:n].double(),
+                            self.span_log[:n].reshape(n, G, 2 * W).double(), self.conf_log[:n].double(),
+                            self.score_log[:n].unsqueeze(-1).double()], dim=-1).cpu().numpy()
+        out = []
+        for r in range(n):
+            clip = {}
+            for g, k in enumerate(self.heads):
+                row = packed[r, g]
+                lists = alignment_lists(row[None, 1:1 + W].astype(np.int64), row[None, 0].astype(np.int64),
+                                        row[None, 1 + W:1 + 3 * W].reshape(1, W, 2).astype(np.int64),
+                                        row[None, 1 + 3 * W:1 + 4 * W], row[None, 1 + 4 * W], frame_scale)
+                clip[logits_name(k)] = lists[0]
+            out.append(clip)
+        return out
 
 
 def _references(src_input, B, device):
@@ -255,12 +295,35 @@ def accumulate(state, tokens, lengths, ref, ref_len, report):
     return counts
 
 
+def log_alignments(state, spans, conf, scores):
+    """`sca_eval_log_alignments`: one step's alignments (G, B, S, 2) / (G, B, S) / (G, B) appended
+    to the state's alignment log at the state's cursor.  Call it BEFORE `accumulate`, which
+    advances the cursor."""
+    G, B, S = conf.shape
+    if G != len(state.heads):
+        raise ValueError(f"log_alignments: {G} heads aligned, the state holds {len(state.heads)}")
+    if not (spans.is_cuda and spans.dtype == torch.int32 and spans.is_contiguous() and conf.is_cuda and
+            conf.dtype == torch.float32 and conf.is_contiguous() and scores.is_cuda and
+            scores.dtype == torch.float32 and scores.is_contiguous()):
+        raise RuntimeError("log_alignments: contiguous int32 spans and fp32 conf / scores on a ROCm device only.  "
+                           "There is no CPU fallback.")
+    L.check(L.lib().sca_eval_log_alignments(L.ptr(spans), L.ptr(conf), L.ptr(scores), G, B, S, L.ptr(state.state),
+                                            L.ptr(state.span_log), L.ptr(state.conf_log), L.ptr(state.score_log),
+                                            state.capacity, state.log_width, L.stream_handle()),
+            "sca_eval_log_alignments")
+
+
 def eval_step(model, src_input, state, beam_size=5):
     """One evaluation step of MSCA_Net, enqueued on the current stream without a host read:
     forward under no_grad with the finite check deferred (a `model.check` of "off" is kept),
     the grouped decode of `state.heads` with outputs["input_lengths"] (`beam_size=0`: greedy),
     and `sca_eval_accumulate` against gloss_labels / gloss_lengths.  Returns the forward's
     outputs plus `tokens` (G, B, T') / `lengths` (G, B) / `counts` (G, B, 4) of this step.
+
+    With `state.align`, every head's own hypothesis is force-aligned to its logits after the
+    decode (`sca_ctc_align_heads` with one label set per head) and logged before the
+    accumulation: the outputs also hold `spans` (G, B, T', 2), `conf` (G, B, T') and
+    `align_scores` (G, B).
 
     The model's `training` flag is left as it is: put the model in `eval()` first."""
     with torch.no_grad():
@@ -275,6 +338,11 @@ def eval_step(model, src_input, state, beam_size=5):
         tokens, lengths, _ = ctc_decode_heads_device(logits, outputs["input_lengths"], beam_size)
         ref, ref_len = _references(src_input, tokens.shape[1], tokens.device)
         outputs["tokens"], outputs["lengths"] = tokens, lengths
+        if state.align:
+            res = ctc_align_heads_device(logits, outputs["input_lengths"], tokens, lengths)
+            spans, conf, scores = res.spans, res.conf.float(), res.scores.float()
+            log_alignments(state, spans, conf, scores)
+            outputs["spans"], outputs["conf"], outputs["align_scores"] = spans, conf, scores
         outputs["counts"] = accumulate(state, tokens, lengths, ref, ref_len, outputs["finite_report"])
     return outputs
 
@@ -303,21 +371,24 @@ class BucketedEvalStep:
     eagerly on a side stream, the second captures the step into a hipGraph (a private pool per
     bucket) and replays it, later uses replay.  A batch whose B differs from `batch_size` runs
     the eager `eval_step` unpadded.  All buckets append to one `EvalState` (`.state`); with
-    `capacity` > 0 it logs the hypotheses, `log_width` being the largest bucket's pooled length.
+    `capacity` > 0 it logs the hypotheses, `log_width` being the largest bucket's pooled length;
+    `align=True` adds the forced alignment of every hypothesis (`alignments()`): a span does not
+    depend on the bucket, because the heads' `input_lengths` are the batch's own.
 
-    Returns the step's outputs, the logits and `tokens` trimmed (views) to the batch's own
+    Returns the step's outputs, the logits, `tokens` (and `spans`, `conf`) trimmed (views) to the batch's own
     T >> n_pool frames; they are views of the bucket's static outputs, valid until the next
     `step`.  The model must be in `eval()`; a bucket's pooled length and `label_bucket` may not
     exceed 128 (the WER matrix)."""
 
-    def __init__(self, model, batch_size, frame_buckets, label_bucket, beam_size=5, heads=None, capacity=0):
+    def __init__(self, model, batch_size, frame_buckets, label_bucket, beam_size=5, heads=None, capacity=0,
+                 align=False):
         self.frame_buckets = check_eval_buckets(model.cfg, frame_buckets, label_bucket)
         if batch_size < 1 or label_bucket < 1:
             raise ValueError("BucketedEvalStep: batch_size and label_bucket must be positive")
         self.model, self.beam_size = model, int(beam_size)
         self.batch_size, self.label_bucket = int(batch_size), int(label_bucket)
         self.n_pool = n_pool_of(model.cfg)
-        self.state = EvalState(model, heads, capacity, self.frame_buckets[-1] >> self.n_pool)
+        self.state = EvalState(model, heads, capacity, self.frame_buckets[-1] >> self.n_pool, align)
         self._buckets = {f: _Bucket(f) for f in self.frame_buckets}
         self._stream = None
         self.eager_fallbacks = 0
@@ -334,6 +405,9 @@ class BucketedEvalStep:
 
     def hypotheses(self):
         return self.state.hypotheses()
+
+    def alignments(self, frame_scale=1):
+        return self.state.alignments(frame_scale)
 
     def _fill(self, bucket, padded, device):
         keys = ("keypoints", "mask", "valid_len_in", "gloss_labels", "gloss_lengths", "valid_frames")
@@ -358,6 +432,8 @@ class BucketedEvalStep:
             if k in out:
                 out[k] = out[k][:, :n]
         out["tokens"] = out["tokens"][:, :, :n]
+        if "spans" in out:
+            out["spans"], out["conf"] = out["spans"][:, :, :n], out["conf"][:, :, :n]
         return out
 
     def step(self, src_input):

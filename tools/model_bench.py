@@ -38,6 +38,10 @@ package from another checkout (the same eager measurement on an earlier commit).
 Whole passes on the host clock, each ending in a device synchronise, alternated windows; ms per
 batch.  `--eager-only` times the loop alone; with `--root DIR` that is the same loop on another
 checkout's package (it uses nothing the parent commit lacks).
+
+--align (with --mixed --eval): two BucketedEvalStep over the same stream, both with a hypothesis
+log of the whole pass, one with align=True (forced alignment of every head's hypotheses, logged);
+whole passes in alternated windows, ms per batch and the per-window difference.
 """
 import argparse
 import json
@@ -289,6 +293,47 @@ def eval_mixed(a, dev):
     print(json.dumps(res))
 
 
+def eval_align(a, dev):
+    """--mixed --eval --align: the bucketed evaluation pass with and without the forced alignment
+    of every hypothesis, both with a hypothesis log of the whole pass, in alternated windows."""
+    import scattennet_amd as S
+    model, _, w, _ = build(a, dev)
+    model.check = "defer"
+    n_pool = (len(w["residual_blocks"]) + 1) // 2
+    batches = mixed_batches(a, w, dev, n_pool)
+    buckets = tuple(int(b) for b in a.buckets.split(","))
+    capacity = a.batches * a.B
+    steps = {"plain": S.BucketedEvalStep(model, a.B, buckets, a.S, beam_size=a.beam, capacity=capacity),
+             "align": S.BucketedEvalStep(model, a.B, buckets, a.S, beam_size=a.beam, capacity=capacity, align=True)}
+    g = torch.Generator().manual_seed(a.seed + 1)
+    for bes in steps.values():
+        for _ in range(2):  # warm-up pass, capture pass
+            bes.state.reset()
+            _pass(bes.step, batches)
+        for f in buckets:  # a bucket the stream visits less than twice (or never) is captured here
+            while bes._buckets[f].graph is None:
+                bes.state.reset()
+                bes.step(_batch(a, w, dev, g, [f] * a.B, n_pool)[0])
+        assert bes.graphs_captured == len(buckets)
+    ms, results = {k: [] for k in steps}, {}
+    for _ in range(a.windows):  # alternated windows
+        for k, bes in steps.items():
+            bes.state.reset()
+            ms[k].append(_pass(bes.step, batches))
+            results[k] = bes.read()  # the pass's one host read (after the timed window's synchronise)
+    same = results["plain"] == results["align"] and steps["plain"].hypotheses() == steps["align"].hypotheses()
+    rows = steps["align"].alignments(frame_scale=1 << n_pool)
+    diff = [x - y for x, y in zip(ms["align"], ms["plain"])]
+    res = {"workload": "MSCA_Net bucketed evaluation pass over a mixed-length stream, with and without the forced "
+                       "alignment of every hypothesis (both log the hypotheses)", "B": a.B, "max_len": a.T, "C": a.C,
+           "S": a.S, "beam": a.beam, "seed": a.seed, "buckets": list(buckets),
+           "batch_lengths": [T for _, T in batches], "plain_ms_per_batch": _spread(ms["plain"]),
+           "align_ms_per_batch": _spread(ms["align"]), "align_minus_plain_ms_per_batch": _spread(diff),
+           "same_results_and_hypotheses": same, "clips_aligned": len(rows), "infeasible": sum(v is None for r in rows for v in r.values()),
+           "results": {k: round(v, 4) for k, v in results["align"].items()}}
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=8)
@@ -302,6 +347,8 @@ def main():
     ap.add_argument("--eager-only", action="store_true", help="with --mixed: time the eager pass alone")
     ap.add_argument("--eval", action="store_true", help="with --mixed: an evaluation pass, loop against "
                                                         "BucketedEvalStep")
+    ap.add_argument("--align", action="store_true", help="with --mixed --eval: the bucketed pass with and without "
+                                                         "the forced alignment of every hypothesis")
     ap.add_argument("--beam", type=int, default=5)
     ap.add_argument("--batches", type=int, default=20)
     ap.add_argument("--buckets", default="64,128,192,256")
@@ -313,6 +360,8 @@ def main():
         raise SystemExit("model_bench needs a GPU: there is no CPU path to time")
     dev = torch.device("cuda:0")
     if a.mixed:
+        if a.eval and a.align:
+            return eval_align(a, dev)
         return eval_mixed(a, dev) if a.eval else mixed(a, dev)
     model, src, w, t4 = build(a, dev)
     graphs = {k: capture(model, src, k, dev) for k in ("off", "defer")}
