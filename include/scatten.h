@@ -54,6 +54,8 @@
  *                          kept in device memory across the steps of a pass
  *   sca_ctc_align_heads    (no counterpart: the reference has no forced alignment) gloss spans
  *   sca_eval_log_alignments  and confidences of given label sequences, and their log in a pass
+ *   sca_ensemble_log_probs (no counterpart) the weighted mean of the heads' posteriors as
+ *                          log-probabilities, decoded as one more head
  *   sca_finite_scan       the isnan().any() / isinf().any() tests of MSCA_Net.forward
  *                          (model/__init__.py:130-235), all tensors in one launch
  *   sca_step_report        total_loss (model/__init__.py:207,237), the loss terms the
@@ -684,6 +686,38 @@ long sca_ctc_align_workspace_bytes(int G, int B, int T, int S);
 int sca_ctc_align_heads(const sca_decode_heads* heads, int G, const int* in_len, const int* labels,
                         const int* lab_len, int labels_per_head, int B, int T, int C, int S, int* frame_label,
                         int* spans, float* conf, float* score, void* ws, void* stream);
+
+/* ---- evaluation: ensemble of the heads' posteriors -----------------------------------------
+ * out (B, T, C) fp32 = the normalised log-probabilities of the weighted mean of G heads'
+ * posteriors, 1 <= G <= SCA_EVAL_MAX_HEADS: the tensor the multi-stream recognisers decode
+ * next to the single heads.  Logits as for the decoders: fp32 (B, T, C) per head, contiguous,
+ * the G device pointers by value in `heads`; the G weights by value in `weights` (finite,
+ * positive; entries [G, 8) are ignored), normalised here in double: W_g = w_g / sum w.  No
+ * device table, nothing to upload: capturable.  Any C >= 1 and any B T >= 1; `out` is none of
+ * the inputs.  Every element of `out` is written by every call.
+ *
+ * Per row (b, t), lp_g[c] = x_g[c] - logsumexp_c x_g (the decoders' row pass: max, then the sum
+ * of exp(x - max)):
+ *   mode 0 ("prob"), the arithmetic mean of the posteriors:
+ *     out[c] = log sum_g W_g exp(lp_g[c]), computed as M + log sum_g exp(a_g - M) with
+ *     a_g = lp_g[c] + log W_g and M = max_g a_g: logits at the heads' clamp (+-50) neither
+ *     overflow nor collapse to -inf.
+ *   mode 1 ("logprob"), the log-linear (geometric) mean, renormalised:
+ *     u[c] = sum_g W_g lp_g[c], summed for g = 0 .. G - 1 in this order;
+ *     out[c] = u[c] - logsumexp_c u.
+ * Both modes give normalised log-probabilities, and with G = 1 both give the row's log_softmax.
+ * Specified for finite logits (what RecognitionHead produces).
+ *
+ * One launch whatever G is: one wave per row, four rows per workgroup; 16-byte loads and stores
+ * where every head's row and the output row start on a 16-byte boundary and C % 4 == 0, scalar
+ * ones otherwise.  No atomics and a fixed order of every sum: a row's result depends on
+ * nothing but the row (not on B, T or the rows beside it), and a replayed capture is bitwise
+ * the eager call.                                                                          */
+typedef struct {
+  float w[SCA_EVAL_MAX_HEADS]; /* entries [G, 8) are ignored */
+} sca_ensemble_weights;
+int sca_ensemble_log_probs(const sca_decode_heads* heads, int G, const sca_ensemble_weights* weights, int mode,
+                           int B, int T, int C, float* out, void* stream);
 
 /* SeqKD over R rows of C logits (student, teacher): columns [start, C) only (use_blank=False
  * -> start 1), temperature temp:

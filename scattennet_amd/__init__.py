@@ -23,7 +23,9 @@ from .optim import FusedAdam, WarmupCosineAnnealingScheduler, build_optimizer, c
 from .model import MSCA_Net, finite_flags, first_error  # noqa: F401
 from .train import read_report, train_step  # noqa: F401
 from .bucketed import BucketedTrainStep, pad_batch  # noqa: F401
+from .ensemble import EnsembleSpec, ensemble_log_probs  # noqa: F401
 from .evaluate import BucketedEvalStep, EvalState, ctc_decode_heads_device, eval_step  # noqa: F401
+from .recognize import BucketedRecognizer, Recognition, recognize_step  # noqa: F401
 from . import library  # noqa: F401  (torch.ops.scatten.*)
 from .utils import KeyPaddingMask, create_attention_mask, create_causal_attention_mask, key_padding_mask  # noqa: F401
 

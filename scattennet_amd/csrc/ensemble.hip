@@ -1,0 +1,210 @@
+// Ensemble of the recognition heads' posteriors (include/scatten.h, sca_ensemble_log_probs):
+// out (B, T, C) = the normalised log-probabilities of the weighted arithmetic ("prob") or
+// log-linear ("logprob") mean of G heads' softmax rows.  The multi-stream recognisers decode
+// this averaged posterior next to the single heads; in torch it is a log_softmax per head, a
+// stack and a logsumexp: G + 2 tensors of (B, T, C) and as many launches.  Here it is one
+// launch whatever G is, G reads and one write.
+//
+// One wave per (b, t) row, four rows per 256-thread workgroup, as the decoders' row pass
+// (decode.hip, ctc_rowstat_heads_kernel), and that pass's arithmetic for the row statistics
+// (max, then the sum of exp(x - max)).  A row is a few KB, so the second and third reads of it
+// come from L2 / L1.  Lanes take 16 bytes each where every head's row and the output row start
+// on a 16-byte boundary and C is a multiple of 4; any other row takes the scalar path.
+// No atomics, no LDS; every sum runs in a fixed order and a row's result depends on nothing
+// but the row, so a replayed capture is bitwise the eager call.
+#include "common.h"
+#include "../../include/scatten.h"
+
+extern "C" void sca_set_error(const char* msg);
+
+namespace {
+
+constexpr float NEG_INF = -__builtin_huge_valf();
+constexpr int G_MAX = SCA_EVAL_MAX_HEADS;
+
+// The G row sources and their weights, by value in the kernel arguments (scalar registers).
+// w[g] = w_g / sum w; lw[g] = log of it ("prob" adds it to the head's log-probabilities).
+struct EnsHeads {
+  const float* x[G_MAX];
+  float w[G_MAX];
+  float lw[G_MAX];
+};
+
+template <int V>
+struct Pack {
+  float v[V];
+};
+
+template <int V>
+__device__ __forceinline__ Pack<V> ldv(const float* p) {
+  Pack<V> r;
+  if constexpr (V == 4) {
+    const f32x4 t = ld4(p);
+    r.v[0] = t[0]; r.v[1] = t[1]; r.v[2] = t[2]; r.v[3] = t[3];
+  } else {
+    r.v[0] = *p;
+  }
+  return r;
+}
+
+template <int V>
+__device__ __forceinline__ void stv(float* p, const Pack<V>& r) {
+  if constexpr (V == 4) {
+    f32x4 t;
+    t[0] = r.v[0]; t[1] = r.v[1]; t[2] = r.v[2]; t[3] = r.v[3];
+    st4(p, t);
+  } else {
+    *p = r.v[0];
+  }
+}
+
+// One row by one wave; lane l owns the elements [V (l + 64 k), V (l + 64 k) + V) in every pass.
+// V = 4 only when C % 4 == 0, so a pack never crosses the end of the row.
+template <int V>
+__device__ __forceinline__ void ensemble_row(const EnsHeads& h, int G, int mode, long off, float* __restrict__ outr,
+                                             int C, int lane) {
+  // row statistics of every member: m = max, ls = log sum exp(x - m)
+  float m[G_MAX], ls[G_MAX];
+#pragma unroll
+  for (int g = 0; g < G_MAX; ++g) {
+    m[g] = 0.0f;
+    ls[g] = 0.0f;
+    if (g < G) {
+      const float* xr = h.x[g] + off;
+      float mx = NEG_INF;
+      for (int c = lane * V; c < C; c += 64 * V) {
+        const Pack<V> x = ldv<V>(xr + c);
+#pragma unroll
+        for (int i = 0; i < V; ++i) mx = fmaxf(mx, x.v[i]);
+      }
+      mx = wave_max(mx);
+      float s = 0.0f;
+      for (int c = lane * V; c < C; c += 64 * V) {
+        const Pack<V> x = ldv<V>(xr + c);
+#pragma unroll
+        for (int i = 0; i < V; ++i) s += __expf(x.v[i] - mx);
+      }
+      s = wave_sum(s);
+      m[g] = mx;
+      ls[g] = __logf(s);
+    }
+  }
+
+  if (mode == 0) {
+    // out[c] = M + log sum_g exp(a_g - M), a_g = lp_g[c] + log w_g, M = max_g a_g: the largest
+    // term of the sum is exp(0) = 1, so nothing overflows and the sum never reaches 0
+    for (int c = lane * V; c < C; c += 64 * V) {
+      float a[G_MAX][V];
+      float M[V];
+#pragma unroll
+      for (int i = 0; i < V; ++i) M[i] = NEG_INF;
+#pragma unroll
+      for (int g = 0; g < G_MAX; ++g) {
+        if (g < G) {
+          const Pack<V> x = ldv<V>(h.x[g] + off + c);
+#pragma unroll
+          for (int i = 0; i < V; ++i) {
+            a[g][i] = ((x.v[i] - m[g]) - ls[g]) + h.lw[g];
+            M[i] = fmaxf(M[i], a[g][i]);
+          }
+        }
+      }
+      Pack<V> o;
+#pragma unroll
+      for (int i = 0; i < V; ++i) {
+        float s = 0.0f;
+#pragma unroll
+        for (int g = 0; g < G_MAX; ++g)
+          if (g < G) s += __expf(a[g][i] - M[i]);
+        o.v[i] = M[i] + __logf(s);
+      }
+      stv<V>(outr + c, o);
+    }
+    return;
+  }
+
+  // mode 1: u[c] = sum_g w_g lp_g[c] (g ascending), out = u - logsumexp_c u.  u is kept in the
+  // output row between the passes: a lane reads back only what it wrote itself.
+  float um = NEG_INF;
+  for (int c = lane * V; c < C; c += 64 * V) {
+    Pack<V> u;
+#pragma unroll
+    for (int i = 0; i < V; ++i) u.v[i] = 0.0f;
+#pragma unroll
+    for (int g = 0; g < G_MAX; ++g) {
+      if (g < G) {
+        const Pack<V> x = ldv<V>(h.x[g] + off + c);
+#pragma unroll
+        for (int i = 0; i < V; ++i) u.v[i] = fmaf(h.w[g], (x.v[i] - m[g]) - ls[g], u.v[i]);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < V; ++i) um = fmaxf(um, u.v[i]);
+    stv<V>(outr + c, u);
+  }
+  um = wave_max(um);
+  float s = 0.0f;
+  for (int c = lane * V; c < C; c += 64 * V) {
+    const Pack<V> u = ldv<V>(outr + c);
+#pragma unroll
+    for (int i = 0; i < V; ++i) s += __expf(u.v[i] - um);
+  }
+  s = wave_sum(s);
+  const float lse = __logf(s);
+  for (int c = lane * V; c < C; c += 64 * V) {
+    Pack<V> u = ldv<V>(outr + c);
+#pragma unroll
+    for (int i = 0; i < V; ++i) u.v[i] = (u.v[i] - um) - lse;
+    stv<V>(outr + c, u);
+  }
+}
+
+__global__ __launch_bounds__(256) void ensemble_log_probs_kernel(EnsHeads h, int G, int mode, float* out, long rows,
+                                                                 int C) {
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= rows) return;  // no barrier below: a wave without a row leaves
+  const long off = row * C;
+  float* outr = out + off;
+  // 16-byte packs only where every member's row and the output row start on a 16-byte boundary
+  uintptr_t bits = reinterpret_cast<uintptr_t>(outr) | (uintptr_t)(C & 3);
+#pragma unroll
+  for (int g = 0; g < G_MAX; ++g)
+    if (g < G) bits |= reinterpret_cast<uintptr_t>(h.x[g] + off);
+  if ((bits & 15) == 0)
+    ensemble_row<4>(h, G, mode, off, outr, C, lane);
+  else
+    ensemble_row<1>(h, G, mode, off, outr, C, lane);
+}
+
+}  // namespace
+
+extern "C" int sca_ensemble_log_probs(const sca_decode_heads* heads, int G, const sca_ensemble_weights* weights,
+                                      int mode, int B, int T, int C, float* out, void* stream) {
+  const long rows = (long)B * T;
+  bool ok = heads && weights && out && G >= 1 && G <= SCA_EVAL_MAX_HEADS && (mode == 0 || mode == 1) && B >= 1 &&
+            T >= 1 && C >= 1 && (rows + 3) / 4 <= 0x7fffffffL;
+  double sum = 0.0;
+  for (int g = 0; ok && g < G; ++g) {
+    const float w = weights->w[g];
+    ok = heads->logits[g] != nullptr && heads->logits[g] != out && w > 0.0f && w <= 3.0e38f;  // NaN fails w > 0
+    sum += w;
+  }
+  if (!ok) {
+    sca_set_error("sca_ensemble_log_probs: bad arguments (1 <= G <= 8 non-null tensors other than out, G finite "
+                  "positive weights, mode 0 or 1, B, T, C >= 1)");
+    return SCA_ERR_ARG;
+  }
+  EnsHeads h;
+  for (int g = 0; g < G_MAX; ++g) {
+    const int s = g < G ? g : 0;
+    const double w = (double)weights->w[s] / sum;
+    h.x[g] = heads->logits[s];
+    h.w[g] = (float)w;
+    h.lw[g] = (float)log(w);
+  }
+  hipLaunchKernelGGL(ensemble_log_probs_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), h, G, mode, out, rows, C);
+  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_ensemble_log_probs: launch failed"); return SCA_ERR_LAUNCH; }
+  return SCA_OK;
+}

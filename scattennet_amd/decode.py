@@ -115,10 +115,16 @@ def ctc_decode(gloss_logits, beam_size, input_lengths):
     return _to_lists(tokens, lengths)
 
 
-def decode_outputs(outputs, beam_size=1):
+def decode_outputs(outputs, beam_size=1, ensembles=None):
     """The decoding loop of evaluate_fn (opt.py:76-89): every key of `outputs` that contains
     "gloss_logits" is decoded with outputs["input_lengths"]; the result is keyed by the
-    reference's logits_name (the key without "gloss_logits")."""
+    reference's logits_name (the key without "gloss_logits").  `ensembles`
+    ({output_key: EnsembleSpec}, ensemble.py) are computed from the logits in `outputs` first and
+    decoded with the rest; `outputs` itself is not modified."""
+    if ensembles is not None:
+        from .ensemble import add_ensembles, check_ensembles
+        outputs = dict(outputs)
+        add_ensembles(outputs, check_ensembles((), ensembles, "decode_outputs"))
     il = outputs["input_lengths"]
     dec = {k.replace("gloss_logits", ""): ctc_decode_device(v, il, beam_size)
            for k, v in outputs.items() if "gloss_logits" in k}

@@ -1,0 +1,161 @@
+"""Ensembles of the recognition heads on the HIP path (`sca_ensemble_log_probs`,
+include/scatten.h): the normalised log-probabilities of the weighted mean of G heads'
+posteriors, the tensor the multi-stream recognisers decode next to the single heads.
+
+* `ensemble_log_probs(logits_list, weights=None, mode="prob")` — one launch over the G logit
+  tensors of one forward; device tensors in and out, no host read, usable under
+  `torch.cuda.graph` capture.  `"prob"`: the arithmetic mean of the posteriors; `"logprob"`:
+  the log-linear (geometric) mean, renormalised.  Its output is a logit tensor like any other:
+  `ctc_decode_device`, `ctc_decode_heads_device` and `ctc_align_heads_device` take it as it is.
+* `EnsembleSpec(members, weights=None, mode="prob")` — which of the model's five logit tensors
+  an ensemble averages; `check_ensembles` validates a `{output_key: EnsembleSpec}` dict against
+  the decoded heads (`EvalState`, `BucketedEvalStep`, `recognize_step`), and `add_ensembles`
+  computes them into a head-output dict.
+
+The reference has no ensemble; the semantics are the header's.
+"""
+import ctypes
+import math
+
+import torch
+from torch import nn
+
+from . import _lib as L
+from .decode import _check_device, _check_logits
+from .model import _LOGITS
+from .precision import fp32_compute
+
+MAX_HEADS = L.EVAL_MAX_HEADS
+MODES = ("prob", "logprob")
+
+
+def _check_mode(mode, what):
+    if mode not in MODES:
+        raise ValueError(f"{what}: mode must be one of {MODES}, got {mode!r}")
+    return MODES.index(mode)
+
+
+def _check_weights(weights, G, what):
+    """G normalised weights as Python floats (computed in double); None: equal weights."""
+    if weights is None:
+        return [1.0 / G] * G
+    try:
+        ws = [float(w) for w in weights]
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: weights must be None or {G} finite positive numbers, got {weights!r}") from None
+    if len(ws) != G or not all(math.isfinite(w) and w > 0.0 for w in ws):
+        raise ValueError(f"{what}: weights must be None or {G} finite positive numbers, got {weights!r}")
+    total = math.fsum(ws)
+    ws = [w / total for w in ws]
+    if not all(float(ctypes.c_float(w).value) > 0.0 for w in ws):
+        raise ValueError(f"{what}: weights must not vanish in fp32 once normalised, got {weights!r}")
+    return ws
+
+
+class _Ensembler(nn.Module):
+    """Parameter-free module, so that fp16 / bf16 logits take the fp32 view of fp32_compute."""
+
+    @fp32_compute()
+    def forward(self, weights, mode, *logits):
+        xs = [x.detach().contiguous() for x in logits]
+        L.require_device(*xs)
+        G = len(xs)
+        B, T, C = xs[0].shape
+        out = torch.empty_like(xs[0])
+        hx, wx = L.DecodeHeads(), L.EnsembleWeights()
+        for g, x in enumerate(xs):
+            hx.logits[g] = x.data_ptr()
+            wx.w[g] = weights[g]
+        L.check(L.lib().sca_ensemble_log_probs(ctypes.byref(hx), G, ctypes.byref(wx), mode, B, T, C, L.ptr(out),
+                                               L.stream_handle()), "sca_ensemble_log_probs")
+        return out
+
+
+_ensembler = _Ensembler()
+
+
+def _check_heads(logits_list):
+    xs = list(logits_list)
+    if not 1 <= len(xs) <= MAX_HEADS:
+        raise ValueError(f"ensemble_log_probs: between 1 and {MAX_HEADS} logit tensors, got {len(xs)}")
+    for x in xs:
+        _check_logits(x)
+    first = xs[0]
+    for x in xs[1:]:
+        if x.shape != first.shape or x.dtype != first.dtype or x.device != first.device:
+            raise ValueError("ensemble_log_probs: every head must have the same shape, dtype and device; got "
+                             f"{tuple(first.shape)} {first.dtype} {first.device} and {tuple(x.shape)} {x.dtype} "
+                             f"{x.device}")
+    if first.numel() == 0:
+        raise ValueError(f"ensemble_log_probs: empty logits {tuple(first.shape)}")
+    return xs
+
+
+def ensemble_log_probs(logits_list, weights=None, mode="prob"):
+    """The ensemble of G heads' posteriors as normalised log-probabilities, in one launch
+    (`sca_ensemble_log_probs`).  `logits_list`: 1..8 tensors of one shape (B, T, C); `weights`:
+    None (equal) or G finite positive numbers, normalised by their sum; `mode`: "prob", the
+    arithmetic mean of the posteriors (log sum_g w_g softmax(x_g)), or "logprob", the log-linear
+    mean renormalised (log_softmax(sum_g w_g log_softmax(x_g))).  With G = 1 both are the rows'
+    log_softmax.  Returns a detached (B, T, C) device tensor.  No host sync; capturable."""
+    xs = _check_heads(logits_list)
+    ws = _check_weights(weights, len(xs), "ensemble_log_probs")
+    m = _check_mode(mode, "ensemble_log_probs")
+    _check_device(xs[0])
+    return _ensembler(ws, m, *xs)
+
+
+class EnsembleSpec:
+    """One ensemble of the model's heads: `members`, 1..8 distinct keys of the five logit
+    tensors (they need not be among the decoded heads), `weights` (None: equal, or one finite
+    positive number per member) and `mode` ("prob" / "logprob"), as `ensemble_log_probs` takes
+    them.  ValueError for anything else."""
+
+    def __init__(self, members, weights=None, mode="prob"):
+        if isinstance(members, str):
+            raise ValueError(f"EnsembleSpec: members must be a sequence of logit keys, got the string {members!r}")
+        members = tuple(members)
+        if not 1 <= len(members) <= MAX_HEADS or len(set(members)) != len(members):
+            raise ValueError(f"EnsembleSpec: members must be 1..{MAX_HEADS} distinct keys, got {members!r}")
+        for k in members:
+            if k not in _LOGITS:
+                raise ValueError(f"EnsembleSpec: unknown member {k!r}; the logit keys are {_LOGITS}")
+        _check_mode(mode, "EnsembleSpec")
+        self.members, self.mode = members, mode
+        self.weights = None if weights is None else tuple(_check_weights(weights, len(members), "EnsembleSpec"))
+
+    def __repr__(self):
+        return f"EnsembleSpec(members={self.members!r}, weights={self.weights!r}, mode={self.mode!r})"
+
+    def compute(self, outputs):
+        return ensemble_log_probs([outputs[k] for k in self.members], self.weights, self.mode)
+
+
+def check_ensembles(heads, ensembles, what):
+    """The `{output_key: EnsembleSpec}` dict of an evaluation or recognition step, validated on
+    the host against the decoded `heads`: every key contains "gloss_logits" (the reference's
+    evaluate_fn loop would pick it up), is none of the five logit keys, and heads plus ensembles
+    are at most 8 decoded tensors.  Returns the dict (empty for None), in insertion order."""
+    if ensembles is None:
+        return {}
+    if not isinstance(ensembles, dict):
+        raise ValueError(f"{what}: ensembles must be a dict {{output_key: EnsembleSpec}}, got {type(ensembles).__name__}")
+    for key, spec in ensembles.items():
+        if not isinstance(key, str) or "gloss_logits" not in key:
+            raise ValueError(f"{what}: an ensemble's output key must contain 'gloss_logits', got {key!r}")
+        if key in _LOGITS:
+            raise ValueError(f"{what}: the ensemble key {key!r} is one of the model's own logit keys {_LOGITS}")
+        if not isinstance(spec, EnsembleSpec):
+            raise ValueError(f"{what}: ensembles[{key!r}] must be an EnsembleSpec, got {type(spec).__name__}")
+    if len(heads) + len(ensembles) > MAX_HEADS:
+        raise ValueError(f"{what}: {len(heads)} heads and {len(ensembles)} ensembles are more than the {MAX_HEADS} "
+                         "tensors one grouped decode takes")
+    return dict(ensembles)
+
+
+def add_ensembles(outputs, ensembles):
+    """Compute every ensemble of `ensembles` from the logits in `outputs` and put it there under
+    its key (one launch each).  Returns the keys added, in order."""
+    for key, spec in ensembles.items():
+        outputs[key] = spec.compute(outputs)
+    return tuple(ensembles)

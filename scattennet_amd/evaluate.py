@@ -17,6 +17,8 @@ read until the pass is over.
 * `BucketedEvalStep` — `BucketedTrainStep`'s scheme for evaluation: batches of any length are
   padded to a frame bucket, each bucket's step is captured on its second use and replayed
   after, and all buckets append to one `EvalState`.
+* `ensembles={output_key: EnsembleSpec}` (ensemble.py) on either: the heads' averaged posterior,
+  computed after the forward and decoded, aligned, scored and logged as one more head.
 
 `{name}wer` keys use the reference's `logits_name` (the output key without "gloss_logits":
 "alignment_", "fuse_coord_").  Hypotheses are class ids; the tokenizer, the results JSON and
@@ -34,6 +36,7 @@ from .bucketed import _Bucket, check_buckets, pad_batch, pick_bucket
 from .align import alignment_lists, ctc_align_heads_device
 from .decode import MAX_BEAM, WER_MAX_LEN, _check_device, _check_lengths, _check_logits, wer_from_counts
 from .encoder import n_pool_of
+from .ensemble import add_ensembles, check_ensembles
 from .heads import _dev_i32
 from .model import _LOGITS, _students_of, first_error, flag_names
 from .precision import fp32_compute
@@ -49,6 +52,17 @@ def logits_name(key):
 def default_heads():
     """The keys evaluate_fn decodes (opt.py:80): those containing "gloss_logits"."""
     return tuple(k for k in _LOGITS if "gloss_logits" in k)
+
+
+def check_head_keys(heads, what):
+    """The decoded heads of a step as a tuple: 1..8 distinct logit keys; None: `default_heads()`."""
+    keys = default_heads() if heads is None else tuple(heads)
+    if not 1 <= len(keys) <= MAX_HEADS or len(set(keys)) != len(keys):
+        raise ValueError(f"{what}: heads must be 1..{MAX_HEADS} distinct keys, got {keys!r}")
+    for k in keys:
+        if k not in _LOGITS:
+            raise ValueError(f"{what}: unknown head {k!r}; the logit keys are {_LOGITS}")
+    return keys
 
 
 def loss_names(students=()):
@@ -166,15 +180,14 @@ class EvalState:
     hypothesis: the pooled frame count).  `align=True` (needs a log) makes `eval_step` force-align
     every head's hypothesis and attaches `span_log` (capacity, G, log_width, 2) int32, `conf_log`
     (capacity, G, log_width) and `score_log` (capacity, G) fp32, read by `alignments()`.
-    `reset()` clears everything on the current stream."""
+    `ensembles`: `{output_key: EnsembleSpec}` (ensemble.py); `eval_step` computes each from the
+    forward's logits and decodes, aligns, scores and logs it after the plain heads, under its
+    `logits_name` (`keys` = `heads` + the ensemble keys is the order of every G above).  The key
+    must contain "gloss_logits" and be none of the five logit keys; heads and ensembles together
+    are at most 8.  `reset()` clears everything on the current stream."""
 
-    def __init__(self, model, heads=None, capacity=0, log_width=None, align=False):
-        keys = default_heads() if heads is None else tuple(heads)
-        if not 1 <= len(keys) <= MAX_HEADS or len(set(keys)) != len(keys):
-            raise ValueError(f"EvalState: heads must be 1..{MAX_HEADS} distinct keys, got {keys!r}")
-        for k in keys:
-            if k not in _LOGITS:
-                raise ValueError(f"EvalState: unknown head {k!r}; the logit keys are {_LOGITS}")
+    def __init__(self, model, heads=None, capacity=0, log_width=None, align=False, ensembles=None):
+        keys = check_head_keys(heads, "EvalState")
         capacity = int(capacity)
         if capacity < 0:
             raise ValueError("EvalState: capacity must not be negative")
@@ -182,14 +195,16 @@ class EvalState:
             raise ValueError(f"EvalState: a log needs log_width in [1, {WER_MAX_LEN}], got {log_width!r}")
         if align and not capacity:
             raise ValueError("EvalState: align=True needs a log (capacity > 0) to keep the alignments in")
+        self.ensembles = check_ensembles(keys, ensembles, "EvalState")
         self.heads = keys
+        self.keys = keys + tuple(self.ensembles)  # every decoded tensor: the plain heads, then the ensembles
         self.align = bool(align)
         self.students = list(model._students())
         self.flag_names = flag_names(self.students)
         self.loss_names = loss_names(self.students)
         self.capacity, self.log_width = capacity, int(log_width) if capacity else 0
         self.device = next(model.parameters()).device
-        G = len(keys)
+        G = len(self.keys)
         self.state = torch.zeros(ctypes.sizeof(L.EvalState) // 8, dtype=torch.int64, device=self.device)
         self.hyp_log = self.hyp_len_log = None
         if capacity:
@@ -220,7 +235,7 @@ class EvalState:
 
     def read(self):
         """The pass's single host read: `results_from_state` of the state."""
-        return results_from_state(self.raw(), self.heads, self.loss_names, self.flag_names)
+        return results_from_state(self.raw(), self.keys, self.loss_names, self.flag_names)
 
     def hypotheses(self):
         """Per clip, in arrival order: {logits_name: [class ids]} (needs a log: capacity > 0)."""
@@ -228,7 +243,7 @@ class EvalState:
             raise RuntimeError("EvalState.hypotheses: no log attached (capacity = 0)")
         n = min(self.raw()["cursor"], self.capacity)
         packed = torch.cat([self.hyp_len_log[:n].unsqueeze(-1), self.hyp_log[:n]], dim=-1).cpu().numpy()
-        return [{logits_name(k): packed[r, g, 1:1 + packed[r, g, 0]].tolist() for g, k in enumerate(self.heads)}
+        return [{logits_name(k): packed[r, g, 1:1 + packed[r, g, 0]].tolist() for g, k in enumerate(self.keys)}
                 for r in range(n)]
 
     def alignments(self, frame_scale=1):
@@ -238,14 +253,14 @@ class EvalState:
         if not self.align:
             raise RuntimeError("EvalState.alignments: the state was built without align=True")
         n = min(self.raw()["cursor"], self.capacity)
-        G, W = len(self.heads), self.log_width
+        G, W = len(self.keys), self.log_width
         packed = torch.cat([self.hyp_len_log[:n].unsqueeze(-1).double(), self.hyp_log[:n].double(),
                             self.span_log[:n].reshape(n, G, 2 * W).double(), self.conf_log[:n].double(),
                             self.score_log[:n].unsqueeze(-1).double()], dim=-1).cpu().numpy()
         out = []
         for r in range(n):
             clip = {}
-            for g, k in enumerate(self.heads):
+            for g, k in enumerate(self.keys):
                 row = packed[r, g]
                 lists = alignment_lists(row[None, 1:1 + W].astype(np.int64), row[None, 0].astype(np.int64),
                                         row[None, 1 + W:1 + 3 * W].reshape(1, W, 2).astype(np.int64),
@@ -274,8 +289,8 @@ def accumulate(state, tokens, lengths, ref, ref_len, report):
     ref_len (B) (int32, device) and added to `state` with the step's `finite_report`.  Returns
     the step's counts (G, B, 4) int32."""
     G, B, Hmax = tokens.shape
-    if G != len(state.heads):
-        raise ValueError(f"accumulate: {G} heads decoded, the state holds {len(state.heads)}")
+    if G != len(state.keys):
+        raise ValueError(f"accumulate: {G} heads decoded, the state holds {len(state.keys)}")
     if ref.dim() != 2 or ref.shape[0] != B:
         raise ValueError(f"accumulate: ref must be ({B}, Rmax), got {tuple(ref.shape)}")
     if Hmax > WER_MAX_LEN or ref.shape[1] > WER_MAX_LEN:
@@ -300,8 +315,8 @@ def log_alignments(state, spans, conf, scores):
     to the state's alignment log at the state's cursor.  Call it BEFORE `accumulate`, which
     advances the cursor."""
     G, B, S = conf.shape
-    if G != len(state.heads):
-        raise ValueError(f"log_alignments: {G} heads aligned, the state holds {len(state.heads)}")
+    if G != len(state.keys):
+        raise ValueError(f"log_alignments: {G} heads aligned, the state holds {len(state.keys)}")
     if not (spans.is_cuda and spans.dtype == torch.int32 and spans.is_contiguous() and conf.is_cuda and
             conf.dtype == torch.float32 and conf.is_contiguous() and scores.is_cuda and
             scores.dtype == torch.float32 and scores.is_contiguous()):
@@ -325,6 +340,10 @@ def eval_step(model, src_input, state, beam_size=5):
     accumulation: the outputs also hold `spans` (G, B, T', 2), `conf` (G, B, T') and
     `align_scores` (G, B).
 
+    With `state.ensembles`, each ensemble is computed right after the forward (one launch,
+    `ensemble_log_probs`), put in the outputs under its key and decoded, aligned, scored and
+    logged as one more head after the plain ones: G = len(state.keys).
+
     The model's `training` flag is left as it is: put the model in `eval()` first."""
     with torch.no_grad():
         check, model.check = model.check, ("off" if model.check == "off" else "defer")
@@ -334,7 +353,8 @@ def eval_step(model, src_input, state, beam_size=5):
             model.check = check
         if _students_of(outputs) != state.students:
             raise ValueError("eval_step: the model's distillation terms differ from the state's")
-        logits = [outputs[k] for k in state.heads]
+        add_ensembles(outputs, state.ensembles)
+        logits = [outputs[k] for k in state.keys]
         tokens, lengths, _ = ctc_decode_heads_device(logits, outputs["input_lengths"], beam_size)
         ref, ref_len = _references(src_input, tokens.shape[1], tokens.device)
         outputs["tokens"], outputs["lengths"] = tokens, lengths
@@ -373,7 +393,8 @@ class BucketedEvalStep:
     the eager `eval_step` unpadded.  All buckets append to one `EvalState` (`.state`); with
     `capacity` > 0 it logs the hypotheses, `log_width` being the largest bucket's pooled length;
     `align=True` adds the forced alignment of every hypothesis (`alignments()`): a span does not
-    depend on the bucket, because the heads' `input_lengths` are the batch's own.
+    depend on the bucket, because the heads' `input_lengths` are the batch's own.  `ensembles`
+    are `EvalState`'s: an ensemble row depends on nothing but its frame, so padding changes none.
 
     Returns the step's outputs, the logits, `tokens` (and `spans`, `conf`) trimmed (views) to the batch's own
     T >> n_pool frames; they are views of the bucket's static outputs, valid until the next
@@ -381,14 +402,14 @@ class BucketedEvalStep:
     exceed 128 (the WER matrix)."""
 
     def __init__(self, model, batch_size, frame_buckets, label_bucket, beam_size=5, heads=None, capacity=0,
-                 align=False):
+                 align=False, ensembles=None):
         self.frame_buckets = check_eval_buckets(model.cfg, frame_buckets, label_bucket)
         if batch_size < 1 or label_bucket < 1:
             raise ValueError("BucketedEvalStep: batch_size and label_bucket must be positive")
         self.model, self.beam_size = model, int(beam_size)
         self.batch_size, self.label_bucket = int(batch_size), int(label_bucket)
         self.n_pool = n_pool_of(model.cfg)
-        self.state = EvalState(model, heads, capacity, self.frame_buckets[-1] >> self.n_pool, align)
+        self.state = EvalState(model, heads, capacity, self.frame_buckets[-1] >> self.n_pool, align, ensembles)
         self._buckets = {f: _Bucket(f) for f in self.frame_buckets}
         self._stream = None
         self.eager_fallbacks = 0
@@ -428,7 +449,7 @@ class BucketedEvalStep:
     def _trim(self, outputs, T):
         n = T >> self.n_pool
         out = dict(outputs)
-        for k in _LOGITS:
+        for k in _LOGITS + tuple(self.state.ensembles):
             if k in out:
                 out[k] = out[k][:, :n]
         out["tokens"] = out["tokens"][:, :, :n]

@@ -25,6 +25,10 @@ length would reach the valid ones — the fusion softmax, the SeqKD terms and th
 reverse direction — then read it on the device, so the valid frames' outputs, the losses and
 every parameter gradient are those of the unpadded batch.
 
+Without labels.  `predict(src_input)` is `forward` up to the heads: the five logit tensors,
+`input_lengths` and `finite_flags` (the flag words of the ten tensors checked before the losses,
+`predict_flag_names`), no loss kernel and no label key; `recognize.py` decodes and aligns them.
+
 The model computes in fp32 (`.half()` of the whole model is not supported; the submodules keep
 their own reduced-precision paths).
 
@@ -51,6 +55,11 @@ def flag_names(students=()):
     """The tensors the reference checks, in the order it checks them (model/__init__.py:130-235)."""
     return (["keypoints", "body_embed", "left_embed", "right_embed", "fuse_embed"] + list(_LOGITS) +
             ["alignment_loss", "fuse_coord_loss"] + [f"{s}_distill_loss" for s in students])
+
+
+def predict_flag_names():
+    """The tensors `MSCA_Net.predict` checks: those the reference tests before its losses."""
+    return flag_names()[:5 + len(_LOGITS)]
 
 
 def first_error(flags, names):
@@ -231,6 +240,48 @@ class MSCA_Net(SCAEncoder):
             self.raise_if_nonfinite(outputs)
         return outputs
 
+    def predict_flag_names(self):
+        return predict_flag_names()
+
+    def predict(self, src_input):
+        """The label-free forward: `forward`'s `encode` and `recognition_head` calls and nothing
+        after them.  `src_input` needs `keypoints`, `mask`, `valid_len_in` and, for a batch padded
+        to a bucket, `valid_frames`; no label key is read and no loss kernel is launched.  Returns
+        the five logit tensors, `input_lengths` and `finite_flags`: the int32 device words of
+        `finite_flags()` over the ten tensors the reference checks before its losses
+        (`predict_flag_names()`), all zero with `check == "off"`.  `check == "sync"` reads them once
+        and raises the reference's ValueError (`first_error`); "defer" and a capturing stream make
+        no host read (`raise_if_flagged(outputs["finite_flags"])` later)."""
+        if self.check not in CHECK_MODES:
+            raise ValueError(f"MSCA_Net.check must be one of {CHECK_MODES}, got {self.check!r}")
+        if torch.cuda.is_available() and self.device == "cuda":
+            src_input = {k: v.cuda() if isinstance(v, torch.Tensor) else v for k, v in src_input.items()}
+        keypoints = src_input["keypoints"]
+        mask = src_input["mask"]
+        valid = None
+        if src_input.get("valid_frames") is not None:
+            if torch.compiler.is_compiling():
+                raise NotImplementedError("MSCA_Net: valid_frames (length-bucketed batches) is not supported while "
+                                          "torch.compile traces; run the bucketed step eagerly or captured")
+            valid = ops.check_valid((src_input["valid_frames"], self.n_pool()))
+
+        fuse_embed, left_embed, right_embed, body_embed = self.encode(keypoints, mask, valid=valid)
+        head_outputs = self.recognition_head(left_embed, right_embed, fuse_embed, body_embed, valid=valid)
+        outputs = {k: head_outputs[k] for k in _LOGITS if k in head_outputs}
+        outputs["input_lengths"] = src_input["valid_len_in"]
+
+        names = predict_flag_names()
+        if self.check == "off":
+            outputs["finite_flags"] = torch.zeros(len(names), dtype=torch.int32, device=keypoints.device)
+            return outputs
+        scanned = {"keypoints": keypoints, "body_embed": body_embed, "left_embed": left_embed,
+                   "right_embed": right_embed, "fuse_embed": fuse_embed}
+        outputs["finite_flags"] = finite_flags([(scanned[n] if n in scanned else outputs[n]).detach().contiguous()
+                                                for n in names])
+        if self.check == "sync" and not torch.cuda.is_current_stream_capturing():
+            raise_if_flagged(outputs["finite_flags"])
+        return outputs
+
     def read_report(self, outputs):
         return read_report(outputs)
 
@@ -262,6 +313,13 @@ def read_report(outputs):
 def guard_of(outputs):
     """0-d fp32 device view of the report's guard scalar, for FusedAdam.step(loss=...)."""
     return outputs["finite_report"].view(torch.float32)[report_layout(_students_of(outputs))["guard"]]
+
+
+def raise_if_flagged(flags):
+    """One host read of `predict`'s `finite_flags`; the reference's ValueError when flagged."""
+    msg = first_error(flags.cpu().tolist(), predict_flag_names())
+    if msg is not None:
+        raise ValueError(msg)
 
 
 def raise_if_nonfinite(outputs):

@@ -1,0 +1,199 @@
+"""Recognition without references: unlabelled keypoints in, glosses with their frame spans and
+confidences out.
+
+* `recognize_step(model, src_input, ...)` — `MSCA_Net.predict` (the label-free forward, finite
+  check deferred), the ensembles, the grouped CTC decode and the forced alignment of every
+  decoded tensor's own hypothesis, enqueued on the current stream without a host read;
+  capturable for a fixed (B, T) by the rules of `train.py`.
+* `BucketedRecognizer` — `BucketedEvalStep`'s scheme for it: batches of any length are padded
+  to a frame bucket, each bucket's step is captured on its second use and replayed after.
+* `Recognition` — a step's outputs (a dict of device tensors); `read()` is the batch's one host
+  read and returns, per clip, {logits_name: [(class id, start, end, confidence), ...]}.
+
+The model must be in `eval()` (a model left in training mode recognises with dropout), and the
+hypotheses are class ids: the tokenizer stays with the caller.
+"""
+import numpy as np
+import torch
+
+from .align import MAX_LABELS, alignment_lists, ctc_align_heads_device
+from .bucketed import _Bucket, check_buckets, pad_batch, pick_bucket
+from .encoder import n_pool_of
+from .ensemble import add_ensembles, check_ensembles
+from .evaluate import check_head_keys, ctc_decode_heads_device, logits_name
+from .model import _LOGITS, first_error, predict_flag_names
+
+_PACKED = ("finite_flags", "lengths", "tokens", "spans", "conf", "align_scores")
+
+
+class Recognition(dict):
+    """The outputs of one recognition step: the logits (the model's five and the ensembles),
+    `input_lengths`, `finite_flags`, `tokens` (G, B, T') / `lengths` (G, B) / `scores` (G, B) and,
+    with `align`, `spans` (G, B, T', 2), `conf` (G, B, T'), `align_scores` (G, B): device tensors,
+    row g belonging to `decoded[g]`.  `frame_scale`: input frames per logit frame."""
+
+    def __init__(self, outputs, decoded, align, frame_scale):
+        super().__init__(outputs)
+        self.decoded, self.align, self.frame_scale = tuple(decoded), bool(align), int(frame_scale)
+
+    def read(self, frame_scale=None):
+        """The batch's one host read, a single packed device-to-host copy.  Raises the
+        reference's ValueError (model/__init__.py:130-167) for the first flagged tensor;
+        otherwise returns a list of B dicts {logits_name: [(class id, start, end, confidence),
+        ...]} (`alignment_lists`: spans in input frames, `frame_scale` defaulting to the
+        encoder's 2**n_pool; None for a clip whose hypothesis could not be aligned), or, for a
+        step without alignment, {logits_name: [class ids]}."""
+        scale = self.frame_scale if frame_scale is None else frame_scale
+        parts = [self[k] for k in _PACKED if k in self]
+        packed = torch.cat([t.reshape(-1).to(torch.float64) for t in parts]).cpu().numpy()  # exact for int32, fp32
+        host, at = {}, 0
+        for k, t in zip([k for k in _PACKED if k in self], parts):
+            host[k] = packed[at:at + t.numel()].reshape(tuple(t.shape))
+            at += t.numel()
+        msg = first_error(host["finite_flags"].astype(np.int64).tolist(), predict_flag_names())
+        if msg is not None:
+            raise ValueError(msg)
+        tokens, lengths = host["tokens"].astype(np.int64), host["lengths"].astype(np.int64)
+        G, B = lengths.shape
+        if self.align:
+            spans = host["spans"].astype(np.int64)
+            per_head = [alignment_lists(tokens[g], lengths[g], spans[g], host["conf"][g], host["align_scores"][g], scale)
+                        for g in range(G)]
+        else:
+            per_head = [[tokens[g, b, :lengths[g, b]].tolist() for b in range(B)] for g in range(G)]
+        return [{logits_name(k): per_head[g][b] for g, k in enumerate(self.decoded)} for b in range(B)]
+
+
+def _recognize(model, src_input, keys, ensembles, beam_size, align):
+    with torch.no_grad():
+        check, model.check = model.check, ("off" if model.check == "off" else "defer")
+        try:
+            outputs = model.predict(src_input)
+        finally:
+            model.check = check
+        add_ensembles(outputs, ensembles)
+        decoded = keys + tuple(ensembles)
+        logits = [outputs[k] for k in decoded]
+        tokens, lengths, scores = ctc_decode_heads_device(logits, outputs["input_lengths"], beam_size)
+        outputs["tokens"], outputs["lengths"], outputs["scores"] = tokens, lengths, scores
+        if align:
+            res = ctc_align_heads_device(logits, outputs["input_lengths"], tokens, lengths)
+            outputs["spans"], outputs["conf"], outputs["align_scores"] = res.spans, res.conf.float(), res.scores.float()
+    return Recognition(outputs, decoded, align, 2 ** model.n_pool())
+
+
+def recognize_step(model, src_input, heads=None, ensembles=None, beam_size=5, align=True):
+    """One recognition step of MSCA_Net, enqueued on the current stream without a host read:
+    `model.predict(src_input)` under no_grad with the finite check deferred (a `model.check` of
+    "off" is kept), the `ensembles` ({output_key: EnsembleSpec}), the grouped decode of `heads`
+    (default: the keys evaluate_fn decodes) and the ensembles with `input_lengths`
+    (`beam_size=0`: greedy) and, with `align`, the forced alignment of every decoded tensor's own
+    hypothesis.  `src_input` needs no label key.  Returns a `Recognition`.
+
+    The model's `training` flag is left as it is: put the model in `eval()` first."""
+    keys = check_head_keys(heads, "recognize_step")
+    return _recognize(model, src_input, keys, check_ensembles(keys, ensembles, "recognize_step"), int(beam_size),
+                      bool(align))
+
+
+class BucketedRecognizer:
+    """`recognize_step` for batches of varying length, `BucketedEvalStep`'s scheme without labels:
+    `step(src_input)` pads keypoints and mask to the smallest of `frame_buckets` that holds the
+    batch (`pad_batch`, `valid_frames`), copies them into the bucket's static device tensors and
+    runs the bucket's step.  The first use of a bucket runs eagerly on a side stream, the second
+    captures the step into a hipGraph (a private pool per bucket) and replays it, later uses
+    replay.  A batch whose B differs from `batch_size` runs the eager step unpadded and counts
+    in `eager_fallbacks`.
+
+    `step` returns a `Recognition` with the logits, `tokens`, `spans` and `conf` trimmed (views) to
+    the batch's own T >> n_pool frames; they are views of the bucket's static outputs, valid
+    until the next `step`.  `Recognition.read()` is the batch's one host read.  The model must be
+    in `eval()`; buckets are multiples of 2**n_pool, at most cfg["max_position_embeddings"], and
+    with `align` their pooled length may not exceed the alignment's 1023 labels."""
+
+    def __init__(self, model, batch_size, frame_buckets, beam_size=5, heads=None, ensembles=None, align=True):
+        frame_buckets = tuple(frame_buckets)
+        self.frame_buckets = check_buckets(model.cfg, frame_buckets, len(frame_buckets))  # no optimizer
+        if batch_size < 1:
+            raise ValueError("BucketedRecognizer: batch_size must be positive")
+        self.n_pool = n_pool_of(model.cfg)
+        if align and self.frame_buckets[-1] >> self.n_pool > MAX_LABELS:
+            raise ValueError(f"BucketedRecognizer: bucket {self.frame_buckets[-1]} has "
+                             f"{self.frame_buckets[-1] >> self.n_pool} pooled frames, more than the {MAX_LABELS} "
+                             "labels the alignment takes")
+        self.heads = check_head_keys(heads, "BucketedRecognizer")
+        self.ensembles = check_ensembles(self.heads, ensembles, "BucketedRecognizer")
+        self.model, self.beam_size, self.align = model, int(beam_size), bool(align)
+        self.batch_size = int(batch_size)
+        self.device = next(model.parameters()).device
+        self._buckets = {f: _Bucket(f) for f in self.frame_buckets}
+        self._stream = None
+        self.eager_fallbacks = 0
+
+    @property
+    def graphs_captured(self):
+        return sum(b.graph is not None for b in self._buckets.values())
+
+    def bucket_for(self, T):
+        return pick_bucket(self.frame_buckets, T)
+
+    def _run(self, src):
+        return _recognize(self.model, src, self.heads, self.ensembles, self.beam_size, self.align)
+
+    def _fill(self, bucket, padded):
+        """The bucket's static inputs, refilled; nothing else of the batch reaches the step."""
+        keys = ("keypoints", "mask", "valid_len_in", "valid_frames")
+        if bucket.static is None:
+            bucket.static = {}
+            for k in keys:
+                t = torch.as_tensor(padded[k])
+                bucket.static[k] = torch.empty(t.shape, dtype=t.dtype, device=self.device)
+        for k in keys:
+            t = torch.as_tensor(padded[k])
+            if t.shape != bucket.static[k].shape or t.dtype != bucket.static[k].dtype:
+                raise ValueError(f"BucketedRecognizer: {k} changed from {tuple(bucket.static[k].shape)} "
+                                 f"{bucket.static[k].dtype} to {tuple(t.shape)} {t.dtype} between batches")
+            bucket.static[k].copy_(t, non_blocking=True)
+        return dict(bucket.static)
+
+    def _trim(self, rec, T):
+        n = T >> self.n_pool
+        out = Recognition(rec, rec.decoded, rec.align, rec.frame_scale)
+        for k in _LOGITS + tuple(self.ensembles):
+            if k in out:
+                out[k] = out[k][:, :n]
+        out["tokens"] = out["tokens"][:, :, :n]
+        if "spans" in out:
+            out["spans"], out["conf"] = out["spans"][:, :, :n], out["conf"][:, :, :n]
+        return out
+
+    def step(self, src_input):
+        kp = src_input["keypoints"]
+        B, T = kp.shape[0], kp.shape[1]
+        if B != self.batch_size:
+            self.eager_fallbacks += 1
+            return self._trim(self._run(src_input), T)
+        bucket = self._buckets[self.bucket_for(T)]
+        src = self._fill(bucket, pad_batch(src_input, bucket.frames))
+        bucket.uses += 1
+        if bucket.graph is not None:
+            bucket.graph.replay()
+            return self._trim(bucket.outputs, T)
+        if bucket.uses == 1:  # warm-up: a real eager step, on a side stream as capture will be
+            if self._stream is None:
+                self._stream = torch.cuda.Stream(device=self.device)
+            self._stream.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(self._stream):
+                rec = self._run(src)
+            torch.cuda.current_stream().wait_stream(self._stream)
+            return self._trim(rec, T)
+        # second use: capture, then the replay is this batch's step
+        torch.cuda.synchronize()
+        bucket.pool = torch.cuda.graph_pool_handle()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, pool=bucket.pool):
+            rec = self._run(src)
+        bucket.outputs = rec
+        bucket.graph = graph
+        graph.replay()
+        return self._trim(bucket.outputs, T)

@@ -42,6 +42,9 @@ checkout's package (it uses nothing the parent commit lacks).
 --align (with --mixed --eval): two BucketedEvalStep over the same stream, both with a hypothesis
 log of the whole pass, one with align=True (forced alignment of every head's hypotheses, logged);
 whole passes in alternated windows, ms per batch and the per-window difference.
+
+--ensemble (with --mixed --eval): the same pair, one with an ensemble of the five heads decoded
+after the two default heads; asserts that the default heads' totals and hypotheses are identical.
 """
 import argparse
 import json
@@ -334,6 +337,54 @@ def eval_align(a, dev):
     print(json.dumps(res))
 
 
+def eval_ensemble(a, dev):
+    """--mixed --eval --ensemble: the bucketed evaluation pass with and without one ensemble of
+    the five heads added to the two default heads, both with a hypothesis log of the whole pass,
+    in alternated windows.  The two default heads' totals and hypotheses must not change."""
+    import scattennet_amd as S
+    from scattennet_amd.model import _LOGITS
+    model, _, w, _ = build(a, dev)
+    model.check = "defer"
+    n_pool = (len(w["residual_blocks"]) + 1) // 2
+    batches = mixed_batches(a, w, dev, n_pool)
+    buckets = tuple(int(b) for b in a.buckets.split(","))
+    capacity = a.batches * a.B
+    spec = {"ensemble_gloss_logits": S.EnsembleSpec(_LOGITS)}
+    steps = {"plain": S.BucketedEvalStep(model, a.B, buckets, a.S, beam_size=a.beam, capacity=capacity),
+             "ensemble": S.BucketedEvalStep(model, a.B, buckets, a.S, beam_size=a.beam, capacity=capacity,
+                                            ensembles=spec)}
+    g = torch.Generator().manual_seed(a.seed + 1)
+    for bes in steps.values():
+        for _ in range(2):  # warm-up pass, capture pass
+            bes.state.reset()
+            _pass(bes.step, batches)
+        for f in buckets:  # a bucket the stream visits less than twice (or never) is captured here
+            while bes._buckets[f].graph is None:
+                bes.state.reset()
+                bes.step(_batch(a, w, dev, g, [f] * a.B, n_pool)[0])
+        assert bes.graphs_captured == len(buckets)
+    ms, results, totals = {k: [] for k in steps}, {}, {}
+    for _ in range(a.windows):  # alternated windows
+        for k, bes in steps.items():
+            bes.state.reset()
+            ms[k].append(_pass(bes.step, batches))
+            results[k] = bes.read()  # the pass's one host read (after the timed window's synchronise)
+            totals[k] = bes.state.raw()["totals"][:2].tolist()
+    names = ("alignment_", "fuse_coord_")
+    hyps = {k: [{n: h[n] for n in names} for h in bes.hypotheses()] for k, bes in steps.items()}
+    assert totals["plain"] == totals["ensemble"], "the default heads' totals changed with the ensemble"
+    assert hyps["plain"] == hyps["ensemble"], "the default heads' hypotheses changed with the ensemble"
+    assert all(results["plain"][n + "wer"] == results["ensemble"][n + "wer"] for n in names)
+    diff = [x - y for x, y in zip(ms["ensemble"], ms["plain"])]
+    res = {"workload": "MSCA_Net bucketed evaluation pass over a mixed-length stream, with and without one "
+                       "five-member ensemble decoded after the two default heads (both log the hypotheses)",
+           "B": a.B, "max_len": a.T, "C": a.C, "S": a.S, "beam": a.beam, "seed": a.seed, "buckets": list(buckets),
+           "batch_lengths": [T for _, T in batches], "plain_ms_per_batch": _spread(ms["plain"]),
+           "ensemble_ms_per_batch": _spread(ms["ensemble"]), "ensemble_minus_plain_ms_per_batch": _spread(diff),
+           "default_heads_identical": True, "results": {k: round(v, 4) for k, v in results["ensemble"].items()}}
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=8)
@@ -349,6 +400,8 @@ def main():
                                                         "BucketedEvalStep")
     ap.add_argument("--align", action="store_true", help="with --mixed --eval: the bucketed pass with and without "
                                                          "the forced alignment of every hypothesis")
+    ap.add_argument("--ensemble", action="store_true", help="with --mixed --eval: the bucketed pass with and without "
+                                                            "one five-member ensemble beside the two default heads")
     ap.add_argument("--beam", type=int, default=5)
     ap.add_argument("--batches", type=int, default=20)
     ap.add_argument("--buckets", default="64,128,192,256")
@@ -362,6 +415,8 @@ def main():
     if a.mixed:
         if a.eval and a.align:
             return eval_align(a, dev)
+        if a.eval and a.ensemble:
+            return eval_ensemble(a, dev)
         return eval_mixed(a, dev) if a.eval else mixed(a, dev)
     model, src, w, t4 = build(a, dev)
     graphs = {k: capture(model, src, k, dev) for k in ("off", "defer")}
