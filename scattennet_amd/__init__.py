@@ -22,7 +22,7 @@ from .align import (align_outputs, alignment_lists, ctc_align, ctc_align_device,
 from .optim import FusedAdam, WarmupCosineAnnealingScheduler, build_optimizer, clip_grad_norm_  # noqa: F401
 from .model import MSCA_Net, finite_flags, first_error  # noqa: F401
 from .train import read_report, train_step  # noqa: F401
-from .bucketed import BucketedTrainStep, pad_batch  # noqa: F401
+from .bucketed import BucketedStep, BucketedTrainStep, pad_batch  # noqa: F401
 from .ensemble import EnsembleSpec, ensemble_log_probs  # noqa: F401
 from .evaluate import BucketedEvalStep, EvalState, ctc_decode_heads_device, eval_step  # noqa: F401
 from .recognize import BucketedRecognizer, Recognition, recognize_step  # noqa: F401

@@ -14,9 +14,9 @@ read until the pass is over.
   decode, `sca_eval_accumulate`.  No host read; capturable for a fixed (B, T, S) by the rules
   of `train.py`.  It does NOT touch the model's `training` flag: call `model.eval()` first, as
   `evaluate_fn` does (opt.py:62) — a model left in training mode is evaluated with dropout.
-* `BucketedEvalStep` — `BucketedTrainStep`'s scheme for evaluation: batches of any length are
-  padded to a frame bucket, each bucket's step is captured on its second use and replayed
-  after, and all buckets append to one `EvalState`.
+* `BucketedEvalStep` — a subclass of `BucketedStep` (bucketed.py), the runner `BucketedTrainStep`
+  is built on: batches of any length are padded to a frame bucket, each bucket's step is
+  captured on its second use and replayed after, and all buckets append to one `EvalState`.
 * `ensembles={output_key: EnsembleSpec}` (ensemble.py) on either: the heads' averaged posterior,
   computed after the forward and decoded, aligned, scored and logged as one more head.
 
@@ -31,14 +31,13 @@ import torch
 from torch import nn
 
 from . import _lib as L
-from . import heads as _heads
-from .bucketed import _Bucket, check_buckets, pad_batch, pick_bucket
+from .bucketed import BucketedStep, check_buckets
 from .align import alignment_lists, ctc_align_heads_device
 from .decode import MAX_BEAM, WER_MAX_LEN, _check_device, _check_lengths, _check_logits, wer_from_counts
 from .encoder import n_pool_of
 from .ensemble import add_ensembles, check_ensembles
-from .heads import _dev_i32
-from .model import _LOGITS, _students_of, first_error, flag_names
+from .heads import _dev_i32, labels_2d
+from .model import _LOGITS, _students_of, deferred_check, first_error, flag_names
 from .precision import fp32_compute
 
 MAX_HEADS = L.EVAL_MAX_HEADS
@@ -271,11 +270,7 @@ class EvalState:
 
 
 def _references(src_input, B, device):
-    lab = torch.as_tensor(src_input["gloss_labels"])
-    if lab.dim() == 1:
-        lab = _heads._pad_concatenated(lab, src_input["gloss_lengths"], B)
-    if lab.dim() != 2 or lab.shape[0] != B:
-        raise ValueError(f"eval_step: gloss_labels must be (B, S) or 1-D concatenated, got {tuple(lab.shape)}")
+    lab = labels_2d(src_input, B, "eval_step")
     if lab.shape[1] > WER_MAX_LEN:
         raise ValueError(f"eval_step: references of {lab.shape[1]} tokens exceed the WER kernel's {WER_MAX_LEN}")
     ref_len = torch.as_tensor(src_input["gloss_lengths"]).reshape(-1)
@@ -328,6 +323,23 @@ def log_alignments(state, spans, conf, scores):
             "sca_eval_log_alignments")
 
 
+def decode_and_align(outputs, keys, ensembles, beam_size, align):
+    """The tail `eval_step` and `recognize_step` share, on a forward's `outputs` (modified in
+    place): the `ensembles` under their keys, the grouped decode of `keys` with
+    outputs["input_lengths"] into `tokens` (G, B, T') / `lengths` (G, B) and, with `align`, the
+    forced alignment of every decoded tensor's own hypothesis into `spans` (G, B, T', 2), `conf`
+    (G, B, T') and `align_scores` (G, B), both fp32.  Returns the decode's scores (G, B), which the
+    caller may publish.  No host read."""
+    add_ensembles(outputs, ensembles)
+    logits = [outputs[k] for k in keys]
+    tokens, lengths, scores = ctc_decode_heads_device(logits, outputs["input_lengths"], beam_size)
+    outputs["tokens"], outputs["lengths"] = tokens, lengths
+    if align:
+        res = ctc_align_heads_device(logits, outputs["input_lengths"], tokens, lengths)
+        outputs["spans"], outputs["conf"], outputs["align_scores"] = res.spans, res.conf.float(), res.scores.float()
+    return scores
+
+
 def eval_step(model, src_input, state, beam_size=5):
     """One evaluation step of MSCA_Net, enqueued on the current stream without a host read:
     forward under no_grad with the finite check deferred (a `model.check` of "off" is kept),
@@ -346,33 +358,21 @@ def eval_step(model, src_input, state, beam_size=5):
 
     The model's `training` flag is left as it is: put the model in `eval()` first."""
     with torch.no_grad():
-        check, model.check = model.check, ("off" if model.check == "off" else "defer")
-        try:
+        with deferred_check(model):
             outputs = model(src_input)
-        finally:
-            model.check = check
         if _students_of(outputs) != state.students:
             raise ValueError("eval_step: the model's distillation terms differ from the state's")
-        add_ensembles(outputs, state.ensembles)
-        logits = [outputs[k] for k in state.keys]
-        tokens, lengths, _ = ctc_decode_heads_device(logits, outputs["input_lengths"], beam_size)
+        decode_and_align(outputs, state.keys, state.ensembles, beam_size, state.align)
+        tokens, lengths = outputs["tokens"], outputs["lengths"]
         ref, ref_len = _references(src_input, tokens.shape[1], tokens.device)
-        outputs["tokens"], outputs["lengths"] = tokens, lengths
         if state.align:
-            res = ctc_align_heads_device(logits, outputs["input_lengths"], tokens, lengths)
-            spans, conf, scores = res.spans, res.conf.float(), res.scores.float()
-            log_alignments(state, spans, conf, scores)
-            outputs["spans"], outputs["conf"], outputs["align_scores"] = spans, conf, scores
+            log_alignments(state, outputs["spans"], outputs["conf"], outputs["align_scores"])
         outputs["counts"] = accumulate(state, tokens, lengths, ref, ref_len, outputs["finite_report"])
     return outputs
 
 
 # ------------------------------------------------------------------------------- buckets
-def check_eval_buckets(cfg, frame_buckets, label_bucket):
-    """Constructor validation of BucketedEvalStep (host only): the sorted bucket tuple."""
-    frame_buckets = tuple(frame_buckets)
-    buckets = check_buckets(cfg, frame_buckets, len(frame_buckets))  # no optimizer: no capture slots to run out of
-    n_pool = n_pool_of(cfg)
+def _check_wer_limits(buckets, n_pool, label_bucket):
     for f in buckets:
         if f >> n_pool > WER_MAX_LEN:
             raise ValueError(f"BucketedEvalStep: bucket {f} has {f >> n_pool} pooled frames, more than the "
@@ -380,14 +380,21 @@ def check_eval_buckets(cfg, frame_buckets, label_bucket):
     if label_bucket > WER_MAX_LEN:
         raise ValueError(f"BucketedEvalStep: label_bucket {label_bucket} exceeds the {WER_MAX_LEN} tokens the WER "
                          "matrix holds")
+
+
+def check_eval_buckets(cfg, frame_buckets, label_bucket):
+    """Constructor validation of BucketedEvalStep (host only): the sorted bucket tuple."""
+    buckets = check_buckets(cfg, frame_buckets, "BucketedEvalStep")
+    _check_wer_limits(buckets, n_pool_of(cfg), label_bucket)
     return buckets
 
 
-class BucketedEvalStep:
-    """`eval_step` for batches of varying length, `BucketedTrainStep`'s scheme without an
-    optimizer: `step(src_input)` pads the batch to the smallest of `frame_buckets` that holds it
-    and to `label_bucket` labels per clip (`pad_batch`, `valid_frames`), copies it into the
-    bucket's static device tensors and runs the bucket's step.  The first use of a bucket runs
+class BucketedEvalStep(BucketedStep):
+    """`eval_step` for batches of varying length, a subclass of `BucketedStep` (bucketed.py, the
+    runner under `BucketedTrainStep`): `step(src_input)` pads the batch to the smallest of
+    `frame_buckets` that holds it and to `label_bucket` labels per clip (`pad_batch`,
+    `valid_frames`), copies it into the bucket's static device tensors and runs the bucket's
+    step, `eval_step`: no optimizer and no hook.  The first use of a bucket runs
     eagerly on a side stream, the second captures the step into a hipGraph (a private pool per
     bucket) and replays it, later uses replay.  A batch whose B differs from `batch_size` runs
     the eager `eval_step` unpadded.  All buckets append to one `EvalState` (`.state`); with
@@ -403,23 +410,10 @@ class BucketedEvalStep:
 
     def __init__(self, model, batch_size, frame_buckets, label_bucket, beam_size=5, heads=None, capacity=0,
                  align=False, ensembles=None):
-        self.frame_buckets = check_eval_buckets(model.cfg, frame_buckets, label_bucket)
-        if batch_size < 1 or label_bucket < 1:
-            raise ValueError("BucketedEvalStep: batch_size and label_bucket must be positive")
-        self.model, self.beam_size = model, int(beam_size)
-        self.batch_size, self.label_bucket = int(batch_size), int(label_bucket)
-        self.n_pool = n_pool_of(model.cfg)
+        super().__init__(model, batch_size, frame_buckets, label_bucket)
+        _check_wer_limits(self.frame_buckets, self.n_pool, label_bucket)
+        self.beam_size = int(beam_size)
         self.state = EvalState(model, heads, capacity, self.frame_buckets[-1] >> self.n_pool, align, ensembles)
-        self._buckets = {f: _Bucket(f) for f in self.frame_buckets}
-        self._stream = None
-        self.eager_fallbacks = 0
-
-    @property
-    def graphs_captured(self):
-        return sum(b.graph is not None for b in self._buckets.values())
-
-    def bucket_for(self, T):
-        return pick_bucket(self.frame_buckets, T)
 
     def read(self):
         return self.state.read()
@@ -430,60 +424,11 @@ class BucketedEvalStep:
     def alignments(self, frame_scale=1):
         return self.state.alignments(frame_scale)
 
-    def _fill(self, bucket, padded, device):
-        keys = ("keypoints", "mask", "valid_len_in", "gloss_labels", "gloss_lengths", "valid_frames")
-        if bucket.static is None:
-            bucket.static = {}
-            for k in keys:
-                t = torch.as_tensor(padded[k])
-                bucket.static[k] = torch.empty(t.shape, dtype=t.dtype, device=device)
-        for k in keys:
-            t = torch.as_tensor(padded[k])
-            if t.shape != bucket.static[k].shape or t.dtype != bucket.static[k].dtype:
-                raise ValueError(f"BucketedEvalStep: {k} changed from {tuple(bucket.static[k].shape)} "
-                                 f"{bucket.static[k].dtype} to {tuple(t.shape)} {t.dtype} between batches")
-            bucket.static[k].copy_(t, non_blocking=True)
-        extra = {k: v for k, v in padded.items() if k not in keys}
-        return {**extra, **bucket.static}
+    def _device(self):
+        return self.state.device
 
-    def _trim(self, outputs, T):
-        n = T >> self.n_pool
-        out = dict(outputs)
-        for k in _LOGITS + tuple(self.state.ensembles):
-            if k in out:
-                out[k] = out[k][:, :n]
-        out["tokens"] = out["tokens"][:, :, :n]
-        if "spans" in out:
-            out["spans"], out["conf"] = out["spans"][:, :, :n], out["conf"][:, :, :n]
-        return out
+    def _run(self, src):
+        return eval_step(self.model, src, self.state, self.beam_size)
 
-    def step(self, src_input):
-        kp = src_input["keypoints"]
-        B, T = kp.shape[0], kp.shape[1]
-        if B != self.batch_size:
-            self.eager_fallbacks += 1
-            return self._trim(eval_step(self.model, src_input, self.state, self.beam_size), T)
-        bucket = self._buckets[self.bucket_for(T)]
-        src = self._fill(bucket, pad_batch(src_input, bucket.frames, self.label_bucket), self.state.device)
-        bucket.uses += 1
-        if bucket.graph is not None:
-            bucket.graph.replay()
-            return self._trim(bucket.outputs, T)
-        if bucket.uses == 1:  # warm-up: a real eager step, on a side stream as capture will be
-            if self._stream is None:
-                self._stream = torch.cuda.Stream(device=self.state.device)
-            self._stream.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(self._stream):
-                outputs = eval_step(self.model, src, self.state, self.beam_size)
-            torch.cuda.current_stream().wait_stream(self._stream)
-            return self._trim(outputs, T)
-        # second use: capture, then the replay is this batch's step
-        torch.cuda.synchronize()
-        bucket.pool = torch.cuda.graph_pool_handle()
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, pool=bucket.pool):
-            outputs = eval_step(self.model, src, self.state, self.beam_size)
-        bucket.outputs = outputs
-        bucket.graph = graph
-        graph.replay()
-        return self._trim(bucket.outputs, T)
+    def _trimmed_keys(self):
+        return tuple(self.state.ensembles)

@@ -147,6 +147,17 @@ def _pad_concatenated(labels, tgt_lengths, B):
     return out
 
 
+def labels_2d(src_input, B, who):
+    """`src_input["gloss_labels"]` as (B, S): 2-D labels as they are, 1-D concatenated labels split
+    by `gloss_lengths`; ValueError under the caller's name `who` for anything else."""
+    lab = torch.as_tensor(src_input["gloss_labels"])
+    if lab.dim() == 1:
+        lab = _pad_concatenated(lab, src_input["gloss_lengths"], B)
+    if lab.dim() != 2 or lab.shape[0] != B:
+        raise ValueError(f"{who}: gloss_labels must be (B, S) or 1-D concatenated, got {tuple(lab.shape)}")
+    return lab
+
+
 def compute_loss(labels, tgt_lengths, logits, input_lengths, return_per_sample=False):
     """MSCA_Net.compute_loss (model/__init__.py:241-290): logits (B, T, C) batch-major (the
     reference permutes to (T, B, C) itself).  labels: (B, S) padded, or 1-D concatenated as

@@ -36,6 +36,7 @@ Report layout (int32 words, `report_layout`): the flag words in `flag_names` ord
 bit 1 Inf), then as fp32 `alignment_loss`, `fuse_coord_loss`, the distillation terms in
 `cfg["distillation_weight"]` order, `total_loss`, `guard`.
 """
+import contextlib
 import ctypes
 
 import torch
@@ -291,6 +292,18 @@ class MSCA_Net(SCAEncoder):
     def raise_if_nonfinite(self, outputs):
         """Read the report (one host read) and raise the reference's ValueError when flagged."""
         return raise_if_nonfinite(outputs)
+
+
+@contextlib.contextmanager
+def deferred_check(model):
+    """For the body, `model.check` is "defer" (an "off" stays "off"): what a step that must not
+    read the host runs its forward under.  The earlier value is back afterwards, also when the
+    body raises."""
+    check, model.check = model.check, ("off" if model.check == "off" else "defer")
+    try:
+        yield
+    finally:
+        model.check = check
 
 
 def _students_of(outputs):

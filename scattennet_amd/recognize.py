@@ -5,8 +5,9 @@ confidences out.
   check deferred), the ensembles, the grouped CTC decode and the forced alignment of every
   decoded tensor's own hypothesis, enqueued on the current stream without a host read;
   capturable for a fixed (B, T) by the rules of `train.py`.
-* `BucketedRecognizer` — `BucketedEvalStep`'s scheme for it: batches of any length are padded
-  to a frame bucket, each bucket's step is captured on its second use and replayed after.
+* `BucketedRecognizer` — a subclass of `BucketedStep` (bucketed.py) for it: batches of any length
+  are padded to a frame bucket, each bucket's step is captured on its second use and replayed
+  after.
 * `Recognition` — a step's outputs (a dict of device tensors); `read()` is the batch's one host
   read and returns, per clip, {logits_name: [(class id, start, end, confidence), ...]}.
 
@@ -16,12 +17,11 @@ hypotheses are class ids: the tokenizer stays with the caller.
 import numpy as np
 import torch
 
-from .align import MAX_LABELS, alignment_lists, ctc_align_heads_device
-from .bucketed import _Bucket, check_buckets, pad_batch, pick_bucket
-from .encoder import n_pool_of
-from .ensemble import add_ensembles, check_ensembles
-from .evaluate import check_head_keys, ctc_decode_heads_device, logits_name
-from .model import _LOGITS, first_error, predict_flag_names
+from .align import MAX_LABELS, alignment_lists
+from .bucketed import BucketedStep
+from .ensemble import check_ensembles
+from .evaluate import check_head_keys, decode_and_align, logits_name
+from .model import deferred_check, first_error, predict_flag_names
 
 _PACKED = ("finite_flags", "lengths", "tokens", "spans", "conf", "align_scores")
 
@@ -66,19 +66,10 @@ class Recognition(dict):
 
 def _recognize(model, src_input, keys, ensembles, beam_size, align):
     with torch.no_grad():
-        check, model.check = model.check, ("off" if model.check == "off" else "defer")
-        try:
+        with deferred_check(model):
             outputs = model.predict(src_input)
-        finally:
-            model.check = check
-        add_ensembles(outputs, ensembles)
         decoded = keys + tuple(ensembles)
-        logits = [outputs[k] for k in decoded]
-        tokens, lengths, scores = ctc_decode_heads_device(logits, outputs["input_lengths"], beam_size)
-        outputs["tokens"], outputs["lengths"], outputs["scores"] = tokens, lengths, scores
-        if align:
-            res = ctc_align_heads_device(logits, outputs["input_lengths"], tokens, lengths)
-            outputs["spans"], outputs["conf"], outputs["align_scores"] = res.spans, res.conf.float(), res.scores.float()
+        outputs["scores"] = decode_and_align(outputs, decoded, ensembles, beam_size, align)
     return Recognition(outputs, decoded, align, 2 ** model.n_pool())
 
 
@@ -96,14 +87,14 @@ def recognize_step(model, src_input, heads=None, ensembles=None, beam_size=5, al
                       bool(align))
 
 
-class BucketedRecognizer:
-    """`recognize_step` for batches of varying length, `BucketedEvalStep`'s scheme without labels:
-    `step(src_input)` pads keypoints and mask to the smallest of `frame_buckets` that holds the
-    batch (`pad_batch`, `valid_frames`), copies them into the bucket's static device tensors and
-    runs the bucket's step.  The first use of a bucket runs eagerly on a side stream, the second
-    captures the step into a hipGraph (a private pool per bucket) and replays it, later uses
-    replay.  A batch whose B differs from `batch_size` runs the eager step unpadded and counts
-    in `eager_fallbacks`.
+class BucketedRecognizer(BucketedStep):
+    """`recognize_step` for batches of varying length, a subclass of `BucketedStep` (bucketed.py)
+    without labels: `step(src_input)` pads keypoints and mask to the smallest of `frame_buckets`
+    that holds the batch (`pad_batch`, `valid_frames`), copies them into the bucket's static
+    device tensors and runs the bucket's step.  The first use of a bucket runs eagerly on a side
+    stream, the second captures the step into a hipGraph (a private pool per bucket) and replays
+    it, later uses replay.  A batch whose B differs from `batch_size` runs the eager step
+    unpadded and counts in `eager_fallbacks`.
 
     `step` returns a `Recognition` with the logits, `tokens`, `spans` and `conf` trimmed (views) to
     the batch's own T >> n_pool frames; they are views of the bucket's static outputs, valid
@@ -111,89 +102,28 @@ class BucketedRecognizer:
     in `eval()`; buckets are multiples of 2**n_pool, at most cfg["max_position_embeddings"], and
     with `align` their pooled length may not exceed the alignment's 1023 labels."""
 
+    static_keys = ("keypoints", "mask", "valid_len_in", "valid_frames")
+    pass_other_keys = False  # nothing else of the batch reaches the step
+
     def __init__(self, model, batch_size, frame_buckets, beam_size=5, heads=None, ensembles=None, align=True):
-        frame_buckets = tuple(frame_buckets)
-        self.frame_buckets = check_buckets(model.cfg, frame_buckets, len(frame_buckets))  # no optimizer
-        if batch_size < 1:
-            raise ValueError("BucketedRecognizer: batch_size must be positive")
-        self.n_pool = n_pool_of(model.cfg)
+        super().__init__(model, batch_size, frame_buckets)
         if align and self.frame_buckets[-1] >> self.n_pool > MAX_LABELS:
             raise ValueError(f"BucketedRecognizer: bucket {self.frame_buckets[-1]} has "
                              f"{self.frame_buckets[-1] >> self.n_pool} pooled frames, more than the {MAX_LABELS} "
                              "labels the alignment takes")
         self.heads = check_head_keys(heads, "BucketedRecognizer")
         self.ensembles = check_ensembles(self.heads, ensembles, "BucketedRecognizer")
-        self.model, self.beam_size, self.align = model, int(beam_size), bool(align)
-        self.batch_size = int(batch_size)
+        self.beam_size, self.align = int(beam_size), bool(align)
         self.device = next(model.parameters()).device
-        self._buckets = {f: _Bucket(f) for f in self.frame_buckets}
-        self._stream = None
-        self.eager_fallbacks = 0
 
-    @property
-    def graphs_captured(self):
-        return sum(b.graph is not None for b in self._buckets.values())
-
-    def bucket_for(self, T):
-        return pick_bucket(self.frame_buckets, T)
+    def _device(self):
+        return self.device
 
     def _run(self, src):
         return _recognize(self.model, src, self.heads, self.ensembles, self.beam_size, self.align)
 
-    def _fill(self, bucket, padded):
-        """The bucket's static inputs, refilled; nothing else of the batch reaches the step."""
-        keys = ("keypoints", "mask", "valid_len_in", "valid_frames")
-        if bucket.static is None:
-            bucket.static = {}
-            for k in keys:
-                t = torch.as_tensor(padded[k])
-                bucket.static[k] = torch.empty(t.shape, dtype=t.dtype, device=self.device)
-        for k in keys:
-            t = torch.as_tensor(padded[k])
-            if t.shape != bucket.static[k].shape or t.dtype != bucket.static[k].dtype:
-                raise ValueError(f"BucketedRecognizer: {k} changed from {tuple(bucket.static[k].shape)} "
-                                 f"{bucket.static[k].dtype} to {tuple(t.shape)} {t.dtype} between batches")
-            bucket.static[k].copy_(t, non_blocking=True)
-        return dict(bucket.static)
+    def _trimmed_keys(self):
+        return tuple(self.ensembles)
 
-    def _trim(self, rec, T):
-        n = T >> self.n_pool
-        out = Recognition(rec, rec.decoded, rec.align, rec.frame_scale)
-        for k in _LOGITS + tuple(self.ensembles):
-            if k in out:
-                out[k] = out[k][:, :n]
-        out["tokens"] = out["tokens"][:, :, :n]
-        if "spans" in out:
-            out["spans"], out["conf"] = out["spans"][:, :, :n], out["conf"][:, :, :n]
-        return out
-
-    def step(self, src_input):
-        kp = src_input["keypoints"]
-        B, T = kp.shape[0], kp.shape[1]
-        if B != self.batch_size:
-            self.eager_fallbacks += 1
-            return self._trim(self._run(src_input), T)
-        bucket = self._buckets[self.bucket_for(T)]
-        src = self._fill(bucket, pad_batch(src_input, bucket.frames))
-        bucket.uses += 1
-        if bucket.graph is not None:
-            bucket.graph.replay()
-            return self._trim(bucket.outputs, T)
-        if bucket.uses == 1:  # warm-up: a real eager step, on a side stream as capture will be
-            if self._stream is None:
-                self._stream = torch.cuda.Stream(device=self.device)
-            self._stream.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(self._stream):
-                rec = self._run(src)
-            torch.cuda.current_stream().wait_stream(self._stream)
-            return self._trim(rec, T)
-        # second use: capture, then the replay is this batch's step
-        torch.cuda.synchronize()
-        bucket.pool = torch.cuda.graph_pool_handle()
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, pool=bucket.pool):
-            rec = self._run(src)
-        bucket.outputs = rec
-        bucket.graph = graph
-        graph.replay()
-        return self._trim(bucket.outputs, T)
+    def _keep(self, rec):
+        return Recognition(rec, rec.decoded, rec.align, rec.frame_scale)

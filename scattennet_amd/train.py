@@ -25,7 +25,7 @@ once per length bucket and replays the bucket's graph on padded batches.
 import math
 
 from . import ops
-from .model import _students_of, first_error, flag_names, guard_of
+from .model import _students_of, deferred_check, first_error, flag_names, guard_of
 from .model import read_report as model_read_report
 
 
@@ -35,11 +35,8 @@ def train_step(model, optimizer, src_input):
     for p in model.parameters():
         p.grad = None
     ops.advance_dropout()
-    check, model.check = model.check, ("off" if model.check == "off" else "defer")
-    try:
+    with deferred_check(model):
         outputs = model(src_input)
-    finally:
-        model.check = check
     ops.fork_ledger_begin()
     try:
         outputs["total_loss"].backward()

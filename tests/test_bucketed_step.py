@@ -160,3 +160,71 @@ def test_new_operator_is_registered_and_the_old_schema_is_unchanged():
         x = torch.empty(2, 5, 16)
         y = torch.ops.scatten.softmax_rows_valid(x, torch.empty(1, dtype=torch.int32), 1)
         assert y.shape == x.shape and y.dtype == x.dtype
+
+
+class _ModelWithParameter(_Model):
+    """For the evaluator and the recognizer, whose constructors take the device from the model."""
+
+    def parameters(self):
+        return iter([torch.nn.Parameter(torch.zeros(1))])
+
+    def _students(self):
+        return []
+
+
+def test_a_bad_bucket_is_reported_under_the_callers_own_name():
+    import scattennet_amd as S
+    m = _ModelWithParameter([64, 64], 64)  # one pooling stage
+    with pytest.raises(ValueError, match="^BucketedRecognizer: bucket 33 is not a multiple") as e:
+        S.BucketedRecognizer(m, 3, (33,))
+    assert "capture_slots" not in str(e.value) and "BucketedTrainStep" not in str(e.value)
+    with pytest.raises(ValueError, match="^BucketedEvalStep: bucket 33 is not a multiple") as e:
+        S.BucketedEvalStep(m, 3, (33,), 8)
+    assert "capture_slots" not in str(e.value) and "BucketedTrainStep" not in str(e.value)
+    with pytest.raises(ValueError, match="^BucketedTrainStep: bucket 33 is not a multiple"):
+        S.BucketedTrainStep(m, _Opt(1), 3, (33,), 8)
+    # neither needs an optimizer, so neither has capture slots to run out of
+    rec, bes = S.BucketedRecognizer(m, 3, (16, 32, 48)), S.BucketedEvalStep(m, 3, (16, 32, 48), 8)
+    with pytest.raises(ValueError, match="^BucketedTrainStep: 3 buckets need .* capture_slots >= 3"):
+        S.BucketedTrainStep(m, _Opt(2), 3, (16, 32, 48), 8)
+    for step, name in ((rec, "BucketedRecognizer"), (bes, "BucketedEvalStep")):
+        assert step.bucket_for(17) == 32 and not step.captured(32)
+        with pytest.raises(ValueError, match=f"^{name}: a batch of 49 frames fits no bucket"):
+            step.bucket_for(49)
+    with pytest.raises(ValueError, match="^BucketedRecognizer: batch_size must be positive"):
+        S.BucketedRecognizer(m, 0, (16,))
+    with pytest.raises(ValueError, match="^BucketedEvalStep: batch_size and label_bucket must be positive"):
+        S.BucketedEvalStep(m, 3, (16,), 0)
+
+
+def test_deferred_check_swaps_and_restores():
+    from types import SimpleNamespace
+    from scattennet_amd.model import deferred_check
+    model = SimpleNamespace(check="sync")
+    with deferred_check(model):
+        assert model.check == "defer"
+    assert model.check == "sync"
+    model.check = "off"
+    with deferred_check(model):
+        assert model.check == "off"
+    assert model.check == "off"
+    model.check = "sync"
+    with pytest.raises(KeyError):
+        with deferred_check(model):
+            assert model.check == "defer"
+            raise KeyError("the body failed")
+    assert model.check == "sync"
+
+
+def test_labels_2d_from_both_label_forms():
+    from scattennet_amd.heads import labels_2d
+    two_d, concat = _batch(), _batch(concat=True)
+    assert labels_2d(two_d, 3, "caller") is two_d["gloss_labels"]  # 2-D: as it is
+    got = labels_2d(concat, 3, "caller")
+    assert got.shape == (3, 3) and got.dtype == two_d["gloss_labels"].dtype
+    valid = torch.arange(3)[None, :] < two_d["gloss_lengths"][:, None]
+    assert torch.equal(got, two_d["gloss_labels"] * valid)  # the same labels, zero past each clip's length
+    with pytest.raises(ValueError, match="^caller: gloss_labels must be .*got \\(3, 3, 1\\)"):
+        labels_2d({**two_d, "gloss_labels": two_d["gloss_labels"].unsqueeze(-1)}, 3, "caller")
+    with pytest.raises(ValueError, match="^eval_step: gloss_labels must be"):
+        labels_2d(two_d, 2, "eval_step")  # (3, S) labels for a batch of two clips

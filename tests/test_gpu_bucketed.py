@@ -439,3 +439,75 @@ def test_other_batch_size_falls_back_to_eager(fx):
     assert bts.eager_fallbacks == 1 and out["left"].shape[1] == 13 and "valid_frames" not in last
     assert bts.graphs_captured == 1 and int(opt.step_count) == 3
     _follow("fallback loss", losses, ref_losses)
+
+
+# ------------------------------------------------------------ the runner alone
+class _Cfg:
+    cfg = {"residual_blocks": [64, 64], "max_position_embeddings": 8}  # one pooling stage
+
+
+def _pooled_sums(src):
+    """A step without model kernels: per clip, the keypoint sums of each pair of frames, in the
+    shapes of a step's logits (B, T', 1), tokens (1, B, T'), spans (1, B, T', 2) and conf
+    (1, B, T'), and the mask's frame count per clip.  Integer-valued inputs: exact in fp32."""
+    kp = src["keypoints"]
+    B, n = kp.shape[0], kp.shape[1] >> 1
+    pooled = kp.sum((2, 3))[:, :2 * n].reshape(B, n, 2).sum(-1)
+    tokens = pooled.to(torch.int32).unsqueeze(0)
+    return {"left": pooled.unsqueeze(-1), "tokens": tokens, "spans": torch.stack([tokens, tokens + 1], -1),
+            "conf": 0.5 * pooled.unsqueeze(0), "frames": src["mask"].sum(1)}
+
+
+def _runner(dev):
+    import scattennet_amd as S
+
+    class Runner(S.BucketedStep):
+        static_keys = ("keypoints", "mask", "valid_frames")
+        replays = captures = 0
+
+        def _device(self):
+            return dev
+
+        def _run(self, src):
+            return _pooled_sums(src)
+
+        def _before_replay(self):
+            self.replays += 1
+
+        def _before_capture(self):
+            self.captures += 1
+
+    return Runner(_Cfg, 2, (8, 4))
+
+
+def _plain_batch(dev, B, T, seed):
+    g = torch.Generator().manual_seed(seed)
+    return {"keypoints": torch.randint(-9, 10, (B, T, 5, 2), generator=g).float().to(dev),
+            "mask": torch.ones(B, T, dtype=torch.int64, device=dev)}
+
+
+def test_runner_alone_warms_up_captures_replays_and_trims():
+    """BucketedStep with a step of a few torch ops: the protocol's counts and every return."""
+    dev = _dev()
+    run = _runner(dev)
+    assert run.frame_buckets == (4, 8) and run.n_pool == 1 and not run.captured(4)
+    captured = []
+    for seed, (B, T) in enumerate([(2, 3), (2, 3), (2, 3), (2, 7), (2, 7), (1, 5)]):
+        src = _plain_batch(dev, B, T, seed)
+        out = run.step(src)
+        captured.append(run.graphs_captured)
+        want = _pooled_sums(src)
+        assert set(out) == set(want) and out["left"].shape == (B, T >> 1, 1) and out["spans"].shape == (1, B, T >> 1, 2)
+        for k, v in want.items():
+            assert torch.equal(out[k], v), (B, T, k)
+        assert out["frames"].tolist() == [T] * B  # the mask was padded with zeros
+    assert captured == [0, 1, 1, 1, 2, 2]
+    assert {f: run._buckets[f].uses for f in (4, 8)} == {4: 3, 8: 2}
+    assert run.captured(4) and run.captured(8) and run.eager_fallbacks == 1
+    assert run.captures == 2  # once per bucket
+    assert run.replays == 1   # the third 3-frame batch; a capture's own first replay is not announced
+    bad = _plain_batch(dev, 2, 3, 9)
+    bad["mask"] = bad["mask"].to(torch.int32)
+    with pytest.raises(ValueError, match="Runner: mask changed from .* to .* between batches"):
+        run.step(bad)
+    assert run._buckets[4].uses == 3

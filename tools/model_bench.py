@@ -179,6 +179,23 @@ def _pass(fn, batches):
     return (time.perf_counter() - t0) * 1e3 / len(batches)
 
 
+def capture_all(step, batches, exact, reset=None):
+    """Every graph of a bucketed step captured before anything is timed: a warm-up pass and a
+    capture pass over the stream, then batches of exactly a bucket's length (`exact(frames)`) for
+    a bucket the stream visits less than twice (or never).  `reset` runs before each pass or
+    extra step."""
+    for _ in range(2):
+        if reset is not None:
+            reset()
+        _pass(step.step, batches)
+    for f in step.frame_buckets:
+        while not step.captured(f):
+            if reset is not None:
+                reset()
+            step.step(exact(f))
+    assert step.graphs_captured == len(step.frame_buckets)
+
+
 def mixed(a, dev):
     import scattennet_amd as S
     adam = dict(lr=1e-4, betas=(0.9, 0.998), weight_decay=1e-3, max_grad_norm=1.0)
@@ -202,12 +219,7 @@ def mixed(a, dev):
     twin_opt = S.FusedAdam(twin.parameters(), capture_slots=len(buckets), **adam)
     bts = S.BucketedTrainStep(twin, twin_opt, a.B, buckets, a.S)
     g = torch.Generator().manual_seed(a.seed + 1)
-    for _ in range(2):  # warm-up pass, capture pass
-        _pass(bts.step, batches)
-    for f in buckets:  # a bucket the stream visits less than twice (or never) is captured here
-        while bts._buckets[f].graph is None:
-            bts.step(_batch(a, w, dev, g, [f] * a.B, n_pool)[0])
-    assert bts.graphs_captured == len(buckets)
+    capture_all(bts, batches, lambda f: _batch(a, w, dev, g, [f] * a.B, n_pool)[0])
     ms = {"eager": [], "bucketed": []}
     for _ in range(a.windows):  # alternated windows
         ms["eager"].append(_pass(eager, batches))
@@ -272,12 +284,7 @@ def eval_mixed(a, dev):
     buckets = tuple(int(b) for b in a.buckets.split(","))
     bes = S.BucketedEvalStep(model, a.B, buckets, a.S, beam_size=a.beam)
     g = torch.Generator().manual_seed(a.seed + 1)
-    for _ in range(2):  # warm-up pass, capture pass
-        _pass(bes.step, batches)
-    for f in buckets:  # a bucket the stream visits less than twice (or never) is captured here
-        while bes._buckets[f].graph is None:
-            bes.step(_batch(a, w, dev, g, [f] * a.B, n_pool)[0])
-    assert bes.graphs_captured == len(buckets)
+    capture_all(bes, batches, lambda f: _batch(a, w, dev, g, [f] * a.B, n_pool)[0])
 
     def bucketed_pass():
         bes.state.reset()
@@ -310,14 +317,7 @@ def eval_align(a, dev):
              "align": S.BucketedEvalStep(model, a.B, buckets, a.S, beam_size=a.beam, capacity=capacity, align=True)}
     g = torch.Generator().manual_seed(a.seed + 1)
     for bes in steps.values():
-        for _ in range(2):  # warm-up pass, capture pass
-            bes.state.reset()
-            _pass(bes.step, batches)
-        for f in buckets:  # a bucket the stream visits less than twice (or never) is captured here
-            while bes._buckets[f].graph is None:
-                bes.state.reset()
-                bes.step(_batch(a, w, dev, g, [f] * a.B, n_pool)[0])
-        assert bes.graphs_captured == len(buckets)
+        capture_all(bes, batches, lambda f: _batch(a, w, dev, g, [f] * a.B, n_pool)[0], bes.state.reset)
     ms, results = {k: [] for k in steps}, {}
     for _ in range(a.windows):  # alternated windows
         for k, bes in steps.items():
@@ -355,14 +355,7 @@ def eval_ensemble(a, dev):
                                             ensembles=spec)}
     g = torch.Generator().manual_seed(a.seed + 1)
     for bes in steps.values():
-        for _ in range(2):  # warm-up pass, capture pass
-            bes.state.reset()
-            _pass(bes.step, batches)
-        for f in buckets:  # a bucket the stream visits less than twice (or never) is captured here
-            while bes._buckets[f].graph is None:
-                bes.state.reset()
-                bes.step(_batch(a, w, dev, g, [f] * a.B, n_pool)[0])
-        assert bes.graphs_captured == len(buckets)
+        capture_all(bes, batches, lambda f: _batch(a, w, dev, g, [f] * a.B, n_pool)[0], bes.state.reset)
     ms, results, totals = {k: [] for k in steps}, {}, {}
     for _ in range(a.windows):  # alternated windows
         for k, bes in steps.items():
