@@ -56,7 +56,10 @@
  *   sca_eval_log_alignments  and confidences of given label sequences, and their log in a pass
  *   sca_ensemble_log_probs (no counterpart) the weighted mean of the heads' posteriors as
  *                          log-probabilities, decoded as one more head
- *   sca_finite_scan       the isnan().any() / isinf().any() tests of MSCA_Net.forward
+ *   sca_ctc_beam_decode*_nbest  (no counterpart; the interface of the decoder's top_paths) the N
+ *   sca_nbest_rescore/mbr/gather  best labellings of the beam search, their rescoring with a
+ *                          bigram gloss model, the posterior over the list and MBR selection
+ *   sca_finite_scan      the isnan().any() / isinf().any() tests of MSCA_Net.forward
  *                          (model/__init__.py:130-235), all tensors in one launch
  *   sca_step_report        total_loss (model/__init__.py:207,237), the loss terms the
  *                          training loop logs (opt.py:39-42) and the device-side form of
@@ -647,6 +650,77 @@ int sca_ctc_greedy_decode_heads(const sca_decode_heads* heads, int G, const int*
 int sca_ctc_beam_decode_heads(const sca_decode_heads* heads, int G, const int* in_len, int B, int T, int C,
                               int beam_width, int collapse_repeats, int* tokens, int* out_len, float* score,
                               void* ws, void* stream);
+
+/* ---- evaluation: n-best lists, bigram rescoring, MBR selection ------------------------------
+ * sca_ctc_beam_decode_nbest / sca_ctc_beam_decode_heads_nbest: the N = nbest best labellings of
+ * the search above, 1 <= nbest <= beam_width <= 32.  Logits, in_len, ws and its size are those
+ * of sca_ctc_beam_decode / sca_ctc_beam_decode_heads (the same three launches; G = 1 for the
+ * single-head form).  tokens (G, B, N, T) int32 padded with 0, out_len (G, B, N) int32, score
+ * (G, B, N) fp32, count (G, B) int32; every element is written by every call.
+ *   The search is sca_ctc_beam_decode's, frame for frame.  After the last frame the active
+ *   beams are in descending order of total, ties in slot order: entry n is beam n, its tokens
+ *   the prefix walked back through the arena, its score offset + total_n (the arithmetic of the
+ *   1-best score).  count = min(nbest, active beams); entries >= count have length 0, score
+ *   -inf and tokens 0.  in_len = 0 gives count 1: the empty hypothesis with score 0.
+ *   collapse_repeats = 0: nothing more is done, and entry 0 (tokens, length, score) is bitwise
+ *   sca_ctc_beam_decode's result.
+ *   collapse_repeats != 0: the groupby of utils.py:185-188 is applied to every entry.  Distinct
+ *   prefixes can collapse to one labelling ((3) and (3, 3) both become (3)), and a list with
+ *   the same hypothesis twice has no posterior, so entries that become equal are merged into
+ *   the first of them, the survivor's score being the logaddexp of its own score and its
+ *   duplicates' in ascending entry order (full-precision expf / log1pf).  The merged list is
+ *   then re-sorted by score, descending; the sort is stable (ties to the lower entry); count is
+ *   the merged count.  Entry 0 can therefore DIFFER from sca_ctc_beam_decode's collapsed
+ *   result: two merged entries can overtake the best single beam (common with few classes,
+ *   rare from some 20 classes on).
+ * One lane per final beam walks and collapses its own prefix, each lane then looks for the
+ * lowest earlier entry with equal labels, the survivors add up and a rank count re-sorts.  No
+ * float atomics: deterministic, a replayed capture is bitwise the eager call, and head g's
+ * rows are bitwise those of the single-head call on heads->logits[g].
+ *
+ * sca_nbest_rescore: the second pass over such a list.  lm: NULL, or a dense (C, C) fp32 table
+ * of log-probabilities lm[prev * C + cur].  Class 0, the blank, is never a token and stands for
+ * the sentence boundary: lm(h) = lm[0, h_0] + sum_i lm[h_{i-1}, h_i] + lm[h_{len-1}, 0], and
+ * lm(empty) = lm[0, 0]; NULL means lm(h) = 0.  Tokens are clamped into [0, C) only to stay in
+ * bounds.  For the valid entries n < count (count clamped to [0, N], lengths to [0, T]):
+ *   total_n     = score_n + (lm_weight * lm(h_n) + length_bonus * len(h_n))
+ *   posterior_n = softmax over the valid entries of posterior_scale * total_n
+ *   order       = the valid entries by total descending, ties to the lower entry
+ * Entries >= count have total -inf, posterior 0 and order[n] = n.  With lm_weight = 0 and
+ * length_bonus = 0 (and finite lm values) total is score, bit for bit, and order the identity.
+ * Specified for finite totals.  One wave per (head, clip); the len + 1 gathers of an entry are
+ * independent and summed by a butterfly in a fixed order.  total, posterior (G, B, N) fp32,
+ * order (G, B, N) int32.
+ *
+ * sca_nbest_mbr: minimum-Bayes-risk selection under the alignment of sca_wer_counts.
+ *   loss (G, B, N, N) int32: loss[i, j] = num_del + num_ins + num_sub of wer_single with
+ *     reference h_j and hypothesis h_i; 0 where i = j or an entry is not valid
+ *   risk (G, B, N) fp32: risk_i = sum_j posterior_j * loss[i, j], j ascending; +inf for i >= count
+ *   best (G, B) int32: the arg-min of risk, ties to the lower entry
+ * T <= SCA_WER_MAX_LEN.  Two launches: one workgroup per ordered pair and (head, clip), then one
+ * wave per (head, clip).
+ *
+ * sca_nbest_gather: entry sel[(g B + b) * sel_stride] (clamped to [0, N)) of every list as a
+ * 1-best row: tokens1 (G, B, T) padded with 0, out_len1 (G, B), value1 (G, B) = value[.., entry]
+ * (value (G, B, N) fp32: score or total).  sel = order with sel_stride = N selects by total,
+ * sel = best with sel_stride = 1 selects by risk.  The aligner and sca_eval_accumulate take the
+ * result as they take a decoder's.
+ *
+ * None of these allocates, copies or synchronises (capturable); arguments are validated before
+ * any GPU call.                                                                              */
+int sca_ctc_beam_decode_nbest(const float* logits, const int* in_len, int B, int T, int C, int beam_width, int nbest,
+                              int collapse_repeats, int* tokens, int* out_len, float* score, int* count, void* ws,
+                              void* stream);
+int sca_ctc_beam_decode_heads_nbest(const sca_decode_heads* heads, int G, const int* in_len, int B, int T, int C,
+                                    int beam_width, int nbest, int collapse_repeats, int* tokens, int* out_len,
+                                    float* score, int* count, void* ws, void* stream);
+int sca_nbest_rescore(const int* tokens, const int* out_len, const float* score, const int* count, int G, int B,
+                      int N, int T, const float* lm, int C, float lm_weight, float length_bonus,
+                      float posterior_scale, float* total, float* posterior, int* order, void* stream);
+int sca_nbest_mbr(const int* tokens, const int* out_len, const int* count, const float* posterior, int G, int B,
+                  int N, int T, int* loss, float* risk, int* best, void* stream);
+int sca_nbest_gather(const int* tokens, const int* out_len, const float* value, const int* sel, int sel_stride,
+                     int G, int B, int N, int T, int* tokens1, int* out_len1, float* value1, void* stream);
 
 /* ---- evaluation: CTC forced alignment (gloss spans and confidences) -----------------------
  * The best single path of G heads' logits through given label sequences: for every (head g,

@@ -181,6 +181,8 @@ class BucketedStep:
         for k in ("tokens", "spans", "conf"):
             if k in out:
                 out[k] = out[k][:, :, :n]
+        if "nbest_tokens" in out:  # (G, B, N, T')
+            out["nbest_tokens"] = out["nbest_tokens"][..., :n]
         return out
 
     def step(self, src_input):

@@ -8,6 +8,9 @@
 //     back-trace in the reference's order of preference (correct, substitution, insertion,
 //     deletion).  The reference keeps the matrix in uint8, which wraps once 3 (R + H) > 255;
 //     here the cells are 16-bit (3 * 256 = 768 at most), so that defect is NOT reproduced.
+//   * The second pass over the beam (no counterpart in the reference): the N best labellings
+//     of the same search, merged after the groupby and re-sorted, their rescoring with a bigram
+//     gloss model, the posterior over the list and MBR selection under the WER alignment above.
 // The T frames of a clip are a dependent chain (like the alpha recursion of the CTC loss),
 // so a clip is one workgroup; everything that does not depend on the beam (row normaliser,
 // the W + 1 best classes of every frame) is computed beforehand by row-parallel launches.
@@ -67,6 +70,13 @@ __device__ __forceinline__ float logaddexp(float a, float b) {
   const float hi = fmaxf(a, b), lo = fminf(a, b);
   if (lo == NEG_INF) return hi;
   return hi + __logf(1.0f + __expf(lo - hi));
+}
+
+// outside the frame loop: full-precision exp and log1p
+__device__ __forceinline__ float logaddexp_tail(float a, float b) {
+  const float hi = fmaxf(a, b), lo = fminf(a, b);
+  if (lo == NEG_INF) return hi;
+  return hi + log1pf(expf(lo - hi));
 }
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
@@ -171,10 +181,17 @@ __global__ __launch_bounds__(256) void ctc_topk_kernel(DecHeads hx, int G, const
 // that leave those loads in flight.  The beam_width best of the M <= W (W + 2) items are
 // found by counting, for each item, the items in front of it (M LDS broadcast reads per
 // item, no cross-lane traffic).
+//
+// NBEST: the same frame loop, then the tail of sca_ctc_beam_decode_nbest instead of the walk of
+// slot 0: one lane per final beam walks and collapses its own prefix into the clip's cls rows
+// (the per-frame best labels are dead once the loop is over, and nbest T <= T (W + 1) ints),
+// equal entries merge into the first of them, a rank count re-sorts, and the wave writes the
+// (nbest, T) rows out.  tokens (nbest, T), out_len / score (nbest) and count (1) per clip.
+template <bool NBEST>
 __global__ __launch_bounds__(64) void ctc_beam_kernel(DecHeads hx, const int* __restrict__ in_len, DecDims d,
-                                                      int collapse, int* __restrict__ tokens,
+                                                      int collapse, int nbest, int* __restrict__ tokens,
                                                       int* __restrict__ out_len, float* __restrict__ score,
-                                                      DecWs w) {
+                                                      int* __restrict__ count, DecWs w) {
   __shared__ int s_node[2][DEC_MAX_W], s_lab[2][DEC_MAX_W], s_par[2][DEC_MAX_W];
   __shared__ float s_lb[2][DEC_MAX_W], s_ll[2][DEC_MAX_W], s_tot[2][DEC_MAX_W];
   __shared__ float s_xe[2][DEC_MAX_W];  // this frame's logit of the beam's last label
@@ -358,6 +375,89 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(DecHeads hx, const int* __
     else lds_barrier();
   }
   __syncthreads();
+  if constexpr (NBEST) {
+    __shared__ int e_len[DEC_MAX_W], e_dup[DEC_MAX_W], e_src[DEC_MAX_W];
+    __shared__ float e_sc[DEC_MAX_W], e_msc[DEC_MAX_W];
+    __shared__ unsigned long long e_hash[DEC_MAX_W];
+    const int N = nbest, n0 = min(N, nb);
+    int* stage = w.cls + (long)slot * T * KS;  // row n: entry n's labels
+    int len = 0;
+    if (lane < n0) {  // the active beams are in descending order of total: entry n is beam n
+      auto node_at = [&](int n) { return n < DEC_ARENA_LDS ? a_lds[n] : arena[n]; };
+      const int leaf = s_node[cur][lane];
+      for (int n = leaf; len < Tb && dec_par(node_at(n)) >= 0; n = dec_par(node_at(n))) ++len;
+      int* row = stage + (long)lane * T;
+      int n = leaf;
+      for (int i = len - 1; i >= 0; --i) {
+        const unsigned long long nd = node_at(n);
+        row[i] = dec_lab(nd);
+        n = dec_par(nd);
+      }
+      unsigned long long h = 1469598103934665603ull;  // FNV-1a over the labels: a filter, not the comparison
+      if (collapse) {
+        int o = 0, prev = 0;
+        for (int i = 0; i < len; ++i) {
+          const int v = row[i];
+          if (i == 0 || v != prev) {
+            row[o++] = v;
+            h = (h ^ (unsigned)v) * 1099511628211ull;
+          }
+          prev = v;
+        }
+        len = o;
+      }
+      e_len[lane] = len;
+      e_hash[lane] = h;
+      e_sc[lane] = (float)(offset + (double)s_tot[cur][lane]);
+    }
+    __syncthreads();  // the staged rows are read by other lanes below
+    bool keep = lane < n0;
+    float msc = keep ? e_sc[lane] : NEG_INF;
+    if (collapse) {  // uncollapsed prefixes are distinct nodes and already sorted
+      int dup = lane;
+      if (lane < n0) {
+        const int* mine = stage + (long)lane * T;
+        for (int m = 0; m < lane && dup == lane; ++m) {  // the lowest earlier entry with equal labels
+          if (e_len[m] != len || e_hash[m] != e_hash[lane]) continue;
+          const int* other = stage + (long)m * T;
+          bool eq = true;
+          for (int i = 0; i < len; ++i) eq &= mine[i] == other[i];
+          if (eq) dup = m;
+        }
+        e_dup[lane] = dup;
+      }
+      keep = lane < n0 && dup == lane;
+      lds_barrier();
+      if (keep)  // the survivor adds its duplicates in ascending entry order
+        for (int m = lane + 1; m < n0; ++m)
+          if (e_dup[m] == lane) msc = logaddexp_tail(msc, e_sc[m]);
+    }
+    if (lane < n0) e_msc[lane] = msc;
+    const unsigned long long km = __ballot(keep);
+    const int cnt = __popcll(km);
+    lds_barrier();
+    int rank = lane;
+    if (collapse && keep) {  // stable: larger score first, ties to the lower entry
+      const unsigned long long mine = dec_ord(msc, lane);
+      rank = 0;
+      for (int m = 0; m < n0; ++m) rank += ((km >> m) & 1ull) && dec_ord(e_msc[m], m) > mine;
+    }
+    if (keep) e_src[rank] = lane;
+    lds_barrier();
+    int* tok = tokens + (long)slot * N * T;
+    for (int r = 0; r < N; ++r) {  // wave-uniform: every element of the clip's rows is written
+      const int src = r < cnt ? e_src[r] : 0, ln = r < cnt ? e_len[src] : 0;
+      const int* row = stage + (long)src * T;
+      for (int i = lane; i < T; i += 64) tok[(long)r * T + i] = i < ln ? row[i] : 0;
+    }
+    if (lane < N) {
+      const int src = lane < cnt ? e_src[lane] : 0;
+      out_len[(long)slot * N + lane] = lane < cnt ? e_len[src] : 0;
+      score[(long)slot * N + lane] = lane < cnt ? e_msc[src] : NEG_INF;
+    }
+    if (lane == 0) count[slot] = cnt;
+    return;
+  }
   // slot 0 is the best beam (ties to the lower slot); walk its prefix back to the root
   int* tok = tokens + (long)slot * T;
   if (lane == 0) {
@@ -557,6 +657,126 @@ __global__ __launch_bounds__(64) void eval_advance_kernel(const unsigned* __rest
   }
 }
 
+// ---- the second pass over an n-best list (include/scatten.h): rescoring, posterior, MBR ----
+// One wave per (head, clip).  The lanes stride over the len + 1 bigram terms of one entry at a
+// time (independent gathers), a butterfly sums them; lane n then holds entry n's total for the
+// softmax over the valid entries and the rank count that gives `order`.
+__global__ __launch_bounds__(64) void nbest_rescore_kernel(const int* __restrict__ tokens,
+                                                           const int* __restrict__ out_len,
+                                                           const float* __restrict__ score,
+                                                           const int* __restrict__ count, int N, int T,
+                                                           const float* __restrict__ lm, int C, float lm_weight,
+                                                           float length_bonus, float posterior_scale,
+                                                           float* __restrict__ total, float* __restrict__ posterior,
+                                                           int* __restrict__ order) {
+  __shared__ unsigned long long key[DEC_MAX_W];
+  const long s = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int cnt = clampi(count[s], 0, N);
+  float mine = NEG_INF;
+  for (int n = 0; n < cnt; ++n) {
+    const int len = clampi(out_len[s * N + n], 0, T);
+    const int* h = tokens + (s * N + n) * T;
+    float acc = 0.0f;
+    if (lm) {
+      for (int i = lane; i <= len; i += 64) {  // class 0 on either side is the sentence boundary
+        const int p = i == 0 ? 0 : clampi(h[i - 1], 0, C - 1), c = i == len ? 0 : clampi(h[i], 0, C - 1);
+        acc += lm[(long)p * C + c];
+      }
+      acc = wave_sum(acc);
+    }
+    const float t = score[s * N + n] + (lm_weight * acc + length_bonus * (float)len);
+    mine = lane == n ? t : mine;
+  }
+  const bool valid = lane < cnt;
+  const float z = valid ? posterior_scale * mine : NEG_INF;
+  const float m = wave_max(z);
+  const float e = valid ? expf(z - m) : 0.0f;
+  const float sum = wave_sum(e);
+  if (lane < N) {
+    total[s * N + lane] = valid ? mine : NEG_INF;
+    posterior[s * N + lane] = valid ? e / sum : 0.0f;
+    key[lane] = valid ? dec_ord(mine, lane) : 0ull;
+  }
+  lds_barrier();
+  if (valid) {  // the keys are distinct: the ranks are a permutation of [0, cnt)
+    int rank = 0;
+    for (int j = 0; j < cnt; ++j) rank += key[j] > key[lane];
+    order[s * N + rank] = lane;
+  } else if (lane < N) {
+    order[s * N + lane] = lane;
+  }
+}
+
+// MBR launch 1, grid (G B, N N): loss[i, j] of the ordered pair (hypothesis i, reference j) of
+// one (head, clip); 0 on the diagonal and where either entry is not valid.
+__global__ __launch_bounds__(128) void nbest_loss_kernel(const int* __restrict__ tokens,
+                                                         const int* __restrict__ out_len,
+                                                         const int* __restrict__ count, int N, int T,
+                                                         int* __restrict__ loss) {
+  __shared__ int c4[4];
+  const long s = blockIdx.x;
+  const int i = (int)blockIdx.y / N, j = (int)blockIdx.y - i * N;
+  const int cnt = clampi(count[s], 0, N);
+  int* out = loss + (s * N + i) * N + j;
+  if (i == j || i >= cnt || j >= cnt) {  // uniform over the workgroup
+    if (threadIdx.x == 0) *out = 0;
+    return;
+  }
+  const int R = clampi(out_len[s * N + j], 0, T), H = clampi(out_len[s * N + i], 0, T);
+  wer_pair(tokens + (s * N + j) * T, R, tokens + (s * N + i) * T, H, c4);
+  if (threadIdx.x == 0) *out = c4[0] + c4[1] + c4[2];  // thread 0 wrote c4
+}
+
+// MBR launch 2, one wave per (head, clip): lane i sums its row in ascending j, then the arg-min
+// (ties to the lower entry).
+__global__ __launch_bounds__(64) void nbest_risk_kernel(const int* __restrict__ loss,
+                                                        const float* __restrict__ posterior,
+                                                        const int* __restrict__ count, int N,
+                                                        float* __restrict__ risk, int* __restrict__ best) {
+  const long s = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int cnt = clampi(count[s], 0, N);
+  const bool valid = lane < cnt;
+  float r = 0.0f;
+  if (valid)
+    for (int j = 0; j < cnt; ++j) r += posterior[s * N + j] * (float)loss[(s * N + lane) * N + j];
+  float v = valid ? r : -NEG_INF;
+  if (lane < N) risk[s * N + lane] = v;
+  int idx = lane;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float w = __shfl_xor(v, o, 64);
+    const int d = __shfl_xor(idx, o, 64);
+    if (w < v || (w == v && d < idx)) { v = w; idx = d; }
+  }
+  if (lane == 0) best[s] = clampi(idx, 0, max(cnt - 1, 0));
+}
+
+// One wave per (head, clip): entry sel[s * sel_stride] of the list as a 1-best-shaped row.
+__global__ __launch_bounds__(64) void nbest_gather_kernel(const int* __restrict__ tokens,
+                                                          const int* __restrict__ out_len,
+                                                          const float* __restrict__ value,
+                                                          const int* __restrict__ sel, int sel_stride, int N, int T,
+                                                          int* __restrict__ tokens1, int* __restrict__ out_len1,
+                                                          float* __restrict__ value1) {
+  const long s = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int e = clampi(sel[s * sel_stride], 0, N - 1);
+  const int len = clampi(out_len[s * N + e], 0, T);
+  const int* row = tokens + (s * N + e) * T;
+  for (int i = lane; i < T; i += 64) tokens1[s * T + i] = i < len ? row[i] : 0;
+  if (lane == 0) {
+    out_len1[s] = len;
+    value1[s] = value[s * N + e];
+  }
+}
+
+bool nbest_dims_ok(int G, int B, int N, int T) {
+  return G >= 1 && G <= SCA_EVAL_MAX_HEADS && B >= 1 && (long)G * B <= 0x7fffffffL / 4 && N >= 1 && N <= DEC_MAX_W &&
+         T >= 1;
+}
+
 bool dec_dims_ok(int B, int T, int C, int W) {
   return B >= 1 && T >= 1 && C >= 1 && C <= SCA_CTC_MAX_C && W >= 1 && W <= SCA_CTC_MAX_BEAM;
 }
@@ -635,8 +855,8 @@ extern "C" int sca_ctc_beam_decode(const float* logits, const int* in_len, int B
   const long rows = (long)B * T;
   sca_ctc_rowstat_launch(logits, w.rowstat, rows, C, st);
   hipLaunchKernelGGL(ctc_topk_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, hx, 1, in_len, d, w);
-  hipLaunchKernelGGL(ctc_beam_kernel, dim3(B), dim3(64), 0, st, hx, in_len, d, collapse_repeats != 0, tokens, out_len,
-                     score, w);
+  hipLaunchKernelGGL(ctc_beam_kernel<false>, dim3(B), dim3(64), 0, st, hx, in_len, d, collapse_repeats != 0, 0, tokens,
+                     out_len, score, static_cast<int*>(nullptr), w);
   if (hipGetLastError() != hipSuccess) { sca_set_error("sca_ctc_beam_decode: launch failed"); return SCA_ERR_LAUNCH; }
   return SCA_OK;
 }
@@ -680,8 +900,8 @@ extern "C" int sca_ctc_beam_decode_heads(const sca_decode_heads* heads, int G, c
   const dim3 row_grid((unsigned)((rows + 3) / 4));
   hipLaunchKernelGGL(ctc_rowstat_heads_kernel, row_grid, dim3(256), 0, st, hx, w.rowstat, rows, (long)B * T, C);
   hipLaunchKernelGGL(ctc_topk_kernel, row_grid, dim3(256), 0, st, hx, G, in_len, d, w);
-  hipLaunchKernelGGL(ctc_beam_kernel, dim3(B, G), dim3(64), 0, st, hx, in_len, d, collapse_repeats != 0, tokens,
-                     out_len, score, w);
+  hipLaunchKernelGGL(ctc_beam_kernel<false>, dim3(B, G), dim3(64), 0, st, hx, in_len, d, collapse_repeats != 0, 0,
+                     tokens, out_len, score, static_cast<int*>(nullptr), w);
   if (hipGetLastError() != hipSuccess) {
     sca_set_error("sca_ctc_beam_decode_heads: launch failed");
     return SCA_ERR_LAUNCH;
@@ -722,5 +942,103 @@ extern "C" int sca_eval_accumulate(const int* tokens, const int* hyp_len, int G,
   hipLaunchKernelGGL(eval_advance_kernel, dim3(1), dim3(64), 0, st, static_cast<const unsigned*>(report), nflags, nloss,
                      B, state);
   if (hipGetLastError() != hipSuccess) { sca_set_error("sca_eval_accumulate: launch failed"); return SCA_ERR_LAUNCH; }
+  return SCA_OK;
+}
+
+extern "C" int sca_ctc_beam_decode_nbest(const float* logits, const int* in_len, int B, int T, int C, int beam_width,
+                                         int nbest, int collapse_repeats, int* tokens, int* out_len, float* score,
+                                         int* count, void* ws, void* stream) {
+  if (!dec_dims_ok(B, T, C, beam_width) || nbest < 1 || nbest > beam_width || !logits || !in_len || !tokens ||
+      !out_len || !score || !count || !ws) {
+    sca_set_error("sca_ctc_beam_decode_nbest: bad arguments (B, T >= 1, 1 <= C <= 8192, "
+                  "1 <= nbest <= beam_width <= 32)");
+    return SCA_ERR_ARG;
+  }
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const DecDims d{B, T, C, beam_width};
+  const DecWs w(ws, d);
+  const DecHeads hx = dec_one_head(logits);
+  const long rows = (long)B * T;
+  sca_ctc_rowstat_launch(logits, w.rowstat, rows, C, st);
+  hipLaunchKernelGGL(ctc_topk_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, hx, 1, in_len, d, w);
+  hipLaunchKernelGGL(ctc_beam_kernel<true>, dim3(B), dim3(64), 0, st, hx, in_len, d, collapse_repeats != 0, nbest,
+                     tokens, out_len, score, count, w);
+  if (hipGetLastError() != hipSuccess) {
+    sca_set_error("sca_ctc_beam_decode_nbest: launch failed");
+    return SCA_ERR_LAUNCH;
+  }
+  return SCA_OK;
+}
+
+extern "C" int sca_ctc_beam_decode_heads_nbest(const sca_decode_heads* heads, int G, const int* in_len, int B, int T,
+                                               int C, int beam_width, int nbest, int collapse_repeats, int* tokens,
+                                               int* out_len, float* score, int* count, void* ws, void* stream) {
+  if (!dec_heads_ok(heads, G, B, T, C, beam_width) || nbest < 1 || nbest > beam_width || !in_len || !tokens ||
+      !out_len || !score || !count || !ws) {
+    sca_set_error("sca_ctc_beam_decode_heads_nbest: bad arguments (1 <= G <= 8 non-null tensors, B, T >= 1, "
+                  "1 <= C <= 8192, 1 <= nbest <= beam_width <= 32)");
+    return SCA_ERR_ARG;
+  }
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const DecDims d{B, T, C, beam_width};
+  const DecWs w(ws, d, G);
+  const DecHeads hx = dec_heads_of(heads, G);
+  const long rows = (long)G * B * T;
+  const dim3 row_grid((unsigned)((rows + 3) / 4));
+  hipLaunchKernelGGL(ctc_rowstat_heads_kernel, row_grid, dim3(256), 0, st, hx, w.rowstat, rows, (long)B * T, C);
+  hipLaunchKernelGGL(ctc_topk_kernel, row_grid, dim3(256), 0, st, hx, G, in_len, d, w);
+  hipLaunchKernelGGL(ctc_beam_kernel<true>, dim3(B, G), dim3(64), 0, st, hx, in_len, d, collapse_repeats != 0, nbest,
+                     tokens, out_len, score, count, w);
+  if (hipGetLastError() != hipSuccess) {
+    sca_set_error("sca_ctc_beam_decode_heads_nbest: launch failed");
+    return SCA_ERR_LAUNCH;
+  }
+  return SCA_OK;
+}
+
+extern "C" int sca_nbest_rescore(const int* tokens, const int* out_len, const float* score, const int* count, int G,
+                                 int B, int N, int T, const float* lm, int C, float lm_weight, float length_bonus,
+                                 float posterior_scale, float* total, float* posterior, int* order, void* stream) {
+  if (!nbest_dims_ok(G, B, N, T) || !tokens || !out_len || !score || !count || !total || !posterior || !order ||
+      (lm && (C < 1 || C > SCA_CTC_MAX_C)) || !(lm_weight - lm_weight == 0.0f) ||
+      !(length_bonus - length_bonus == 0.0f) || !(posterior_scale - posterior_scale == 0.0f)) {
+    sca_set_error("sca_nbest_rescore: bad arguments (1 <= G <= 8, B, T >= 1, 1 <= N <= 32, 1 <= C <= 8192 with a "
+                  "table, finite weights)");
+    return SCA_ERR_ARG;
+  }
+  hipLaunchKernelGGL(nbest_rescore_kernel, dim3((unsigned)(G * B)), dim3(64), 0, reinterpret_cast<hipStream_t>(stream),
+                     tokens, out_len, score, count, N, T, lm, C, lm_weight, length_bonus, posterior_scale, total,
+                     posterior, order);
+  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_nbest_rescore: launch failed"); return SCA_ERR_LAUNCH; }
+  return SCA_OK;
+}
+
+extern "C" int sca_nbest_mbr(const int* tokens, const int* out_len, const int* count, const float* posterior, int G,
+                             int B, int N, int T, int* loss, float* risk, int* best, void* stream) {
+  if (!nbest_dims_ok(G, B, N, T) || T > SCA_WER_MAX_LEN || !tokens || !out_len || !count || !posterior || !loss ||
+      !risk || !best) {
+    sca_set_error("sca_nbest_mbr: bad arguments (1 <= G <= 8, B >= 1, 1 <= N <= 32, 1 <= T <= 128)");
+    return SCA_ERR_ARG;
+  }
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(nbest_loss_kernel, dim3((unsigned)(G * B), (unsigned)(N * N)), dim3(128), 0, st, tokens, out_len,
+                     count, N, T, loss);
+  hipLaunchKernelGGL(nbest_risk_kernel, dim3((unsigned)(G * B)), dim3(64), 0, st, loss, posterior, count, N, risk,
+                     best);
+  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_nbest_mbr: launch failed"); return SCA_ERR_LAUNCH; }
+  return SCA_OK;
+}
+
+extern "C" int sca_nbest_gather(const int* tokens, const int* out_len, const float* value, const int* sel,
+                                int sel_stride, int G, int B, int N, int T, int* tokens1, int* out_len1,
+                                float* value1, void* stream) {
+  if (!nbest_dims_ok(G, B, N, T) || sel_stride < 1 || sel_stride > N || !tokens || !out_len || !value || !sel ||
+      !tokens1 || !out_len1 || !value1) {
+    sca_set_error("sca_nbest_gather: bad arguments (1 <= G <= 8, B, T >= 1, 1 <= N <= 32, 1 <= sel_stride <= N)");
+    return SCA_ERR_ARG;
+  }
+  hipLaunchKernelGGL(nbest_gather_kernel, dim3((unsigned)(G * B)), dim3(64), 0, reinterpret_cast<hipStream_t>(stream),
+                     tokens, out_len, value, sel, sel_stride, N, T, tokens1, out_len1, value1);
+  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_nbest_gather: launch failed"); return SCA_ERR_LAUNCH; }
   return SCA_OK;
 }

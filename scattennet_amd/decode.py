@@ -115,17 +115,26 @@ def ctc_decode(gloss_logits, beam_size, input_lengths):
     return _to_lists(tokens, lengths)
 
 
-def decode_outputs(outputs, beam_size=1, ensembles=None):
+def decode_outputs(outputs, beam_size=1, ensembles=None, rescoring=None):
     """The decoding loop of evaluate_fn (opt.py:76-89): every key of `outputs` that contains
     "gloss_logits" is decoded with outputs["input_lengths"]; the result is keyed by the
     reference's logits_name (the key without "gloss_logits").  `ensembles`
     ({output_key: EnsembleSpec}, ensemble.py) are computed from the logits in `outputs` first and
-    decoded with the rest; `outputs` itself is not modified."""
+    decoded with the rest; `outputs` itself is not modified.  `rescoring` (a `Rescoring`,
+    nbest.py): every tensor's hypothesis is the one selected from its rescored n-best list."""
     if ensembles is not None:
         from .ensemble import add_ensembles, check_ensembles
         outputs = dict(outputs)
         add_ensembles(outputs, check_ensembles((), ensembles, "decode_outputs"))
     il = outputs["input_lengths"]
+    if rescoring is not None:
+        from .nbest import rescored_decode
+        dec = {}
+        for k, v in outputs.items():
+            if "gloss_logits" in k:
+                res = rescored_decode([v], il, beam_size, rescoring, "decode_outputs")
+                dec[k.replace("gloss_logits", "")] = (res["tokens"][0], res["lengths"][0], res["scores"][0])
+        return {k: _to_lists(t, n) for k, (t, n, _) in dec.items()}
     dec = {k.replace("gloss_logits", ""): ctc_decode_device(v, il, beam_size)
            for k, v in outputs.items() if "gloss_logits" in k}
     return {k: _to_lists(t, n) for k, (t, n, _) in dec.items()}

@@ -19,6 +19,9 @@ read until the pass is over.
   captured on its second use and replayed after, and all buckets append to one `EvalState`.
 * `ensembles={output_key: EnsembleSpec}` (ensemble.py) on either: the heads' averaged posterior,
   computed after the forward and decoded, aligned, scored and logged as one more head.
+* `rescoring=Rescoring(...)` (nbest.py) on `eval_step` / `BucketedEvalStep`: the n-best decode, the
+  bigram rescore and the selection ("score" or "mbr") in place of the 1-best decode; the selected
+  hypothesis is aligned, scored and logged like a decoder's.
 
 `{name}wer` keys use the reference's `logits_name` (the output key without "gloss_logits":
 "alignment_", "fuse_coord_").  Hypotheses are class ids; the tokenizer, the results JSON and
@@ -38,6 +41,7 @@ from .encoder import n_pool_of
 from .ensemble import add_ensembles, check_ensembles
 from .heads import _dev_i32, labels_2d
 from .model import _LOGITS, _students_of, deferred_check, first_error, flag_names
+from .nbest import check_rescoring, rescored_decode
 from .precision import fp32_compute
 
 MAX_HEADS = L.EVAL_MAX_HEADS
@@ -323,16 +327,27 @@ def log_alignments(state, spans, conf, scores):
             "sca_eval_log_alignments")
 
 
-def decode_and_align(outputs, keys, ensembles, beam_size, align):
+def decode_and_align(outputs, keys, ensembles, beam_size, align, rescoring=None):
     """The tail `eval_step` and `recognize_step` share, on a forward's `outputs` (modified in
     place): the `ensembles` under their keys, the grouped decode of `keys` with
     outputs["input_lengths"] into `tokens` (G, B, T') / `lengths` (G, B) and, with `align`, the
     forced alignment of every decoded tensor's own hypothesis into `spans` (G, B, T', 2), `conf`
     (G, B, T') and `align_scores` (G, B), both fp32.  Returns the decode's scores (G, B), which the
-    caller may publish.  No host read."""
+    caller may publish.  No host read.
+
+    `rescoring` (a `Rescoring`, nbest.py): the grouped n-best decode, the rescore and, for
+    select="mbr", the MBR selection replace the 1-best decode; `tokens` / `lengths` hold the
+    selected hypothesis, the returned scores its total, and `outputs` gains `nbest_tokens`
+    (G, B, N, T'), `nbest_lengths`, `nbest_totals`, `nbest_posterior`, `nbest_order` (G, B, N)
+    and `nbest_count` (G, B).  None: exactly the calls above, nothing more."""
     add_ensembles(outputs, ensembles)
     logits = [outputs[k] for k in keys]
-    tokens, lengths, scores = ctc_decode_heads_device(logits, outputs["input_lengths"], beam_size)
+    if rescoring is not None:
+        res = rescored_decode(logits, outputs["input_lengths"], beam_size, rescoring, "decode_and_align")
+        tokens, lengths, scores = res.pop("tokens"), res.pop("lengths"), res.pop("scores")
+        outputs.update(res)
+    else:
+        tokens, lengths, scores = ctc_decode_heads_device(logits, outputs["input_lengths"], beam_size)
     outputs["tokens"], outputs["lengths"] = tokens, lengths
     if align:
         res = ctc_align_heads_device(logits, outputs["input_lengths"], tokens, lengths)
@@ -340,7 +355,7 @@ def decode_and_align(outputs, keys, ensembles, beam_size, align):
     return scores
 
 
-def eval_step(model, src_input, state, beam_size=5):
+def eval_step(model, src_input, state, beam_size=5, rescoring=None):
     """One evaluation step of MSCA_Net, enqueued on the current stream without a host read:
     forward under no_grad with the finite check deferred (a `model.check` of "off" is kept),
     the grouped decode of `state.heads` with outputs["input_lengths"] (`beam_size=0`: greedy),
@@ -356,13 +371,19 @@ def eval_step(model, src_input, state, beam_size=5):
     `ensemble_log_probs`), put in the outputs under its key and decoded, aligned, scored and
     logged as one more head after the plain ones: G = len(state.keys).
 
+    With `rescoring` (a `Rescoring`, nbest.py), the n-best decode, the rescore and the selection
+    replace the 1-best decode: `tokens` / `lengths` are the selected hypotheses, which are aligned,
+    scored and logged as above, and the outputs also hold the `nbest_*` tensors of
+    `decode_and_align`.
+
     The model's `training` flag is left as it is: put the model in `eval()` first."""
+    check_rescoring(rescoring, beam_size, "eval_step")
     with torch.no_grad():
         with deferred_check(model):
             outputs = model(src_input)
         if _students_of(outputs) != state.students:
             raise ValueError("eval_step: the model's distillation terms differ from the state's")
-        decode_and_align(outputs, state.keys, state.ensembles, beam_size, state.align)
+        decode_and_align(outputs, state.keys, state.ensembles, beam_size, state.align, rescoring)
         tokens, lengths = outputs["tokens"], outputs["lengths"]
         ref, ref_len = _references(src_input, tokens.shape[1], tokens.device)
         if state.align:
@@ -406,13 +427,15 @@ class BucketedEvalStep(BucketedStep):
     Returns the step's outputs, the logits, `tokens` (and `spans`, `conf`) trimmed (views) to the batch's own
     T >> n_pool frames; they are views of the bucket's static outputs, valid until the next
     `step`.  The model must be in `eval()`; a bucket's pooled length and `label_bucket` may not
-    exceed 128 (the WER matrix)."""
+    exceed 128 (the WER matrix).  `rescoring` is `eval_step`'s; the `nbest_tokens` it adds are
+    trimmed like `tokens`."""
 
     def __init__(self, model, batch_size, frame_buckets, label_bucket, beam_size=5, heads=None, capacity=0,
-                 align=False, ensembles=None):
+                 align=False, ensembles=None, rescoring=None):
         super().__init__(model, batch_size, frame_buckets, label_bucket)
         _check_wer_limits(self.frame_buckets, self.n_pool, label_bucket)
         self.beam_size = int(beam_size)
+        self.rescoring = check_rescoring(rescoring, self.beam_size, "BucketedEvalStep")
         self.state = EvalState(model, heads, capacity, self.frame_buckets[-1] >> self.n_pool, align, ensembles)
 
     def read(self):
@@ -428,7 +451,7 @@ class BucketedEvalStep(BucketedStep):
         return self.state.device
 
     def _run(self, src):
-        return eval_step(self.model, src, self.state, self.beam_size)
+        return eval_step(self.model, src, self.state, self.beam_size, self.rescoring)
 
     def _trimmed_keys(self):
         return tuple(self.state.ensembles)

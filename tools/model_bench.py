@@ -45,6 +45,9 @@ whole passes in alternated windows, ms per batch and the per-window difference.
 
 --ensemble (with --mixed --eval): the same pair, one with an ensemble of the five heads decoded
 after the two default heads; asserts that the default heads' totals and hypotheses are identical.
+
+--rescore N[:score|mbr] (with --mixed --eval): the same pair, one with rescoring=Rescoring(N, a random
+bigram table, lm_weight 0.5, length_bonus 0.2, select) in place of the 1-best decode.
 """
 import argparse
 import json
@@ -378,6 +381,47 @@ def eval_ensemble(a, dev):
     print(json.dumps(res))
 
 
+def eval_rescore(a, dev):
+    """--mixed --eval --rescore: the bucketed evaluation pass with the 1-best decode and with the
+    n-best decode, bigram rescore and selection in its place, both with a hypothesis log of the
+    whole pass, in alternated windows."""
+    import scattennet_amd as S
+    model, _, w, _ = build(a, dev)
+    model.check = "defer"
+    n_pool = (len(w["residual_blocks"]) + 1) // 2
+    batches = mixed_batches(a, w, dev, n_pool)
+    buckets = tuple(int(b) for b in a.buckets.split(","))
+    capacity = a.batches * a.B
+    n, _, select = a.rescore.partition(":")
+    lm = S.BigramLM(torch.log_softmax(torch.randn(a.C, a.C, generator=torch.Generator().manual_seed(a.seed)) * 2, -1),
+                    device=dev)
+    spec = S.Rescoring(int(n), lm, 0.5, 0.2, select=select or "score")
+    steps = {"plain": S.BucketedEvalStep(model, a.B, buckets, a.S, beam_size=a.beam, capacity=capacity),
+             "rescored": S.BucketedEvalStep(model, a.B, buckets, a.S, beam_size=a.beam, capacity=capacity,
+                                            rescoring=spec)}
+    g = torch.Generator().manual_seed(a.seed + 1)
+    for bes in steps.values():
+        capture_all(bes, batches, lambda f: _batch(a, w, dev, g, [f] * a.B, n_pool)[0], bes.state.reset)
+    ms, results = {k: [] for k in steps}, {}
+    for _ in range(a.windows):  # alternated windows
+        for k, bes in steps.items():
+            bes.state.reset()
+            ms[k].append(_pass(bes.step, batches))
+            results[k] = bes.read()  # the pass's one host read (after the timed window's synchronise)
+    hyps = {k: bes.hypotheses() for k, bes in steps.items()}
+    changed = sum(x != y for x, y in zip(hyps["plain"], hyps["rescored"]))
+    diff = [x - y for x, y in zip(ms["rescored"], ms["plain"])]
+    res = {"workload": "MSCA_Net bucketed evaluation pass over a mixed-length stream, with the 1-best decode and with "
+                       "the n-best decode, bigram rescore and selection in its place (both log the hypotheses)",
+           "B": a.B, "max_len": a.T, "C": a.C, "S": a.S, "beam": a.beam, "nbest": spec.nbest, "select": spec.select,
+           "seed": a.seed, "buckets": list(buckets), "batch_lengths": [T for _, T in batches],
+           "plain_ms_per_batch": _spread(ms["plain"]), "rescored_ms_per_batch": _spread(ms["rescored"]),
+           "rescored_minus_plain_ms_per_batch": _spread(diff), "clips": len(hyps["plain"]),
+           "clips_with_another_hypothesis": changed,
+           "results": {k: round(v, 4) for k, v in results["rescored"].items()}}
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=8)
@@ -395,6 +439,8 @@ def main():
                                                          "the forced alignment of every hypothesis")
     ap.add_argument("--ensemble", action="store_true", help="with --mixed --eval: the bucketed pass with and without "
                                                             "one five-member ensemble beside the two default heads")
+    ap.add_argument("--rescore", default=None, help="with --mixed --eval: N[:score|mbr], the bucketed pass with and "
+                                                    "without the rescored n-best decode")
     ap.add_argument("--beam", type=int, default=5)
     ap.add_argument("--batches", type=int, default=20)
     ap.add_argument("--buckets", default="64,128,192,256")
@@ -410,6 +456,8 @@ def main():
             return eval_align(a, dev)
         if a.eval and a.ensemble:
             return eval_ensemble(a, dev)
+        if a.eval and a.rescore:
+            return eval_rescore(a, dev)
         return eval_mixed(a, dev) if a.eval else mixed(a, dev)
     model, src, w, t4 = build(a, dev)
     graphs = {k: capture(model, src, k, dev) for k in ("off", "defer")}

@@ -1,0 +1,75 @@
+"""Time the second pass over the CTC beam search (scattennet_amd/nbest.py) on one MI355X at the
+evaluation shape of the 2014T yaml (B = 8, T/4 = 64, C = 1124): the n-best decode, the bigram
+rescore, the MBR selection and the whole chain (decode, rescore, MBR, gather), beside the 1-best
+beam decode of the same build at the same beam.  Two configurations: beam 5 with N = 5 (main.py's
+beam) and beam 32 with N = 32 (the widest list).  Each op is timed two ways, as in
+tools/decode_bench.py: eager calls (Python, allocator and launch overhead included) and replays
+of a captured graph (device time of the launches only).  Both windows end in a device
+synchronise; the figure is the median of --repeats windows of --steps calls, with the spread
+(min, max) beside it.  Synthetic logits N(0, 4^2), full-length clips (the longest dependent
+chain), a random normalised bigram table.  Needs a GPU.
+
+Usage: python tools/nbest_bench.py [--B 8] [--T 64] [--C 1124] [--configs 5:5,32:32] [--steps 200]
+
+The 1-best decode of another build (the parent commit's library, SCA_LIB_PATH) is timed by
+tools/decode_bench.py --beam W in the same session; this tool only runs the build it imports.
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from tools.decode_bench import graphed, windows  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--B", type=int, default=8)
+    ap.add_argument("--T", type=int, default=64)
+    ap.add_argument("--C", type=int, default=1124)
+    ap.add_argument("--configs", default="5:5,32:32", help="beam:nbest pairs")
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--repeats", type=int, default=5)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("nbest_bench: needs a GPU; nothing is measured without one")
+    import scattennet_amd as S
+    dev = torch.device("cuda")
+    g = torch.Generator().manual_seed(0)
+    x = (torch.randn(a.B, a.T, a.C, generator=g) * 4).to(dev)
+    il = torch.full((a.B,), a.T, dtype=torch.int32, device=dev)
+    lm = S.BigramLM(torch.log_softmax(torch.randn(a.C, a.C, generator=g) * 2, -1), device=dev)
+    res = {"workload": "n-best CTC decode, bigram rescore, MBR", "B": a.B, "T": a.T, "C": a.C, "steps": a.steps,
+           "repeats": a.repeats, "unit": "us per call: [median, min, max]", "configs": {}}
+    for pair in a.configs.split(","):
+        W, N = (int(v) for v in pair.split(":"))
+        nb = S.ctc_decode_nbest_device(x, il, W, N)
+        total, post, order = S.rescore_nbest_device(nb, lm, 0.5, 0.2)
+        spec = S.Rescoring(N, lm, 0.5, 0.2, select="mbr")
+        ops = {
+            "beam_1best": lambda: S.ctc_decode_device(x, il, W),
+            "beam_nbest": lambda: S.ctc_decode_nbest_device(x, il, W, N),
+            "rescore": lambda: S.rescore_nbest_device(nb, lm, 0.5, 0.2),
+            "mbr": lambda: S.mbr_select_device(nb, post),
+            "chain": lambda: S.rescored_decode([x], il, W, spec),
+        }
+        out = {"merged_count_mean": round(float(nb.count.float().mean()), 2)}
+        for name, fn in ops.items():
+            for _ in range(a.warmup):
+                fn()
+            out[name + "_eager"] = windows(fn, a.steps, a.repeats)
+            replay = graphed(fn)
+            for _ in range(a.warmup):
+                replay()
+            out[name + "_graph"] = windows(replay, a.steps, a.repeats)
+        res["configs"][f"beam{W}_n{N}"] = out
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
