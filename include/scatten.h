@@ -722,6 +722,56 @@ int sca_nbest_mbr(const int* tokens, const int* out_len, const int* count, const
 int sca_nbest_gather(const int* tokens, const int* out_len, const float* value, const int* sel, int sel_stride,
                      int G, int B, int N, int T, int* tokens1, int* out_len1, float* value1, void* stream);
 
+/* ---- evaluation: shallow fusion of the bigram gloss model into the beam search --------------
+ * sca_ctc_beam_decode_fused_nbest / sca_ctc_beam_decode_heads_fused_nbest: the search of
+ * sca_ctc_beam_decode_nbest with one change: what a beam is ranked by.  lm: NULL, or the dense
+ * (C, C) fp32 table of sca_nbest_rescore (class 0 is the sentence boundary), C the logits'.
+ * Every prefix p carries a bonus that depends on the prefix only:
+ *   g(empty) = 0
+ *   g(q + c) = g(q) + lm_weight * lm[last(q) (0 for the empty prefix), c] + length_bonus
+ *   lb, ll, total, the update rule, the parent-merge rule and the candidate rule are unchanged
+ *     and purely acoustic.  Two paths to the same prefix have the same g, so merging stays well
+ *     defined, and a pruned prefix that comes back takes its arena node again.
+ *   Per-frame cut: the beam_width best of updated beams and candidates by
+ *     key = total + g(prefix); ties as in the unfused search: updated beams first, then the
+ *     lower slot, then the lower class.
+ *   After the last frame the beams are ordered by
+ *     final key = total + g(p) + lm_weight * lm[last(p) (0 if empty), 0], ties to the lower slot:
+ *     exactly the total sca_nbest_rescore computes for the uncollapsed entry with the same
+ *     table, weight and bonus.  Entry n of the list is the n-th beam in that order.
+ *   The outputs keep the n-best entry's format and meaning: score is the acoustic
+ *     offset + total_n, not the key; tokens, out_len and count are as there.  With
+ *     collapse_repeats the tail of sca_ctc_beam_decode_nbest (collapse, merge by logaddexp of the
+ *     acoustic scores, stable re-sort by score) runs unchanged on that list.  sca_nbest_rescore,
+ *     sca_nbest_mbr, sca_nbest_gather, the aligner and sca_eval_accumulate take the result as
+ *     they take the unfused list's, and the rescorer with the same arguments turns the scores
+ *     into the totals the search ranked by.
+ *   lm = NULL means lm(.) = 0: the search is guided by the length bonus only.  With
+ *     lm_weight = 0 and length_bonus = 0 every output is bitwise
+ *     sca_ctc_beam_decode_heads_nbest's.  Specified for finite tables and finite weights of
+ *     either sign; in_len = 0 gives count 1, the empty hypothesis, score 0.
+ * A beam's candidates come from the W + 1 labels with the largest lp[c] + lm_weight * lm[last, c]
+ * (ties to the lower class), selected per beam and frame over the whole row: the frame's shared
+ * top-(W + 1) by lp is not exact once the order depends on the beam's last label.  At least W of
+ * those labels differ from the beam's last label, and each of them has an item in the pool that
+ * is no worse than any label left out, so the cut is the cut over all C - 1 labels.
+ * g is carried relative to the best beam's, as the totals are.  Limits: those of the beam
+ * decoder (1 <= nbest <= beam_width <= 32, C <= 8192).  ws: sca_ctc_fused_workspace_bytes(G, B,
+ * T, C, W) bytes (0 for unsupported sizes; G = 1 for the single-head form), 8-byte aligned.  Two
+ * launches (row statistics, frame recursion); no float atomics, deterministic, a replayed
+ * capture is bitwise the eager call and head g of a grouped call is bitwise the single-head
+ * call; nothing allocates, copies or synchronises, and arguments are validated before any GPU
+ * call.                                                                                      */
+long sca_ctc_fused_workspace_bytes(int G, int B, int T, int C, int W);
+int sca_ctc_beam_decode_fused_nbest(const float* logits, const int* in_len, int B, int T, int C, int beam_width,
+                                    int nbest, int collapse_repeats, const float* lm, float lm_weight,
+                                    float length_bonus, int* tokens, int* out_len, float* score, int* count,
+                                    void* ws, void* stream);
+int sca_ctc_beam_decode_heads_fused_nbest(const sca_decode_heads* heads, int G, const int* in_len, int B, int T,
+                                          int C, int beam_width, int nbest, int collapse_repeats, const float* lm,
+                                          float lm_weight, float length_bonus, int* tokens, int* out_len,
+                                          float* score, int* count, void* ws, void* stream);
+
 /* ---- evaluation: CTC forced alignment (gloss spans and confidences) -----------------------
  * The best single path of G heads' logits through given label sequences: for every (head g,
  * clip b) the frames at which each label is emitted.  Logits as for the decoders (fp32

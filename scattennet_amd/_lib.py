@@ -223,6 +223,11 @@ EXPORTS = {
     "sca_ctc_beam_decode_heads": ([c_void_p, c_int, c_void_p] + [c_int] * 5 + [c_void_p] * 5, c_int),
     "sca_ctc_beam_decode_nbest": ([c_void_p, c_void_p] + [c_int] * 6 + [c_void_p] * 6, c_int),
     "sca_ctc_beam_decode_heads_nbest": ([c_void_p, c_int, c_void_p] + [c_int] * 6 + [c_void_p] * 6, c_int),
+    "sca_ctc_fused_workspace_bytes": ([c_int] * 5, c_long),
+    "sca_ctc_beam_decode_fused_nbest": ([c_void_p, c_void_p] + [c_int] * 6 + [c_void_p, c_float, c_float] +
+                                        [c_void_p] * 6, c_int),
+    "sca_ctc_beam_decode_heads_fused_nbest": ([c_void_p, c_int, c_void_p] + [c_int] * 6 +
+                                              [c_void_p, c_float, c_float] + [c_void_p] * 6, c_int),
     "sca_nbest_rescore": ([c_void_p] * 4 + [c_int] * 4 + [c_void_p, c_int] + [c_float] * 3 + [c_void_p] * 4, c_int),
     "sca_nbest_mbr": ([c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 4, c_int),
     "sca_nbest_gather": ([c_void_p] * 4 + [c_int] * 5 + [c_void_p] * 4, c_int),

@@ -28,6 +28,8 @@ constexpr int DEC_MAX_W = SCA_CTC_MAX_BEAM;
 constexpr int DEC_MAX_ITEMS = DEC_MAX_W * (DEC_MAX_W + 1) + DEC_MAX_W;  // candidates + updated beams
 constexpr int KEY_CAND = 64;                                             // keys below: updated beams
 constexpr int DEC_ARENA_LDS = 2048;                                      // arena nodes mirrored in LDS
+constexpr int DEC_FUSE_LIST = 256;  // fused search: labels above the threshold that the rank count merges
+constexpr int DEC_FUSE_CHUNK = 24;  // fused search: labels per lane loaded together (64 * 24 >= 1124 - 1)
 
 struct DecDims {
   int B, T, C, W;
@@ -66,6 +68,12 @@ struct DecWs {
 
 __device__ __forceinline__ float dec_lp(float x, float m, float ls) { return (x - m) - ls; }
 
+// The bigram model of the fused search (sca_ctc_beam_decode_fused_nbest): lm (C, C) or NULL.
+struct DecLm {
+  const float* lm;
+  float weight, bonus;
+};
+
 __device__ __forceinline__ float logaddexp(float a, float b) {
   const float hi = fmaxf(a, b), lo = fminf(a, b);
   if (lo == NEG_INF) return hi;
@@ -100,6 +108,29 @@ __device__ __forceinline__ unsigned long long dec_ord(float v, int key) {
   unsigned u = __float_as_uint(v + 0.0f);
   u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
   return ((unsigned long long)u << 32) | (unsigned)(NONE - key);
+}
+__device__ __forceinline__ int dec_ord_key(unsigned long long o) { return NONE - (int)(unsigned)(o & 0xffffffffull); }
+
+// What a beam of the fused search ranks a label by: lp[c] + weight * lm[last, c], one rounding,
+// the same value wherever it is evaluated.  lp and the bigram term go out as they enter the
+// candidate.  fuse_ord: the same from the rows (row NULL: no table), as a dec_ord word with c.
+__device__ __forceinline__ float fuse_key(float xv, float lmv, float weight, float m, float ls, float& lp, float& bg) {
+  lp = dec_lp(xv, m, ls);
+  bg = weight * lmv;
+  return __fmaf_rn(weight, lmv, lp);
+}
+__device__ __forceinline__ unsigned long long fuse_ord(const float* __restrict__ xr, const float* __restrict__ row,
+                                                        float weight, int c, float m, float ls, float& lp, float& bg) {
+  return dec_ord(fuse_key(xr[c], row ? row[c] : 0.0f, weight, m, ls, lp, bg), c);
+}
+
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long w = __shfl_xor(v, o, 64);
+    v = w > v ? w : v;
+  }
+  return v;
 }
 
 // an arena node, and a beam's identity as "child of node par by label lab", as one word
@@ -187,11 +218,34 @@ __global__ __launch_bounds__(256) void ctc_topk_kernel(DecHeads hx, int G, const
 // (the per-frame best labels are dead once the loop is over, and nbest T <= T (W + 1) ints),
 // equal entries merge into the first of them, a rank count re-sorts, and the wave writes the
 // (nbest, T) rows out.  tokens (nbest, T), out_len / score (nbest) and count (1) per clip.
-template <bool NBEST>
+//
+// FUSED (with NBEST): shallow fusion, sca_ctc_beam_decode_fused_nbest.  Every beam carries
+// g(prefix), relative to slot 0's like the totals; items are ranked by total + g and the slots
+// stay sorted by that key.  The frame's shared label list is not exact under a bigram term, so
+// every beam selects its own K labels by lp[c] + weight * lm[last, c] (fuse_ord) over the whole
+// row: the lanes stride over the row and keep their maximum, the K-th largest of the 64 maxima
+// is a threshold that at least K labels reach, and only labels of the lanes whose maximum
+// reaches it can.  A second pass over the row appends those labels to an LDS list by ballot, and
+// a rank count over the list's (value, class) words yields the K best in order.  A list longer than DEC_FUSE_LIST (K
+// lanes full of large values) falls back to K rounds of wave arg-max, ctc_topk_kernel's method.
+// Both are exact, so with weight 0 and bonus 0 the item pool, and every output, is bitwise the
+// unfused instantiation's.  After the last frame a rank count orders the beams by the final key
+// (the closing bigram included) and the tail takes entry n from beam p_src[n].  The unfused
+// instantiations contain none of this: every fused statement is under `if constexpr`.
+template <bool NBEST, bool FUSED = false>
 __global__ __launch_bounds__(64) void ctc_beam_kernel(DecHeads hx, const int* __restrict__ in_len, DecDims d,
                                                       int collapse, int nbest, int* __restrict__ tokens,
                                                       int* __restrict__ out_len, float* __restrict__ score,
-                                                      int* __restrict__ count, DecWs w) {
+                                                      int* __restrict__ count, DecWs w, DecLm f) {
+  static_assert(NBEST || !FUSED, "the fused search has the n-best tail only");
+  constexpr int FW = FUSED ? DEC_MAX_W : 1, FI = FUSED ? DEC_MAX_ITEMS : 1, FL = FUSED ? DEC_FUSE_LIST : 1;
+  __shared__ float s_g[2][FW], it_g[FI];       // g of the beams and of the items
+  __shared__ int it_cls[FI];                   // an item's label
+  __shared__ float l_max[FUSED ? 64 : 1];      // the lanes' maxima
+  __shared__ unsigned long long f_key[FW], l_ord[FL];  // the final keys; one beam's list
+  __shared__ float l_lp[FL], l_bg[FL];
+  __shared__ int pk_cls[FW + 1], p_src[FW];    // one beam's K labels; the final order
+  __shared__ float pk_lp[FW + 1], pk_bg[FW + 1];
   __shared__ int s_node[2][DEC_MAX_W], s_lab[2][DEC_MAX_W], s_par[2][DEC_MAX_W];
   __shared__ float s_lb[2][DEC_MAX_W], s_ll[2][DEC_MAX_W], s_tot[2][DEC_MAX_W];
   __shared__ float s_xe[2][DEC_MAX_W];  // this frame's logit of the beam's last label
@@ -222,9 +276,11 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(DecHeads hx, const int* __
     pm = w.rowstat[2 * row];
     pls = w.rowstat[2 * row + 1];
     px0 = x[(long)t * C];
-    if (lane < K) {
-      pcls = w.cls[row * KS + lane];
-      pclp = w.clp[row * KS + lane];
+    if constexpr (!FUSED) {
+      if (lane < K) {
+        pcls = w.cls[row * KS + lane];
+        pclp = w.clp[row * KS + lane];
+      }
     }
   };
   if (Tb > 0) prefetch(0);
@@ -233,17 +289,22 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(DecHeads hx, const int* __
     a_lds[0] = dec_pl(-1, 0);
     s_node[0][0] = 0; s_lab[0][0] = 0; s_par[0][0] = -1; s_pl[0][0] = dec_pl(-1, 0);
     s_lb[0][0] = 0.0f; s_ll[0][0] = NEG_INF; s_tot[0][0] = 0.0f; s_xe[0][0] = 0.0f;
+    if constexpr (FUSED) s_g[0][0] = 0.0f;
   }
   __syncthreads();
   for (int t = 0; t < Tb; ++t) {
     const float m = pm, ls = pls, lp0 = dec_lp(px0, pm, pls);
     const int nxt = cur ^ 1;
-    if (lane < K) { f_cls[lane] = pcls; f_clp[lane] = pclp; }
+    if constexpr (!FUSED) {
+      if (lane < K) { f_cls[lane] = pcls; f_clp[lane] = pclp; }
+    }
     if (lane < W) sel[lane] = -1;
     float nxc = 0.0f, nxb = 0.0f;
     if (t + 1 < Tb) {  // wave-uniform
       const float* xn = x + (long)(t + 1) * C;
-      if (lane < K) nxc = xn[pcls];
+      if constexpr (!FUSED) {
+        if (lane < K) nxc = xn[pcls];
+      }
       if (lane < nb) nxb = xn[s_lab[cur][lane]];
       prefetch(t + 1);
     }
@@ -265,11 +326,107 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(DecHeads hx, const int* __
       u_lb[lane] = nlb;
       u_ll[lane] = nll;
       it_val[lane] = tot;
-      it_ord[lane] = dec_ord(tot, lane);
+      if constexpr (FUSED) it_ord[lane] = dec_ord(tot + s_g[cur][lane], lane);
+      else it_ord[lane] = dec_ord(tot, lane);
+    }
+    const int M = nb + nb * K;
+    if constexpr (FUSED) {
+      // extension candidates: beam j x its own K best labels by lp + weight * lm[last(j), .]
+      const float* __restrict__ xr = x + (long)t * C;
+      for (int j = 0; K > 0 && j < nb; ++j) {  // wave-uniform
+        const int lj = s_lab[cur][j];          // 0 for the empty prefix: the sentence boundary
+        const float* __restrict__ row = f.lm ? f.lm + (long)lj * C : nullptr;
+        // A chunk is DEC_FUSE_CHUNK labels per lane, loaded together (one trip to L1 / L2, not one
+        // per label; past the row's end the last label again, masked below) and kept in registers;
+        // a row that fits one chunk is loaded once for both passes.
+        float lp, bg;
+        float cv[DEC_FUSE_CHUNK], clp[DEC_FUSE_CHUNK], cbg[DEC_FUSE_CHUNK];
+        auto load_chunk = [&](int c0) {
+          float xv[DEC_FUSE_CHUNK], lv[DEC_FUSE_CHUNK];
+#pragma unroll
+          for (int u = 0; u < DEC_FUSE_CHUNK; ++u) xv[u] = xr[min(c0 + lane + 64 * u, C - 1)];
+#pragma unroll
+          for (int u = 0; u < DEC_FUSE_CHUNK; ++u) lv[u] = row ? row[min(c0 + lane + 64 * u, C - 1)] : 0.0f;
+#pragma unroll
+          for (int u = 0; u < DEC_FUSE_CHUNK; ++u) cv[u] = fuse_key(xv[u], lv[u], f.weight, m, ls, clp[u], cbg[u]);
+        };
+        const bool one_chunk = C - 1 <= 64 * DEC_FUSE_CHUNK;
+        float top = NEG_INF;  // the lane's largest value
+        for (int c0 = 1; c0 < C; c0 += 64 * DEC_FUSE_CHUNK) {  // wave-uniform
+          load_chunk(c0);
+#pragma unroll
+          for (int u = 0; u < DEC_FUSE_CHUNK; ++u) top = (c0 + lane + 64 * u < C && cv[u] > top) ? cv[u] : top;
+        }
+        l_max[lane] = top;
+        lds_barrier();
+        // A threshold that at least K labels reach: the smallest maximum among the lanes with fewer
+        // than K maxima strictly above theirs (the K largest maxima are among them).  Every label
+        // of the K best reaches it too, so the list below is a superset of them; ties only add to it.
+        int above = 0;
+#pragma unroll 16
+        for (int i = 0; i < 64; ++i) above += l_max[i] > top;
+        const float tau = -wave_max(above < K ? -top : NEG_INF);
+        int cnt = 0;
+        for (int c0 = 1; c0 < C; c0 += 64 * DEC_FUSE_CHUNK) {  // wave-uniform
+          if (!one_chunk) load_chunk(c0);
+#pragma unroll
+          for (int u = 0; u < DEC_FUSE_CHUNK; ++u) {
+            const int c = c0 + lane + 64 * u;
+            const bool in = c < C && cv[u] >= tau;
+            const unsigned long long mask = __ballot(in);
+            if (mask == 0ull) continue;  // wave-uniform: most strides hold no such label
+            const int pos = cnt + __popcll(mask & ((1ull << lane) - 1ull));
+            if (in && pos < DEC_FUSE_LIST) { l_ord[pos] = dec_ord(cv[u], c); l_lp[pos] = clp[u]; l_bg[pos] = cbg[u]; }
+            cnt += __popcll(mask);
+          }
+        }
+        lds_barrier();
+        if (cnt <= DEC_FUSE_LIST) {  // wave-uniform
+          for (int n = lane; n < cnt; n += 64) {
+            const unsigned long long mine = l_ord[n];
+            int rank = 0;
+#pragma unroll 4
+            for (int i = 0; i < cnt; ++i) rank += l_ord[i] > mine;
+            if (rank < K) { pk_cls[rank] = dec_ord_key(mine); pk_lp[rank] = l_lp[n]; pk_bg[rank] = l_bg[n]; }
+          }
+        } else {  // round k: the best label strictly behind round k - 1's
+          unsigned long long prev = ~0ull;
+          for (int k = 0; k < K; ++k) {
+            unsigned long long best = 0ull;
+            for (int c = 1 + lane; c < C; c += 64) {
+              const unsigned long long o = fuse_ord(xr, row, f.weight, c, m, ls, lp, bg);
+              best = (o < prev && o > best) ? o : best;
+            }
+            best = wave_max_u64(best);
+            if (lane == 0) {
+              const int c = clampi(dec_ord_key(best), 1, C - 1);  // best != 0: K <= C - 1 labels exist
+              fuse_ord(xr, row, f.weight, c, m, ls, lp, bg);
+              pk_cls[k] = c; pk_lp[k] = lp; pk_bg[k] = bg;
+            }
+            prev = best;
+          }
+        }
+        lds_barrier();
+        if (lane < K) {
+          const int c = clampi(pk_cls[lane], 1, C - 1);  // a NaN logit cannot carry it out of the row
+          float v = NEG_INF;
+          const unsigned long long qc = dec_pl(s_node[cur][j], c);
+          bool active = false;
+#pragma unroll 4
+          for (int i = 0; i < nb; ++i) active |= s_pl[cur][i] == qc;
+          if (!active) v = pk_lp[lane] + (c == lj ? s_lb[cur][j] : s_tot[cur][j]);
+          const float gn = s_g[cur][j] + pk_bg[lane] + f.bonus;
+          const int n = nb + j * K + lane;
+          it_val[n] = v;
+          it_g[n] = gn;
+          it_cls[n] = c;
+          it_ord[n] = v == NEG_INF ? 0ull : dec_ord(v + gn, KEY_CAND + j * SCA_CTC_MAX_C + c);  // -inf: dropped
+        }
+        lds_barrier();
+      }
     }
     // extension candidates: beam j x the frame's k-th best label
-    const int M = nb + nb * K;
-    for (int n = lane; n < nb * K; n += 64) {
+    for (int n = lane; !FUSED && n < nb * K; n += 64) {
       const int j = n / K, k = n - j * K;
       const int c = f_cls[k];
       float v = NEG_INF;
@@ -294,13 +451,16 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(DecHeads hx, const int* __
       for (int i = 0; i < M; ++i) rank += it_ord[i] > mine;
       if (rank < W) sel[rank] = n;
     }
-    if (lane < K) n_xc[lane] = nxc;
+    if constexpr (!FUSED) {
+      if (lane < K) n_xc[lane] = nxc;
+    }
     if (lane < nb) n_xb[lane] = nxb;
     lds_barrier();
     const int R = __popcll(__ballot(lane < W && sel[lane < W ? lane : 0] >= 0));
     // the new beam set, in selection order
     int node = -1, lab = 0, par = -1;
     float lb = NEG_INF, ll = NEG_INF, tot = NEG_INF, xe = 0.0f;
+    [[maybe_unused]] float g = 0.0f;
     bool fresh = false;
     if (lane < R) {
       const int idx = max(sel[lane], 0);  // ranks are a permutation unless a total is NaN: stay in bounds
@@ -309,12 +469,19 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(DecHeads hx, const int* __
         node = s_node[cur][idx]; lab = s_lab[cur][idx]; par = s_par[cur][idx];
         lb = u_lb[idx]; ll = u_ll[idx];
         xe = n_xb[idx];
+        if constexpr (FUSED) g = s_g[cur][idx];
       } else {
         const int n = idx - nb, j = n / K, k = n - j * K;
         par = s_node[cur][j];
-        lab = f_cls[k];
+        if constexpr (FUSED) {  // the label is the beam's own pick: its next logit could not be asked for earlier
+          lab = it_cls[idx];
+          g = it_g[idx];
+          if (t + 1 < Tb) xe = x[(long)(t + 1) * C + lab];
+        } else {
+          lab = f_cls[k];
+          xe = n_xc[k];
+        }
         ll = tot;
-        xe = n_xc[k];
         fresh = true;
       }
       s_par[nxt][lane] = par;
@@ -364,9 +531,11 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(DecHeads hx, const int* __
       offset += (double)shift;
       lb -= shift; ll -= shift; tot -= shift;
     }
+    if constexpr (FUSED) g -= __shfl(g, 0, 64);  // only differences of g are ever compared
     if (lane < R) {
       s_node[nxt][lane] = node;
       s_lb[nxt][lane] = lb; s_ll[nxt][lane] = ll; s_tot[nxt][lane] = tot; s_xe[nxt][lane] = xe;
+      if constexpr (FUSED) s_g[nxt][lane] = g;
     }
     nb = R;
     cur = nxt;
@@ -381,10 +550,27 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(DecHeads hx, const int* __
     __shared__ unsigned long long e_hash[DEC_MAX_W];
     const int N = nbest, n0 = min(N, nb);
     int* stage = w.cls + (long)slot * T * KS;  // row n: entry n's labels
+    if constexpr (FUSED) {  // the final key adds the closing bigram: order the beams once more
+      unsigned long long mine = 0ull;
+      if (lane < nb) {
+        const float close = f.lm ? f.weight * f.lm[(long)s_lab[cur][lane] * C] : 0.0f;
+        mine = dec_ord(s_tot[cur][lane] + s_g[cur][lane] + close, lane);
+        f_key[lane] = mine;
+      }
+      lds_barrier();
+      if (lane < nb) {
+        int rank = 0;
+        for (int i = 0; i < nb; ++i) rank += f_key[i] > mine;
+        p_src[rank] = lane;
+      }
+      lds_barrier();
+    }
     int len = 0;
     if (lane < n0) {  // the active beams are in descending order of total: entry n is beam n
       auto node_at = [&](int n) { return n < DEC_ARENA_LDS ? a_lds[n] : arena[n]; };
-      const int leaf = s_node[cur][lane];
+      int beam = lane;
+      if constexpr (FUSED) beam = p_src[lane];
+      const int leaf = s_node[cur][beam];
       for (int n = leaf; len < Tb && dec_par(node_at(n)) >= 0; n = dec_par(node_at(n))) ++len;
       int* row = stage + (long)lane * T;
       int n = leaf;
@@ -408,7 +594,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(DecHeads hx, const int* __
       }
       e_len[lane] = len;
       e_hash[lane] = h;
-      e_sc[lane] = (float)(offset + (double)s_tot[cur][lane]);
+      e_sc[lane] = (float)(offset + (double)s_tot[cur][beam]);
     }
     __syncthreads();  // the staged rows are read by other lanes below
     bool keep = lane < n0;
@@ -856,7 +1042,7 @@ extern "C" int sca_ctc_beam_decode(const float* logits, const int* in_len, int B
   sca_ctc_rowstat_launch(logits, w.rowstat, rows, C, st);
   hipLaunchKernelGGL(ctc_topk_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, hx, 1, in_len, d, w);
   hipLaunchKernelGGL(ctc_beam_kernel<false>, dim3(B), dim3(64), 0, st, hx, in_len, d, collapse_repeats != 0, 0, tokens,
-                     out_len, score, static_cast<int*>(nullptr), w);
+                     out_len, score, static_cast<int*>(nullptr), w, DecLm{});
   if (hipGetLastError() != hipSuccess) { sca_set_error("sca_ctc_beam_decode: launch failed"); return SCA_ERR_LAUNCH; }
   return SCA_OK;
 }
@@ -901,7 +1087,7 @@ extern "C" int sca_ctc_beam_decode_heads(const sca_decode_heads* heads, int G, c
   hipLaunchKernelGGL(ctc_rowstat_heads_kernel, row_grid, dim3(256), 0, st, hx, w.rowstat, rows, (long)B * T, C);
   hipLaunchKernelGGL(ctc_topk_kernel, row_grid, dim3(256), 0, st, hx, G, in_len, d, w);
   hipLaunchKernelGGL(ctc_beam_kernel<false>, dim3(B, G), dim3(64), 0, st, hx, in_len, d, collapse_repeats != 0, 0,
-                     tokens, out_len, score, static_cast<int*>(nullptr), w);
+                     tokens, out_len, score, static_cast<int*>(nullptr), w, DecLm{});
   if (hipGetLastError() != hipSuccess) {
     sca_set_error("sca_ctc_beam_decode_heads: launch failed");
     return SCA_ERR_LAUNCH;
@@ -962,7 +1148,7 @@ extern "C" int sca_ctc_beam_decode_nbest(const float* logits, const int* in_len,
   sca_ctc_rowstat_launch(logits, w.rowstat, rows, C, st);
   hipLaunchKernelGGL(ctc_topk_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, hx, 1, in_len, d, w);
   hipLaunchKernelGGL(ctc_beam_kernel<true>, dim3(B), dim3(64), 0, st, hx, in_len, d, collapse_repeats != 0, nbest,
-                     tokens, out_len, score, count, w);
+                     tokens, out_len, score, count, w, DecLm{});
   if (hipGetLastError() != hipSuccess) {
     sca_set_error("sca_ctc_beam_decode_nbest: launch failed");
     return SCA_ERR_LAUNCH;
@@ -988,12 +1174,74 @@ extern "C" int sca_ctc_beam_decode_heads_nbest(const sca_decode_heads* heads, in
   hipLaunchKernelGGL(ctc_rowstat_heads_kernel, row_grid, dim3(256), 0, st, hx, w.rowstat, rows, (long)B * T, C);
   hipLaunchKernelGGL(ctc_topk_kernel, row_grid, dim3(256), 0, st, hx, G, in_len, d, w);
   hipLaunchKernelGGL(ctc_beam_kernel<true>, dim3(B, G), dim3(64), 0, st, hx, in_len, d, collapse_repeats != 0, nbest,
-                     tokens, out_len, score, count, w);
+                     tokens, out_len, score, count, w, DecLm{});
   if (hipGetLastError() != hipSuccess) {
     sca_set_error("sca_ctc_beam_decode_heads_nbest: launch failed");
     return SCA_ERR_LAUNCH;
   }
   return SCA_OK;
+}
+
+// ---- shallow fusion: the bigram model inside the search (include/scatten.h) ----
+namespace {
+
+bool fused_args_ok(int nbest, int beam_width, float lm_weight, float length_bonus, const void* in_len,
+                   const void* tokens, const void* out_len, const void* score, const void* count, const void* ws) {
+  return nbest >= 1 && nbest <= beam_width && lm_weight - lm_weight == 0.0f && length_bonus - length_bonus == 0.0f &&
+         in_len && tokens && out_len && score && count && ws;
+}
+
+// two launches: the row statistics, then the frame recursion (no shared label list to precompute)
+int fused_launch(const char* what, DecHeads hx, int G, const int* in_len, DecDims d, int nbest, int collapse,
+                 DecLm f, int* tokens, int* out_len, float* score, int* count, void* ws, hipStream_t st) {
+  const DecWs w(ws, d, G);
+  const long rows = (long)G * d.B * d.T;
+  hipLaunchKernelGGL(ctc_rowstat_heads_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, hx, w.rowstat, rows,
+                     (long)d.B * d.T, d.C);
+  hipLaunchKernelGGL((ctc_beam_kernel<true, true>), dim3(d.B, G), dim3(64), 0, st, hx, in_len, d, collapse, nbest,
+                     tokens, out_len, score, count, w, f);
+  if (hipGetLastError() != hipSuccess) {
+    sca_set_error(what);
+    return SCA_ERR_LAUNCH;
+  }
+  return SCA_OK;
+}
+
+}  // namespace
+
+extern "C" long sca_ctc_fused_workspace_bytes(int G, int B, int T, int C, int W) {
+  return sca_ctc_decode_heads_workspace_bytes(G, B, T, C, W);  // the same layout; cls holds the tail's rows only
+}
+
+extern "C" int sca_ctc_beam_decode_fused_nbest(const float* logits, const int* in_len, int B, int T, int C,
+                                               int beam_width, int nbest, int collapse_repeats, const float* lm,
+                                               float lm_weight, float length_bonus, int* tokens, int* out_len,
+                                               float* score, int* count, void* ws, void* stream) {
+  if (!dec_dims_ok(B, T, C, beam_width) || !logits ||
+      !fused_args_ok(nbest, beam_width, lm_weight, length_bonus, in_len, tokens, out_len, score, count, ws)) {
+    sca_set_error("sca_ctc_beam_decode_fused_nbest: bad arguments (B, T >= 1, 1 <= C <= 8192, "
+                  "1 <= nbest <= beam_width <= 32, finite weights)");
+    return SCA_ERR_ARG;
+  }
+  return fused_launch("sca_ctc_beam_decode_fused_nbest: launch failed", dec_one_head(logits), 1, in_len,
+                      DecDims{B, T, C, beam_width}, nbest, collapse_repeats != 0, DecLm{lm, lm_weight, length_bonus},
+                      tokens, out_len, score, count, ws, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int sca_ctc_beam_decode_heads_fused_nbest(const sca_decode_heads* heads, int G, const int* in_len, int B,
+                                                     int T, int C, int beam_width, int nbest, int collapse_repeats,
+                                                     const float* lm, float lm_weight, float length_bonus,
+                                                     int* tokens, int* out_len, float* score, int* count, void* ws,
+                                                     void* stream) {
+  if (!dec_heads_ok(heads, G, B, T, C, beam_width) ||
+      !fused_args_ok(nbest, beam_width, lm_weight, length_bonus, in_len, tokens, out_len, score, count, ws)) {
+    sca_set_error("sca_ctc_beam_decode_heads_fused_nbest: bad arguments (1 <= G <= 8 non-null tensors, B, T >= 1, "
+                  "1 <= C <= 8192, 1 <= nbest <= beam_width <= 32, finite weights)");
+    return SCA_ERR_ARG;
+  }
+  return fused_launch("sca_ctc_beam_decode_heads_fused_nbest: launch failed", dec_heads_of(heads, G), G, in_len,
+                      DecDims{B, T, C, beam_width}, nbest, collapse_repeats != 0, DecLm{lm, lm_weight, length_bonus},
+                      tokens, out_len, score, count, ws, reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" int sca_nbest_rescore(const int* tokens, const int* out_len, const float* score, const int* count, int G,

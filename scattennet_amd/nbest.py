@@ -8,6 +8,10 @@ of this.
 * `ctc_decode_nbest_device` / `ctc_decode_nbest_heads_device` — an `NBest` of device tensors
   (tokens (.., N, T) int32 padded with 0, lengths (.., N), scores (.., N), count (..)), `..`
   being (B) or (G, B).  `ctc_decode_nbest` — host lists of (ids, score) with one copy.
+* `ctc_decode_fused_nbest_device` / `ctc_decode_fused_nbest_heads_device` / `ctc_decode_fused_nbest` —
+  the same list from the search with the bigram model inside it (shallow fusion,
+  `sca_ctc_beam_decode_fused_nbest`): beams are ranked by total + lm_weight * bigram terms +
+  length_bonus * len; scores stay acoustic.  `Rescoring(..., fusion=True)` selects it in the steps.
 * `BigramLM` — a dense (C, C) table of log-probabilities; class 0, the blank, is the sentence
   boundary.  `BigramLM.from_sequences` estimates one with add-k smoothing on the host.
 * `rescore_nbest_device` — (total, posterior, order); `mbr_select_device` — (best, risk, loss);
@@ -89,7 +93,41 @@ class _NBestDecoderOne(nn.Module):
         return tokens, lengths, scores, count
 
 
-_decoder_heads, _decoder_one = _NBestDecoder(), _NBestDecoderOne()
+class _FusedDecoder(nn.Module):
+    """`sca_ctc_beam_decode_heads_fused_nbest`, or with `grouped=False` the single-head entry
+    point on `logits[0]`.  `table` is a keyword so that the logits decide the module's dtype."""
+
+    @fp32_compute()
+    def forward(self, in_len, beam, nbest, collapse, lm_weight, length_bonus, grouped, *logits, table=None):
+        xs = [x.detach().contiguous() for x in logits]
+        L.require_device(*xs)
+        G = len(xs)
+        B, T, C = xs[0].shape
+        lib = L.lib()
+        nbytes = lib.sca_ctc_fused_workspace_bytes(G, B, T, C, beam)
+        dev = xs[0].device
+        lead = (G, B) if grouped else (B,)
+        tokens = torch.empty(lead + (nbest, T), dtype=torch.int32, device=dev)
+        lengths = torch.empty(lead + (nbest,), dtype=torch.int32, device=dev)
+        scores = xs[0].new_empty(lead + (nbest,))
+        count = torch.empty(lead, dtype=torch.int32, device=dev)
+        ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.int64, device=dev)
+        lm = None if table is None else L.ptr(table)
+        tail = (B, T, C, beam, nbest, int(collapse), lm, lm_weight, length_bonus, L.ptr(tokens), L.ptr(lengths),
+                L.ptr(scores), L.ptr(count), L.ptr(ws), L.stream_handle())
+        if grouped:
+            hx = L.DecodeHeads()
+            for g, x in enumerate(xs):
+                hx.logits[g] = x.data_ptr()
+            L.check(lib.sca_ctc_beam_decode_heads_fused_nbest(ctypes.byref(hx), G, L.ptr(in_len), *tail),
+                    "sca_ctc_beam_decode_heads_fused_nbest")
+        else:
+            L.check(lib.sca_ctc_beam_decode_fused_nbest(L.ptr(xs[0]), L.ptr(in_len), *tail),
+                    "sca_ctc_beam_decode_fused_nbest")
+        return tokens, lengths, scores, count
+
+
+_decoder_heads, _decoder_one, _decoder_fused = _NBestDecoder(), _NBestDecoderOne(), _FusedDecoder()
 
 
 def _check_beam(beam_size, nbest):
@@ -167,12 +205,80 @@ def nbest_lists(tokens, lengths, values, count, extra=None, order=None):
 def ctc_decode_nbest(gloss_logits, beam_size, input_lengths, nbest=None, collapse_repeats=True):
     """`ctc_decode` with alternatives: a list of B lists of (class ids, score), best first, with
     one device-to-host copy."""
-    nb = ctc_decode_nbest_device(gloss_logits, input_lengths, beam_size, nbest, collapse_repeats)
+    return _host_lists(ctc_decode_nbest_device(gloss_logits, input_lengths, beam_size, nbest, collapse_repeats))
+
+
+def _host_lists(nb):
     B, N, T = nb.tokens.shape
     packed = torch.cat([nb.count.reshape(B, 1).double(), nb.lengths.double(), nb.scores.double(),
                         nb.tokens.reshape(B, N * T).double()], dim=1).cpu().numpy()  # exact for int32, fp32
     return nbest_lists(packed[:, 1 + 2 * N:].reshape(B, N, T).astype(np.int64), packed[:, 1:1 + N].astype(np.int64),
                        packed[:, 1 + N:1 + 2 * N], packed[:, 0].astype(np.int64))
+
+
+# ----------------------------------------------------------------------- shallow fusion
+def _check_fusion(lm, lm_weight, length_bonus, num_classes, what):
+    """Host-side validation; (lm_weight, length_bonus) as floats."""
+    if lm is not None and not isinstance(lm, BigramLM):
+        raise ValueError(f"{what}: lm must be a BigramLM or None, got {type(lm).__name__}")
+    lw, lb = _finite("lm_weight", lm_weight, what), _finite("length_bonus", length_bonus, what)
+    if lm is not None and lm.num_classes != num_classes:
+        raise ValueError(f"{what}: the gloss model has {lm.num_classes} classes, the logits {num_classes}")
+    return lw, lb
+
+
+def _fusion_table(lm, device, what):
+    if lm is None:
+        return None
+    if lm.table.device != device:
+        raise RuntimeError(f"{what}: the gloss model is on {lm.table.device}, the logits on {device}; use lm.to(device)")
+    return lm.table
+
+
+def ctc_decode_fused_nbest_device(gloss_logits, input_lengths, beam_size, lm, lm_weight=0.0, length_bonus=0.0,
+                                  nbest=None, collapse_repeats=True):
+    """`ctc_decode_nbest_device` with the bigram gloss model inside the search (shallow fusion,
+    `sca_ctc_beam_decode_fused_nbest`): every frame keeps the `beam_size` best prefixes by
+    total + lm_weight * (the prefix's bigram terms) + length_bonus * len, and the final beams are
+    ordered by that key with the closing bigram added.  `lm`: a `BigramLM` on the logits' device,
+    or None (the length bonus alone guides the search).  The `NBest` has the unfused call's
+    format: `scores` are acoustic log-probabilities, so `rescore_nbest_device` with the same
+    `lm`, `lm_weight` and `length_bonus` gives the totals the search ranked by.  With weight 0
+    and bonus 0 the result is bitwise `ctc_decode_nbest_device`'s.  No host sync; capturable."""
+    what = "ctc_decode_fused_nbest"
+    _check_logits(gloss_logits)
+    B, T, C = gloss_logits.shape
+    beam, n = _check_beam(beam_size, nbest)
+    il = _check_lengths(input_lengths, B, T)
+    lw, lb = _check_fusion(lm, lm_weight, length_bonus, C, what)
+    _check_device(gloss_logits)
+    table = _fusion_table(lm, gloss_logits.device, what)
+    return NBest(*_decoder_fused(_dev_i32(il, gloss_logits.device), beam, n, bool(collapse_repeats), lw, lb, False,
+                                 gloss_logits, table=table))
+
+
+def ctc_decode_fused_nbest_heads_device(logits_list, input_lengths, beam_size, lm, lm_weight=0.0, length_bonus=0.0,
+                                        nbest=None, collapse_repeats=True):
+    """`ctc_decode_fused_nbest_device` over the G heads of one forward in one grouped call, shaped
+    like `ctc_decode_nbest_heads_device`'s result; row g is bitwise the single-head call's."""
+    what = "ctc_decode_fused_nbest_heads"
+    xs = _check_heads(logits_list)
+    beam, n = _check_beam(beam_size, nbest)
+    B, T, C = xs[0].shape
+    il = _check_lengths(input_lengths, B, T)
+    lw, lb = _check_fusion(lm, lm_weight, length_bonus, C, what)
+    _check_device(xs[0])
+    table = _fusion_table(lm, xs[0].device, what)
+    return NBest(*_decoder_fused(_dev_i32(il, xs[0].device), beam, n, bool(collapse_repeats), lw, lb, True, *xs,
+                                 table=table))
+
+
+def ctc_decode_fused_nbest(gloss_logits, beam_size, input_lengths, lm, lm_weight=0.0, length_bonus=0.0, nbest=None,
+                           collapse_repeats=True):
+    """`ctc_decode_nbest` over the fused search: a list of B lists of (class ids, acoustic score),
+    in the list's order, with one device-to-host copy."""
+    return _host_lists(ctc_decode_fused_nbest_device(gloss_logits, input_lengths, beam_size, lm, lm_weight,
+                                                     length_bonus, nbest, collapse_repeats))
 
 
 # ------------------------------------------------------------------------- the gloss model
@@ -343,10 +449,14 @@ class Rescoring:
     best labellings of the beam search (1 <= nbest <= 32, and at most the step's beam_size),
     rescored with `lm` (a `BigramLM` or None), `lm_weight`, `length_bonus` and `posterior_scale`
     as `rescore_nbest_device` takes them, and the hypothesis picked by `select`: "score", the
-    best total, or "mbr", the minimum expected error count under the posterior.  ValueError for
-    anything else."""
+    best total, or "mbr", the minimum expected error count under the posterior.  `fusion=True`:
+    the list comes from the fused search (`ctc_decode_fused_nbest_heads_device` with this spec's
+    `lm`, `lm_weight` and `length_bonus`), so the search keeps what the rescorer would have
+    preferred; everything after the decode is unchanged.  ValueError for anything else, and for
+    `fusion=True` with neither a table nor a length bonus (nothing to fuse)."""
 
-    def __init__(self, nbest, lm=None, lm_weight=0.0, length_bonus=0.0, posterior_scale=1.0, select="score"):
+    def __init__(self, nbest, lm=None, lm_weight=0.0, length_bonus=0.0, posterior_scale=1.0, select="score",
+                 fusion=False):
         if isinstance(nbest, bool) or not isinstance(nbest, int) or not 1 <= nbest <= MAX_BEAM:
             raise ValueError(f"Rescoring: nbest must be an int in [1, {MAX_BEAM}], got {nbest!r}")
         if lm is not None and not isinstance(lm, BigramLM):
@@ -360,10 +470,16 @@ class Rescoring:
             self.posterior_scale = _finite("posterior_scale", posterior_scale, "Rescoring")
         except TypeError:
             raise ValueError("Rescoring: lm_weight, length_bonus and posterior_scale must be numbers") from None
+        if not isinstance(fusion, bool):
+            raise ValueError(f"Rescoring: fusion must be a bool, got {fusion!r}")
+        if fusion and lm is None and self.length_bonus == 0.0:
+            raise ValueError("Rescoring: fusion=True needs a gloss model or a length bonus: there is nothing to fuse")
+        self.fusion = fusion
 
     def __repr__(self):
         return (f"Rescoring(nbest={self.nbest}, lm={self.lm!r}, lm_weight={self.lm_weight}, length_bonus="
-                f"{self.length_bonus}, posterior_scale={self.posterior_scale}, select={self.select!r})")
+                f"{self.length_bonus}, posterior_scale={self.posterior_scale}, select={self.select!r}, "
+                f"fusion={self.fusion})")
 
     def check(self, beam_size, num_classes, frames, what):
         """Host-side validation against a step's beam, the logits' class count and their frame
@@ -391,15 +507,19 @@ def check_rescoring(rescoring, beam_size, what, num_classes=None, frames=None):
 
 
 def rescored_decode(logits_list, input_lengths, beam_size, rescoring, what="rescored_decode"):
-    """The grouped n-best decode of G heads, the rescore and (select="mbr") the MBR selection, and
-    the selected hypothesis as a 1-best triple.  Returns a dict of device tensors: `tokens`
+    """The grouped n-best decode of G heads (the fused search with `rescoring.fusion`), the rescore
+    and (select="mbr") the MBR selection, and the selected hypothesis as a 1-best triple.  Returns a dict of device tensors: `tokens`
     (G, B, T), `lengths` (G, B), `scores` (G, B) (the selected entry's total) and the list itself:
     `nbest_tokens` (G, B, N, T), `nbest_lengths`, `nbest_totals`, `nbest_posterior`, `nbest_order`
     (G, B, N), `nbest_count` (G, B), and with "mbr" `nbest_risk` (G, B, N), `nbest_best` (G, B).
     No host read."""
     xs = _check_heads(logits_list)
     check_rescoring(rescoring, beam_size, what, xs[0].shape[2], xs[0].shape[1])
-    nb = ctc_decode_nbest_heads_device(xs, input_lengths, beam_size, rescoring.nbest)
+    if rescoring.fusion:
+        nb = ctc_decode_fused_nbest_heads_device(xs, input_lengths, beam_size, rescoring.lm, rescoring.lm_weight,
+                                                 rescoring.length_bonus, rescoring.nbest)
+    else:
+        nb = ctc_decode_nbest_heads_device(xs, input_lengths, beam_size, rescoring.nbest)
     total, posterior, order = rescore_nbest_device(nb, rescoring.lm, rescoring.lm_weight, rescoring.length_bonus,
                                                    rescoring.posterior_scale)
     out = {"nbest_tokens": nb.tokens, "nbest_lengths": nb.lengths, "nbest_totals": total,

@@ -47,7 +47,8 @@ whole passes in alternated windows, ms per batch and the per-window difference.
 after the two default heads; asserts that the default heads' totals and hypotheses are identical.
 
 --rescore N[:score|mbr] (with --mixed --eval): the same pair, one with rescoring=Rescoring(N, a random
-bigram table, lm_weight 0.5, length_bonus 0.2, select) in place of the 1-best decode.
+bigram table, lm_weight 0.5, length_bonus 0.2, select) in place of the 1-best decode.  With --fusion a
+third pass takes its list from the fused search (Rescoring(..., fusion=True)), in the same alternation.
 """
 import argparse
 import json
@@ -399,6 +400,10 @@ def eval_rescore(a, dev):
     steps = {"plain": S.BucketedEvalStep(model, a.B, buckets, a.S, beam_size=a.beam, capacity=capacity),
              "rescored": S.BucketedEvalStep(model, a.B, buckets, a.S, beam_size=a.beam, capacity=capacity,
                                             rescoring=spec)}
+    if a.fusion:  # a third pass: the list from the fused search, everything after it unchanged
+        fspec = S.Rescoring(int(n), lm, 0.5, 0.2, select=select or "score", fusion=True)
+        steps["fused"] = S.BucketedEvalStep(model, a.B, buckets, a.S, beam_size=a.beam, capacity=capacity,
+                                            rescoring=fspec)
     g = torch.Generator().manual_seed(a.seed + 1)
     for bes in steps.values():
         capture_all(bes, batches, lambda f: _batch(a, w, dev, g, [f] * a.B, n_pool)[0], bes.state.reset)
@@ -419,6 +424,11 @@ def eval_rescore(a, dev):
            "rescored_minus_plain_ms_per_batch": _spread(diff), "clips": len(hyps["plain"]),
            "clips_with_another_hypothesis": changed,
            "results": {k: round(v, 4) for k, v in results["rescored"].items()}}
+    if a.fusion:
+        res.update({"fused_ms_per_batch": _spread(ms["fused"]),
+                    "fused_minus_rescored_ms_per_batch": _spread([x - y for x, y in zip(ms["fused"], ms["rescored"])]),
+                    "clips_fused_differs_from_rescored": sum(x != y for x, y in zip(hyps["rescored"], hyps["fused"])),
+                    "fused_results": {k: round(v, 4) for k, v in results["fused"].items()}})
     print(json.dumps(res))
 
 
@@ -439,6 +449,8 @@ def main():
                                                          "the forced alignment of every hypothesis")
     ap.add_argument("--ensemble", action="store_true", help="with --mixed --eval: the bucketed pass with and without "
                                                             "one five-member ensemble beside the two default heads")
+    ap.add_argument("--fusion", action="store_true", help="with --mixed --eval --rescore: a third pass whose list "
+                                                          "comes from the fused search (Rescoring(fusion=True))")
     ap.add_argument("--rescore", default=None, help="with --mixed --eval: N[:score|mbr], the bucketed pass with and "
                                                     "without the rescored n-best decode")
     ap.add_argument("--beam", type=int, default=5)

@@ -10,6 +10,13 @@ synchronise; the figure is the median of --repeats windows of --steps calls, wit
 chain), a random normalised bigram table.  Needs a GPU.
 
 Usage: python tools/nbest_bench.py [--B 8] [--T 64] [--C 1124] [--configs 5:5,32:32] [--steps 200]
+                                   [--fusion]
+
+--fusion adds the fused search (shallow fusion, ctc_decode_fused_nbest_device) with the same table,
+weight 0.5 and bonus 0.2: `fused_nbest` beside `beam_nbest`, `fused_chain` beside `chain`, the cost
+per frame of both decodes (graph median / T), and what the two searches end with on these random
+logits: the lists' mean count, the merge rate (1 - count / active beams), the posterior mass of
+entry 0, and how often the fused list's best total exceeds the rescored unfused list's.
 
 The 1-best decode of another build (the parent commit's library, SCA_LIB_PATH) is timed by
 tools/decode_bench.py --beam W in the same session; this tool only runs the build it imports.
@@ -35,6 +42,7 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--fusion", action="store_true", help="also time the fused search and compare its lists")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("nbest_bench: needs a GPU; nothing is measured without one")
@@ -59,6 +67,21 @@ def main():
             "chain": lambda: S.rescored_decode([x], il, W, spec),
         }
         out = {"merged_count_mean": round(float(nb.count.float().mean()), 2)}
+        if a.fusion:
+            fspec = S.Rescoring(N, lm, 0.5, 0.2, select="mbr", fusion=True)
+            ops["fused_nbest"] = lambda: S.ctc_decode_fused_nbest_device(x, il, W, lm, 0.5, 0.2, N)
+            ops["fused_chain"] = lambda: S.rescored_decode([x], il, W, fspec)
+            fnb = ops["fused_nbest"]()
+            ftotal, fpost, forder = S.rescore_nbest_device(fnb, lm, 0.5, 0.2)
+            raw = S.ctc_decode_fused_nbest_device(x, il, W, lm, 0.5, 0.2, N, collapse_repeats=False).count.float()
+            out["fused"] = {
+                "count_mean": round(float(fnb.count.float().mean()), 2),
+                "merge_rate": round(float(1 - (fnb.count.float() / raw).mean()), 4),
+                "posterior_entry0_mean": round(float(fpost.gather(1, forder[:, :1].long()).mean()), 4),
+                "unfused_posterior_entry0_mean": round(float(post.gather(1, order[:, :1].long()).mean()), 4),
+                "best_total_gain_mean": round(float((ftotal.max(1).values - total.max(1).values).mean()), 4),
+                "clips_with_larger_best_total": int((ftotal.max(1).values > total.max(1).values).sum()),
+                "clips": a.B}
         for name, fn in ops.items():
             for _ in range(a.warmup):
                 fn()
@@ -67,6 +90,9 @@ def main():
             for _ in range(a.warmup):
                 replay()
             out[name + "_graph"] = windows(replay, a.steps, a.repeats)
+        if a.fusion:
+            for name in ("beam_nbest", "fused_nbest"):
+                out[name + "_us_per_frame"] = round(out[name + "_graph"][0] / a.T, 3)
         res["configs"][f"beam{W}_n{N}"] = out
     print(json.dumps(res))
 
