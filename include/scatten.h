@@ -772,6 +772,57 @@ int sca_ctc_beam_decode_heads_fused_nbest(const sca_decode_heads* heads, int G, 
                                           float lm_weight, float length_bonus, int* tokens, int* out_len,
                                           float* score, int* count, void* ws, void* stream);
 
+/* ---- training: minimum word error rate (MWER) loss over an n-best list ----------------------
+ * The expected number of errors of a clip's n-best hypotheses under the model's own posterior
+ * over that list, with exact CTC likelihoods, and its gradient with respect to the logits.
+ * Inputs: batch-major fp32 logits (B, T, C), blank = class 0; in_len (B) clamped to [0, T] as
+ * the decoders clamp it; a list in sca_ctc_beam_decode_nbest's format, tokens (B, N, H) int32,
+ * out_len (B, N) clamped to [0, H], count (B) clamped to [0, N]; references ref (B, R) int32,
+ * ref_len (B) clamped to [0, R] as sca_wer_counts clamps it (a reference may be empty).
+ * Per clip b, with lp = clamp(log_softmax(logits[b, t]), -100, 0), the log-probabilities of
+ * sca_ctc_loss_fwd:
+ *   ll_n   = the exact CTC log-likelihood of hypothesis n over the frames [0, in_len_b): the
+ *            alpha recursion of the CTC loss WITHOUT its rule T_b = max(in_len, 1, S_b).  A
+ *            hypothesis that does not fit (len + adjacent repeats > in_len) has ll = -inf; the
+ *            empty hypothesis has ll = sum_t lp[t, 0], 0 for in_len = 0.
+ *   V      = the valid entries: n < count and ll_n finite (a NaN ll counts as valid, so that it
+ *            reaches the loss).  post_n = softmax over V of posterior_scale * ll_n, 0 outside V.
+ *   err_n  = num_del + num_ins + num_sub of sca_wer_counts with reference ref_b and hypothesis
+ *            h_n: the same device code as the WER kernel and sca_nbest_mbr (costs 3 / 3 / 4 and
+ *            the back-trace's order of preference: not Levenshtein's counts).
+ *   ebar_b = the mean of err over V;  d_n = err_n - ebar_b;  risk_b = sum_V post_n err_n;
+ *   loss_b = sum_V post_n d_n;  loss = (1 / B) sum_b loss_b; a clip with empty V contributes 0.
+ * Gradient, with w_n = (dloss / B) posterior_scale post_n (d_n - sum_V post_m d_m) (the centred
+ * form: a list whose error counts are all equal has every w_n exactly 0):
+ *   d loss / d lp[t, c] = sum_n w_n occ_n(t, c),  occ_n(t, c) = sum over the states s of h_n with
+ *   label c of exp(alpha_n[t, s] + beta_n[t, s] - lp[t, c] - ll_n), followed by the gate of the
+ *   clamp and the log-softmax backward as in sca_ctc_loss_bwd.  Rows t >= in_len_b, and clips
+ *   with at most one valid entry, are written as zeros; every element of dlogits is written.
+ * Outputs of fwd: loglik (B, N) (-inf for entries >= count and for those that do not fit),
+ * posterior (B, N), errors (B, N) int32 (0 for entries >= count), risk (B), loss (1).  ws:
+ * sca_mwer_workspace_floats(B, N, T, H) floats, kept between the forward and the backward (row
+ * statistics, alpha, beta, ll, w).  bwd: dloss (1 float, device).
+ * Limits, validated before any GPU call: 1 <= B <= 65535, T >= 1, C <= SCA_CTC_MAX_C,
+ * 1 <= N <= SCA_CTC_MAX_BEAM, 1 <= H, R <= SCA_WER_MAX_LEN.  Tokens and lengths are clamped
+ * in-kernel only to stay in bounds; entries >= count may hold anything and are ignored.  Tokens
+ * are class ids in [1, C): no decoder emits the blank; a token 0 is treated as one more blank
+ * state (no skip transition into it, its occupancy counted with the blank's).
+ * Three launches forward (row statistics; one launch with alpha and beta, one wave64 per (clip,
+ * entry, direction), beside the error count of every (clip, entry), one workgroup each; the
+ * per-clip statistics and the loss, one workgroup for B <= 64, else four clips per workgroup and
+ * one more launch for the fixed-order sum over the clips) and one backward (one workgroup per
+ * logits row: one dense gradient pass for the N
+ * hypotheses).  Nothing allocates, copies or synchronises (capturable).  No float atomics:
+ * every reduction over entries, states and clips runs in a fixed order, so a replayed capture is
+ * bitwise the eager call.                                                                    */
+long sca_mwer_workspace_floats(int B, int N, int T, int H);
+int sca_mwer_fwd(const float* logits, const int* in_len, const int* tokens, const int* out_len, const int* count,
+                 const int* ref, const int* ref_len, int B, int N, int T, int C, int H, int R, float posterior_scale,
+                 float* loglik, float* posterior, int* errors, float* risk, float* loss, float* ws, void* stream);
+int sca_mwer_bwd(const float* logits, const int* in_len, const int* tokens, const int* out_len, const int* count,
+                 int B, int N, int T, int C, int H, const float* dloss, const float* ws, float* dlogits,
+                 void* stream);
+
 /* ---- evaluation: CTC forced alignment (gloss spans and confidences) -----------------------
  * The best single path of G heads' logits through given label sequences: for every (head g,
  * clip b) the frames at which each label is emitted.  Logits as for the decoders (fp32

@@ -231,6 +231,9 @@ EXPORTS = {
     "sca_nbest_rescore": ([c_void_p] * 4 + [c_int] * 4 + [c_void_p, c_int] + [c_float] * 3 + [c_void_p] * 4, c_int),
     "sca_nbest_mbr": ([c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 4, c_int),
     "sca_nbest_gather": ([c_void_p] * 4 + [c_int] * 5 + [c_void_p] * 4, c_int),
+    "sca_mwer_workspace_floats": ([c_int] * 4, c_long),
+    "sca_mwer_fwd": ([c_void_p] * 7 + [c_int] * 6 + [c_float] + [c_void_p] * 7, c_int),
+    "sca_mwer_bwd": ([c_void_p] * 5 + [c_int] * 5 + [c_void_p] * 4, c_int),
     "sca_eval_accumulate": ([c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
                              c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p], c_int),
     "sca_ctc_align_workspace_bytes": ([c_int] * 4, c_long),

@@ -19,6 +19,7 @@ import torch
 from . import heads
 from .encoder import n_pool_of
 from .model import _LOGITS
+from .mwer import check_mwer
 from .train import train_step
 
 
@@ -245,15 +246,18 @@ class BucketedTrainStep(BucketedStep):
     Buckets must be multiples of 2**n_pool and at most cfg["max_position_embeddings"]; the
     optimizer needs `capture_slots >= len(frame_buckets)`.  `label_bucket` is the largest
     label count per clip (at most the CTC kernels' limit).  `step` uploads the optimizer's
-    hyper-parameters before a replay when a scheduler changed them.
+    hyper-parameters before a replay when a scheduler changed them.  `mwer`: None or an `MWER`,
+    handed to `train_step`; the added frames lie past `input_lengths`, so the MWER loss and its
+    gradients are those of the unpadded batch.
 
     Memory: every bucket keeps its own graph memory pool — all activations, gradients and
     workspaces of one step at (batch_size, bucket) stay reserved for the graph's lifetime, so
     the cost is about the sum over buckets of an eager step's peak at that length (parameters
     and optimizer state are shared, not duplicated)."""
 
-    def __init__(self, model, optimizer, batch_size, frame_buckets, label_bucket):
+    def __init__(self, model, optimizer, batch_size, frame_buckets, label_bucket, mwer=None):
         super().__init__(model, batch_size, frame_buckets, label_bucket)
+        self.mwer = check_mwer(mwer, "BucketedTrainStep")
         n, slots = len(self.frame_buckets), getattr(optimizer, "capture_slots", 0)
         if slots < n:
             raise ValueError(f"BucketedTrainStep: {n} buckets need an optimizer with capture_slots >= {n} (one "
@@ -264,7 +268,9 @@ class BucketedTrainStep(BucketedStep):
         return next(self.model.parameters()).device
 
     def _run(self, src):
-        return train_step(self.model, self.optimizer, src)
+        if self.mwer is None:
+            return train_step(self.model, self.optimizer, src)
+        return train_step(self.model, self.optimizer, src, mwer=self.mwer)
 
     def _keep(self, outputs):
         """Detached: the step's backward has run, and an autograd graph a caller keeps alive must

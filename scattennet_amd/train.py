@@ -24,22 +24,48 @@ once per length bucket and replays the bucket's graph on padded batches.
 """
 import math
 
-from . import ops
+import torch
+
+from . import heads, ops
 from .model import _students_of, deferred_check, first_error, flag_names, guard_of
 from .model import read_report as model_read_report
+from .mwer import check_mwer, mwer_guard, mwer_loss
 
 
-def train_step(model, optimizer, src_input):
+def _add_mwer(outputs, src_input, mwer):
+    """The MWER term of a step: `outputs["mwer_loss"]`, `outputs["mwer_risk"]` (B) and
+    `outputs["mwer_report"]` = (mwer_loss, mean risk), the two numbers `read_report` adds to its
+    one copy.  Returns the loss to back-propagate."""
+    logits = outputs[mwer.head]
+    labels = heads.labels_2d(src_input, logits.shape[0], "train_step")
+    loss, details = mwer_loss(logits, outputs["input_lengths"], labels, src_input["gloss_lengths"],
+                              beam_size=mwer.beam_size, nbest_size=mwer.nbest, posterior_scale=mwer.posterior_scale,
+                              return_details=True)
+    outputs["mwer_loss"], outputs["mwer_risk"] = loss, details["risk"]
+    outputs["mwer_report"] = torch.stack([loss.detach(), details["risk"].mean()])
+    return outputs["total_loss"] + mwer.weight * loss
+
+
+def train_step(model, optimizer, src_input, mwer=None):
     """One training step of MSCA_Net with FusedAdam, enqueued on the current stream without a
-    host read.  Returns the forward's outputs (`finite_report` holds the losses and flags)."""
+    host read.  Returns the forward's outputs (`finite_report` holds the losses and flags).
+    `mwer`: None, or an `MWER`: the step decodes the chosen head's logits into an n-best list,
+    adds `mwer_loss`, `mwer_risk` and `mwer_report` to the outputs (the last is the pair
+    (mwer_loss, mean risk) as one device tensor, which lets `read_report` keep to a single copy) and
+    back-propagates `total_loss + weight * mwer_loss`; a non-finite `mwer_loss` skips the update on the device like a flagged tensor."""
+    check_mwer(mwer, "train_step")
     for p in model.parameters():
         p.grad = None
     ops.advance_dropout()
     with deferred_check(model):
         outputs = model(src_input)
+    loss, guard = outputs["total_loss"], None
+    if mwer is not None:
+        loss = _add_mwer(outputs, src_input, mwer)
+        guard = mwer_guard(guard_of(outputs), outputs["mwer_loss"])
     ops.fork_ledger_begin()
     try:
-        outputs["total_loss"].backward()
+        loss.backward()
         # weight gradients held back for the side stream and deferred LayerNorm-affine
         # reductions are normally launched by the backward's final callback; a backward that
         # left some behind must not reach the update without them
@@ -51,7 +77,7 @@ def train_step(model, optimizer, src_input):
             pass  # the backward's own error is the one to report
         raise
     ops.fork_ledger_end()  # every stream forked in the step has joined the origin (capture rule)
-    optimizer.step(loss=guard_of(outputs))
+    optimizer.step(loss=guard_of(outputs) if guard is None else guard)
     return outputs
 
 
@@ -60,9 +86,18 @@ def read_report(outputs):
     `fuse_coord_loss`, `*_distill_loss`) and `guard` as Python floats, the flag words, and
     `skipped` (the update did not happen: `guard` was not finite, the test FusedAdam makes on
     the device).  Raises the reference's ValueError (model/__init__.py:130-235) when a checked
-    tensor was not finite."""
-    rep = model_read_report(outputs)
-    rep["skipped"] = not math.isfinite(rep["guard"])
+    tensor was not finite.  After a step with `mwer=`, also `mwer_loss` and `mwer_risk` (the mean
+    over the clips), from the same single copy; a non-finite `mwer_loss` counts as `skipped`."""
+    extra = outputs.get("mwer_report")
+    if extra is None:
+        rep = model_read_report(outputs)
+        rep["skipped"] = not math.isfinite(rep["guard"])
+    else:
+        report = outputs["finite_report"]
+        words = torch.cat([report, extra.view(report.dtype)]).cpu()
+        rep = model_read_report({**outputs, "finite_report": words[:report.numel()]})
+        rep["mwer_loss"], rep["mwer_risk"] = (float(v) for v in words[report.numel():].view(torch.float32))
+        rep["skipped"] = not (math.isfinite(rep["guard"]) and math.isfinite(rep["mwer_loss"]))
     msg = first_error(rep["flags"], flag_names(_students_of(outputs)))
     if msg is not None:
         raise ValueError(msg)

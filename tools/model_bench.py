@@ -49,6 +49,10 @@ after the two default heads; asserts that the default heads' totals and hypothes
 --rescore N[:score|mbr] (with --mixed --eval): the same pair, one with rescoring=Rescoring(N, a random
 bigram table, lm_weight 0.5, length_bonus 0.2, select) in place of the 1-best decode.  With --fusion a
 third pass takes its list from the fused search (Rescoring(..., fusion=True)), in the same alternation.
+
+--mwer (with --mixed): two BucketedTrainStep over the same stream, one with mwer=MWER(0.5, beam_size=--beam)
+(the n-best decode, the MWER loss and its backward inside every bucket's graph); whole passes in alternated
+windows, ms per step and the per-window difference, and the mean mwer_risk / mwer_loss of the stream.
 """
 import argparse
 import json
@@ -252,6 +256,66 @@ def mixed(a, dev):
     print(json.dumps(res))
 
 
+def mixed_mwer(a, dev):
+    """--mixed --mwer: two BucketedTrainStep over the same stream in alternated windows, one with
+    mwer=MWER(0.5, beam_size=--beam) (the n-best decode, the MWER loss and its backward inside the
+    graph), and the loss's statistics on the stream: the mean risk, the share of clips whose error
+    counts are not all equal (the clips that get a gradient) and the share of non-zero gradient rows,
+    from an untimed `mwer_loss` call on each step's own logits (an untrained head: this shows the path
+    is exercised, not that MWER lowers WER)."""
+    import scattennet_amd as S
+    adam = dict(lr=1e-4, betas=(0.9, 0.998), weight_decay=1e-3, max_grad_norm=1.0)
+    buckets = tuple(int(b) for b in a.buckets.split(","))
+    steps = {}
+    for name, spec in (("plain", None), ("mwer", S.MWER(0.5, beam_size=a.beam))):
+        model, _, w, _ = build(a, dev)
+        model.check = "defer"
+        opt = S.FusedAdam(model.parameters(), capture_slots=len(buckets), **adam)
+        steps[name] = S.BucketedTrainStep(model, opt, a.B, buckets, a.S, mwer=spec)
+    n_pool = (len(w["residual_blocks"]) + 1) // 2
+    batches = mixed_batches(a, w, dev, n_pool)
+    g = torch.Generator().manual_seed(a.seed + 1)
+    for step in steps.values():
+        capture_all(step, batches, lambda f: _batch(a, w, dev, g, [f] * a.B, n_pool)[0])
+    ms = {k: [] for k in steps}
+    for _ in range(a.windows):  # alternated windows
+        for k, step in steps.items():
+            ms[k].append(_pass(step.step, batches))
+    risk, loss, skipped, clips, live, rows, nonzero = [], [], 0, 0, 0, 0, 0
+    for src, _ in batches:
+        out = steps["mwer"].step(src)
+        rep = S.read_report(out)
+        risk.append(rep["mwer_risk"])
+        loss.append(rep["mwer_loss"])
+        skipped += rep["skipped"]
+        # the same list and loss once more on the step's logits, for the per-clip figures
+        z = out["fuse_coord_gloss_logits"].detach().clone().requires_grad_(True)
+        nb = S.ctc_decode_nbest_device(z, out["input_lengths"], a.beam, a.beam, collapse_repeats=False)
+        l, det = S.mwer_loss(z, out["input_lengths"], src["gloss_labels"], src["gloss_lengths"], nbest=nb,
+                             return_details=True)
+        l.backward()
+        valid = torch.isfinite(det["loglik"])
+        err = det["errors"].float()
+        hi = torch.where(valid, err, err.new_full((), -1e9)).max(1).values
+        lo = torch.where(valid, err, err.new_full((), 1e9)).min(1).values
+        clips += a.B
+        live += int((hi > lo).sum())
+        frames = torch.arange(z.shape[1], device=dev)[None, :] < out["input_lengths"][:, None]
+        rows += int(frames.sum())
+        nonzero += int(((z.grad.abs().amax(-1) > 0) & frames).sum())
+        del l, det
+    diff = [x - y for x, y in zip(ms["mwer"], ms["plain"])]
+    print(json.dumps({"workload": "MSCA_Net BucketedTrainStep over a mixed-length stream with and without the MWER "
+                                  "loss, eval mode, no report read in the timed passes",
+                      "B": a.B, "max_len": a.T, "C": a.C, "S": a.S, "seed": a.seed, "beam": a.beam,
+                      "buckets": list(buckets), "batch_lengths": [T for _, T in batches],
+                      "plain_ms_per_step": _spread(ms["plain"]), "mwer_ms_per_step": _spread(ms["mwer"]),
+                      "mwer_minus_plain_ms_per_step": _spread(diff), "mwer_risk_mean": round(statistics.mean(risk), 4),
+                      "mwer_loss_mean": round(statistics.mean(loss), 6),
+                      "clips_with_non_constant_errors": round(live / clips, 4),
+                      "gradient_rows_non_zero": round(nonzero / max(rows, 1), 4), "skipped_steps": skipped}))
+
+
 def eval_loop(S, model, beam):
     """One batch of the loop a user writes from the parts: returns what it read."""
     def step(src):
@@ -453,6 +517,8 @@ def main():
                                                           "comes from the fused search (Rescoring(fusion=True))")
     ap.add_argument("--rescore", default=None, help="with --mixed --eval: N[:score|mbr], the bucketed pass with and "
                                                     "without the rescored n-best decode")
+    ap.add_argument("--mwer", action="store_true", help="with --mixed: BucketedTrainStep with and without the MWER "
+                                                        "loss (beam --beam), alternated windows")
     ap.add_argument("--beam", type=int, default=5)
     ap.add_argument("--batches", type=int, default=20)
     ap.add_argument("--buckets", default="64,128,192,256")
@@ -470,6 +536,8 @@ def main():
             return eval_ensemble(a, dev)
         if a.eval and a.rescore:
             return eval_rescore(a, dev)
+        if a.mwer and not a.eval:
+            return mixed_mwer(a, dev)
         return eval_mixed(a, dev) if a.eval else mixed(a, dev)
     model, src, w, t4 = build(a, dev)
     graphs = {k: capture(model, src, k, dev) for k in ("off", "defer")}

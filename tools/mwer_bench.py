@@ -1,0 +1,128 @@
+"""Time the MWER loss (scattennet_amd/mwer.py) on one MI355X at the evaluation shape of the 2014T
+yaml (B = 8, T/4 = 64, C = 1124), beam 5 and N = 5, with the lists the decoder gives, beside what
+the CTC loss of the same build costs on the same logits:
+
+* `mwer`            MWERLossOp forward + backward over the decoder's N-best list
+* `ctc_1target`     CTCLossOp forward + backward, one target per clip (entry 0 of the list)
+* `ctc_replicated`  CTCLossOp forward + backward on logits.repeat_interleave(N, 0) with the N
+                    hypotheses as labels: what the existing kernels charge for the N likelihoods
+                    (the replication included); it does not deliver the MWER gradient
+* `wer_pairs`       wer_counts on the B N (reference, entry) pairs: the alignment alone, which the
+                    MWER forward contains and neither CTC route does
+* `decode_nbest`    the uncollapsed n-best decode that a training step adds in front
+
+Every op is a captured graph replayed in windows that take turns (tools/decode_bench.alternated):
+us per call, median, min and max of --repeats windows of --steps replays, each window ending in a
+device synchronise.  Synthetic logits N(0, 4^2), full-length clips, references = entry 1 of each
+clip's list (so the error counts differ).  Also the statistics of the loss on these inputs: the mean
+risk, the share of clips with non-constant error counts and the share of non-zero gradient rows.
+Needs a GPU.
+
+Usage: python tools/mwer_bench.py [--B 8] [--T 64] [--C 1124] [--beam 5] [--nbest 5] [--steps 200]
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from tools.decode_bench import alternated, graphed  # noqa: E402
+
+
+def statistics_of(S, z, il, ref, ref_len, nb):
+    """The loss on the benchmark's inputs: host numbers only (the autograd graph dies with the call)."""
+    N = nb.tokens.shape[1]
+    loss, det = S.mwer_loss(z, il, ref, ref_len, nbest=nb, return_details=True)
+    loss.backward()
+    err = det["errors"].float()
+    live = torch.arange(N, device=z.device)[None, :] < nb.count[:, None]
+    hi = torch.where(live, err, err.new_full((), -1e9)).max(1).values
+    lo = torch.where(live, err, err.new_full((), 1e9)).min(1).values
+    return {"loss": round(float(loss.detach()), 6), "risk_mean": round(float(det["risk"].mean()), 4),
+            "count_mean": round(float(nb.count.float().mean()), 2),
+            "clips_with_non_constant_errors": round(float((hi != lo).float().mean()), 4),
+            "gradient_rows_non_zero": round(float((z.grad.abs().amax(-1) > 0).float().mean()), 4)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--B", type=int, default=8)
+    ap.add_argument("--T", type=int, default=64)
+    ap.add_argument("--C", type=int, default=1124)
+    ap.add_argument("--beam", type=int, default=5)
+    ap.add_argument("--nbest", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--repeats", type=int, default=5)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("mwer_bench: needs a GPU; nothing is measured without one")
+    import scattennet_amd as S
+    from scattennet_amd.heads import CTCLossOp
+    dev = torch.device("cuda")
+    g = torch.Generator().manual_seed(0)
+    x = (torch.randn(a.B, a.T, a.C, generator=g) * 4).to(dev)
+    il = torch.full((a.B,), a.T, dtype=torch.int32, device=dev)
+    N = a.nbest
+    nb = S.ctc_decode_nbest_device(x, il, a.beam, N, collapse_repeats=False)
+    ref = nb.tokens[:, min(1, N - 1)].contiguous()
+    ref_len = nb.lengths[:, min(1, N - 1)].contiguous()
+    R = max(int(ref_len.max()), 1)
+    ref = ref[:, :R].contiguous()
+    # the CTC baselines' labels: entry 0 per clip; every entry of the replicated batch
+    S1 = max(int(nb.lengths[:, 0].max()), 1)
+    lab1, len1 = nb.tokens[:, 0, :S1].contiguous(), nb.lengths[:, 0].contiguous()
+    SN = max(int(nb.lengths.max()), 1)
+    labN, lenN = nb.tokens.reshape(a.B * N, -1)[:, :SN].contiguous(), nb.lengths.reshape(-1).contiguous()
+    ilN = il.repeat_interleave(N, 0)
+
+    # Every timed op owns its leaf: a captured backward must not meet a gradient accumulator that an
+    # earlier autograd graph of the same tensor left on another stream (capture rules), so
+    # nothing runs a backward on the default stream before the captures, and the statistics, whose
+    # graph lives on that stream, come last and on a leaf of their own.
+    def leaf():
+        return x.detach().clone().requires_grad_(True)
+
+    def mwer(z=leaf()):
+        z.grad = None
+        S.mwer_loss(z, il, ref, ref_len, nbest=nb).backward()
+
+    def ctc_1target(z=leaf()):
+        z.grad = None
+        CTCLossOp.apply(z, lab1, il, len1)[0].backward()
+
+    def ctc_replicated(z=leaf()):
+        z.grad = None
+        CTCLossOp.apply(z.repeat_interleave(N, 0), labN, ilN, lenN)[0].backward()
+
+    refN, ref_lenN = ref.repeat_interleave(N, 0).contiguous(), ref_len.repeat_interleave(N, 0).contiguous()
+    hypN = nb.tokens.reshape(a.B * N, -1).contiguous()
+
+    def wer_pairs():
+        S.wer_counts(refN, ref_lenN, hypN, lenN)
+
+    def decode_nbest():
+        S.ctc_decode_nbest_device(x, il, a.beam, N, collapse_repeats=False)
+
+    replays = {}
+    for name, fn in (("mwer", mwer), ("ctc_1target", ctc_1target), ("ctc_replicated", ctc_replicated),
+                     ("wer_pairs", wer_pairs), ("decode_nbest", decode_nbest)):
+        replays[name] = graphed(fn)  # one eager run on a side stream, then the capture
+        for _ in range(a.warmup):
+            replays[name]()
+    timed = alternated(replays, a.steps, a.repeats)
+    stats = statistics_of(S, leaf(), il, ref, ref_len, nb)
+    res = {"workload": "MWER loss forward + backward beside the CTC loss, graph replays", "B": a.B, "T": a.T, "C": a.C,
+           "beam": a.beam, "nbest": N, "steps": a.steps, "repeats": a.repeats, "unit": "us per call",
+           "statistics": stats, "graph": timed}
+    m = res["graph"]
+    res["mwer_over_ctc_1target"] = round(m["mwer"]["median"] / m["ctc_1target"]["median"], 3)
+    res["mwer_over_ctc_replicated"] = round(m["mwer"]["median"] / m["ctc_replicated"]["median"], 3)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
