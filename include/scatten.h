@@ -639,7 +639,14 @@ int sca_wer_counts(const int* ref, const int* ref_len, const int* hyp, const int
  * aligned.  The row statistics and the per-frame best labels of all G B T rows are one launch
  * each, the frame recursion runs on a (B, G) grid, and every (head, clip) has its own arena
  * slice and cls / clp rows: head g's results are bitwise those of the single-head entry point
- * called on heads->logits[g].                                                              */
+ * called on heads->logits[g].
+ *
+ * All eight decoders (these four, the n-best and the fused forms below) are one argument check
+ * and one launcher; a single-head entry point is the grouped one with G = 1 and its tensor in
+ * heads->logits[0].  The launcher enqueues the row statistics (the row pass of the CTC loss,
+ * one body for both; with G = 1 the loss's own launch), the per-frame best labels for the beam
+ * and n-best searches, and one search kernel; the three workspace-size functions are one formula, the single-head layout
+ * over G B clips.                                                                          */
 #define SCA_EVAL_MAX_HEADS 8
 typedef struct {
   const float* logits[SCA_EVAL_MAX_HEADS]; /* entries [G, 8) are ignored */
@@ -654,8 +661,8 @@ int sca_ctc_beam_decode_heads(const sca_decode_heads* heads, int G, const int* i
 /* ---- evaluation: n-best lists, bigram rescoring, MBR selection ------------------------------
  * sca_ctc_beam_decode_nbest / sca_ctc_beam_decode_heads_nbest: the N = nbest best labellings of
  * the search above, 1 <= nbest <= beam_width <= 32.  Logits, in_len, ws and its size are those
- * of sca_ctc_beam_decode / sca_ctc_beam_decode_heads (the same three launches; G = 1 for the
- * single-head form).  tokens (G, B, N, T) int32 padded with 0, out_len (G, B, N) int32, score
+ * of sca_ctc_beam_decode / sca_ctc_beam_decode_heads (the one launcher's three launches; G = 1
+ * for the single-head form).  tokens (G, B, N, T) int32 padded with 0, out_len (G, B, N) int32, score
  * (G, B, N) fp32, count (G, B) int32; every element is written by every call.
  *   The search is sca_ctc_beam_decode's, frame for frame.  After the last frame the active
  *   beams are in descending order of total, ties in slot order: entry n is beam n, its tokens

@@ -304,6 +304,19 @@ def ptr(t):
     return None if t is None else c_void_p(t.data_ptr())
 
 
+def decode_heads(tensors):
+    """The `DecodeHeads` (sca_decode_heads) of up to 8 device tensors: their pointers, by value."""
+    hx = DecodeHeads()
+    for g, x in enumerate(tensors):
+        hx.logits[g] = x.data_ptr()
+    return hx
+
+
+def workspace(nbytes, device):
+    """An 8-byte-aligned workspace of `nbytes` bytes from the caching allocator (never empty)."""
+    return torch.empty(max(nbytes, 8) // 8, dtype=torch.int64, device=device)
+
+
 def require_device(*tensors):
     for t in tensors:
         if t is not None and (not t.is_cuda or t.dtype != torch.float32):

@@ -26,7 +26,7 @@ import torch
 from torch import nn
 
 from . import _lib as L
-from .decode import _check_device, _check_lengths, _check_logits
+from .decode import _check_lengths, _check_logits, check_heads, check_on_device
 from .heads import _dev_i32
 from .precision import fp32_compute
 
@@ -54,10 +54,7 @@ class _HeadsAligner(nn.Module):
         spans = torch.empty(G, B, S, 2, dtype=torch.int32, device=dev)
         conf = xs[0].new_empty(G, B, S)
         scores = xs[0].new_empty(G, B)
-        ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.int64, device=dev)
-        hx = L.DecodeHeads()
-        for g, x in enumerate(xs):
-            hx.logits[g] = x.data_ptr()
+        ws, hx = L.workspace(nbytes, dev), L.decode_heads(xs)
         L.check(lib.sca_ctc_align_heads(ctypes.byref(hx), G, L.ptr(in_len), L.ptr(labels), L.ptr(lab_len),
                                         int(per_head), B, T, C, S, L.ptr(frame_label), L.ptr(spans), L.ptr(conf),
                                         L.ptr(scores), L.ptr(ws), L.stream_handle()), "sca_ctc_align_heads")
@@ -65,21 +62,6 @@ class _HeadsAligner(nn.Module):
 
 
 _heads_aligner = _HeadsAligner()
-
-
-def _check_heads(logits_list):
-    xs = list(logits_list)
-    if not 1 <= len(xs) <= MAX_HEADS:
-        raise ValueError(f"ctc_align_heads: between 1 and {MAX_HEADS} logit tensors, got {len(xs)}")
-    for x in xs:
-        _check_logits(x)
-    first = xs[0]
-    for x in xs[1:]:
-        if x.shape != first.shape or x.dtype != first.dtype or x.device != first.device:
-            raise ValueError("ctc_align_heads: every head must have the same shape, dtype and device; got "
-                             f"{tuple(first.shape)} {first.dtype} {first.device} and {tuple(x.shape)} {x.dtype} "
-                             f"{x.device}")
-    return xs
 
 
 def _check_labels(labels, label_lengths, G, B, C):
@@ -127,11 +109,11 @@ def ctc_align_heads_device(logits_list, input_lengths, labels, label_lengths):
     conf (G, B, S): the mean posterior of the label over its span; scores (G, B): the path's
     log-probability, -inf for a clip that cannot emit its labels) on the device: row g is bitwise
     what the single-head call returns.  No host sync; capturable."""
-    xs = _check_heads(logits_list)
+    xs = check_heads(logits_list, "ctc_align_heads")
     B, T, C = xs[0].shape
     il = _check_lengths(input_lengths, B, T)
     lab, n, per_head = _check_labels(labels, label_lengths, len(xs), B, C)
-    _check_device(xs[0])
+    check_on_device(None, xs[0])
     dev = xs[0].device
     return Alignment(*_heads_aligner(_dev_i32(il, dev), _dev_i32(lab, dev), _dev_i32(n, dev), per_head, *xs))
 

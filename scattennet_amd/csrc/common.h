@@ -102,8 +102,24 @@ __host__ __device__ __forceinline__ uint32_t sca_mix32(uint32_t x) {
 
 extern "C" const unsigned long long* sca_drop_offset_ptr(void);
 
-// heads.hip: one wave per row of C logits, rowstat[2 row] = max, rowstat[2 row + 1] =
-// log(sum exp(x - max)); the CTC loss and the CTC decoders (decode.hip) share it
+// One wave over one row xr of C logits: lane 0 writes stat[0] = max and stat[1] =
+// log(sum exp(x - max)).  The row pass of the CTC loss (heads.hip, ctc_rowstat_kernel) and of
+// the CTC decoders (decode.hip, ctc_rowstat_heads_kernel): one body, so the two agree bitwise.
+__device__ __forceinline__ void ctc_row_stat(const float* xr, int C, int lane, float* stat) {
+  float m = -__builtin_huge_valf();
+  for (int c = lane; c < C; c += 64) m = fmaxf(m, xr[c]);
+  m = wave_max(m);
+  float s = 0.0f;
+  for (int c = lane; c < C; c += 64) s += __expf(xr[c] - m);
+  s = wave_sum(s);
+  if (lane == 0) {
+    stat[0] = m;
+    stat[1] = __logf(s);
+  }
+}
+
+// heads.hip: ctc_row_stat over the rows of one tensor, rowstat (rows, 2); the CTC loss, the MWER
+// loss (mwer.hip) and a decoder call over one tensor (decode.hip) use it
 __attribute__((visibility("hidden"))) void sca_ctc_rowstat_launch(const float* x, float* rowstat, long rows, int C,
                                                                   hipStream_t st);
 

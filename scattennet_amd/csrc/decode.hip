@@ -15,11 +15,18 @@
 // so a clip is one workgroup; everything that does not depend on the beam (row normaliser,
 // the W + 1 best classes of every frame) is computed beforehand by row-parallel launches.
 // No float atomics; every sum runs in a fixed order: results are deterministic.
+#include <cstdio>
+
 #include "common.h"
 #include "wer_pair.h"
 #include "../../include/scatten.h"
 
 extern "C" void sca_set_error(const char* msg);
+// the grouped row pass of the decoders (G > 1) and of align.hip (which validates heads and G): rowstat
+// (G, rows_per_head, 2)
+__attribute__((visibility("hidden"))) void sca_ctc_rowstat_heads_launch(const sca_decode_heads* heads, int G,
+                                                                        float* rowstat, long rows_per_head, int C,
+                                                                        hipStream_t st);
 
 namespace {
 
@@ -141,25 +148,15 @@ __device__ __forceinline__ unsigned long long dec_pl(int par, int lab) {
 __device__ __forceinline__ int dec_par(unsigned long long v) { return (int)(v >> 32); }
 __device__ __forceinline__ int dec_lab(unsigned long long v) { return (int)(v & 0xffffffffull); }
 
-// One wave per (g, b, t) row: max and log-sum-exp of the logits row, the arithmetic of the
-// CTC loss's row pass (heads.hip, ctc_rowstat_kernel) over the rows of G tensors.
+// One wave per (g, b, t) row: max and log-sum-exp of the logits row, the CTC loss's row pass
+// (ctc_row_stat, common.h) over the rows of G tensors.  A grouped decoder's first launch.
 __global__ __launch_bounds__(256) void ctc_rowstat_heads_kernel(DecHeads hx, float* __restrict__ rowstat, long rows,
                                                                 long rows_per_head, int C) {
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= rows) return;
   const int g = (int)(row / rows_per_head);
-  const float* xr = dec_head(hx, g) + (row - g * rows_per_head) * C;
-  float m = NEG_INF;
-  for (int c = lane; c < C; c += 64) m = fmaxf(m, xr[c]);
-  m = wave_max(m);
-  float s = 0.0f;
-  for (int c = lane; c < C; c += 64) s += __expf(xr[c] - m);
-  s = wave_sum(s);
-  if (lane == 0) {
-    rowstat[2 * row] = m;
-    rowstat[2 * row + 1] = __logf(s);
-  }
+  ctc_row_stat(dec_head(hx, g) + (row - g * rows_per_head) * C, C, lane, rowstat + 2 * row);
 }
 
 // One wave per (g, b, t) row: the K = min(W + 1, C - 1) labels (c != 0) with the largest
@@ -937,15 +934,88 @@ DecHeads dec_heads_of(const sca_decode_heads* heads, int G) {
   return h;
 }
 
-DecHeads dec_one_head(const float* logits) {
-  DecHeads h = {};
-  for (int g = 0; g < SCA_EVAL_MAX_HEADS; ++g) h.x[g] = logits;
-  return h;
+// the single-head layout over N = G B clips; 0 for unsupported sizes
+long dec_ws_bytes(int G, int B, int T, int C, int W) {
+  if (G < 1 || G > SCA_EVAL_MAX_HEADS || !dec_dims_ok(B, T, C, W)) return 0;
+  const long N = (long)G * B, NT = N * T;
+  return 4 * (2 * NT + 2 * NT * (W + 1)) + 8 * N * ((long)T * W + 1);
+}
+
+// One call of any of the eight decoders.  A single-head entry point is G = 1 with its tensor in
+// heads->logits[0]; the fields a mode does not take are 0 / NULL.
+enum DecMode { DEC_GREEDY, DEC_BEAM, DEC_NBEST, DEC_FUSED };
+struct DecCall {
+  DecMode mode;
+  const sca_decode_heads* heads;
+  int G;
+  const int* in_len;
+  DecDims d;            // W = beam_width; 1 for DEC_GREEDY
+  int collapse, nbest;  // nbest, count: DEC_NBEST and DEC_FUSED
+  DecLm f;              // DEC_FUSED
+  int *tokens, *out_len;
+  float* score;
+  int* count;
+  void* ws;
+};
+
+bool dec_call_ok(const DecCall& c) {
+  if (!dec_heads_ok(c.heads, c.G, c.d.B, c.d.T, c.d.C, c.d.W) || !c.in_len || !c.tokens || !c.out_len || !c.score ||
+      !c.ws)
+    return false;
+  if (c.mode >= DEC_NBEST && (c.nbest < 1 || c.nbest > c.d.W || !c.count)) return false;
+  return c.mode != DEC_FUSED || (c.f.weight - c.f.weight == 0.0f && c.f.bonus - c.f.bonus == 0.0f);
+}
+
+// The launches of every decoder: the row statistics of all G B T rows, the per-frame best labels
+// (the fused search selects its own per beam, the greedy kernel needs none), then one workgroup
+// per (clip, head).
+void dec_launch(const DecCall& c, hipStream_t st) {
+  const DecDims d = c.d;
+  const DecWs w(c.ws, d, c.G);
+  const DecHeads hx = dec_heads_of(c.heads, c.G);
+  const long rows = (long)c.G * d.B * d.T;
+  const dim3 clips(d.B, c.G);
+  // one tensor: the CTC loss's launch of the same row body, without the head select (measured:
+  // 0.2 us of the 24 us greedy decode at B = 8, T = 64, C = 1124)
+  if (c.G == 1) sca_ctc_rowstat_launch(c.heads->logits[0], w.rowstat, rows, d.C, st);
+  else sca_ctc_rowstat_heads_launch(c.heads, c.G, w.rowstat, (long)d.B * d.T, d.C, st);
+  if (c.mode == DEC_BEAM || c.mode == DEC_NBEST)
+    hipLaunchKernelGGL(ctc_topk_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, hx, c.G, c.in_len, d, w);
+  if (c.mode == DEC_GREEDY) {
+    hipLaunchKernelGGL(ctc_greedy_kernel, clips, dim3(64 * GREEDY_WAVES), 0, st, hx, c.in_len, d, c.tokens, c.out_len,
+                       c.score, w);
+    return;
+  }
+  const auto search = c.mode == DEC_BEAM    ? ctc_beam_kernel<false>
+                      : c.mode == DEC_NBEST ? ctc_beam_kernel<true>
+                                            : ctc_beam_kernel<true, true>;
+  hipLaunchKernelGGL(search, clips, dim3(64), 0, st, hx, c.in_len, d, c.collapse, c.nbest, c.tokens, c.out_len,
+                     c.score, c.count, w, c.f);
+}
+
+// An entry point: the argument check, the launches, the launch check.  `name` and `grouped`
+// (the _heads form) only word the messages.
+int dec_decode(const char* name, bool grouped, const DecCall& c, void* stream) {
+  static const char* const limits[] = {"", ", 1 <= beam_width <= 32", ", 1 <= nbest <= beam_width <= 32",
+                                       ", 1 <= nbest <= beam_width <= 32, finite weights"};
+  char msg[256];
+  if (!dec_call_ok(c)) {
+    snprintf(msg, sizeof(msg), "%s: bad arguments (%sB, T >= 1, 1 <= C <= 8192%s)", name,
+             grouped ? "1 <= G <= 8 non-null tensors, " : "", limits[c.mode]);
+    sca_set_error(msg);
+    return SCA_ERR_ARG;
+  }
+  dec_launch(c, reinterpret_cast<hipStream_t>(stream));
+  if (hipGetLastError() != hipSuccess) {
+    snprintf(msg, sizeof(msg), "%s: launch failed", name);
+    sca_set_error(msg);
+    return SCA_ERR_LAUNCH;
+  }
+  return SCA_OK;
 }
 
 }  // namespace
 
-// the grouped row pass for align.hip (which validates heads and G): rowstat (G, rows_per_head, 2)
 __attribute__((visibility("hidden"))) void sca_ctc_rowstat_heads_launch(const sca_decode_heads* heads, int G,
                                                                         float* rowstat, long rows_per_head, int C,
                                                                         hipStream_t st) {
@@ -954,100 +1024,46 @@ __attribute__((visibility("hidden"))) void sca_ctc_rowstat_heads_launch(const sc
                      dec_heads_of(heads, G), rowstat, rows, rows_per_head, C);
 }
 
-extern "C" long sca_ctc_decode_workspace_bytes(int B, int T, int C, int W) {
-  if (!dec_dims_ok(B, T, C, W)) return 0;
-  const long BT = (long)B * T;
-  return 4 * (2 * BT + 2 * BT * (W + 1)) + 8 * (long)B * ((long)T * W + 1);
-}
+extern "C" long sca_ctc_decode_workspace_bytes(int B, int T, int C, int W) { return dec_ws_bytes(1, B, T, C, W); }
 
 extern "C" long sca_ctc_decode_heads_workspace_bytes(int G, int B, int T, int C, int W) {
-  if (G < 1 || G > SCA_EVAL_MAX_HEADS || !dec_dims_ok(B, T, C, W)) return 0;
-  const long N = (long)G * B, NT = N * T;  // the single-head layout over N = G B clips
-  return 4 * (2 * NT + 2 * NT * (W + 1)) + 8 * N * ((long)T * W + 1);
+  return dec_ws_bytes(G, B, T, C, W);
 }
+
+// the same layout; cls holds the tail's rows only
+extern "C" long sca_ctc_fused_workspace_bytes(int G, int B, int T, int C, int W) { return dec_ws_bytes(G, B, T, C, W); }
 
 extern "C" int sca_ctc_greedy_decode(const float* logits, const int* in_len, int B, int T, int C, int* tokens,
                                      int* out_len, float* score, void* ws, void* stream) {
-  if (!dec_dims_ok(B, T, C, 1) || !logits || !in_len || !tokens || !out_len || !score || !ws) {
-    sca_set_error("sca_ctc_greedy_decode: bad arguments (B, T >= 1, 1 <= C <= 8192)");
-    return SCA_ERR_ARG;
-  }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const DecDims d{B, T, C, 1};
-  const DecWs w(ws, d);
-  sca_ctc_rowstat_launch(logits, w.rowstat, (long)B * T, C, st);
-  hipLaunchKernelGGL(ctc_greedy_kernel, dim3(B), dim3(64 * GREEDY_WAVES), 0, st, dec_one_head(logits), in_len, d,
-                     tokens, out_len, score, w);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_ctc_greedy_decode: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  const sca_decode_heads one = {{logits}};
+  return dec_decode("sca_ctc_greedy_decode", false,
+                    {DEC_GREEDY, &one, 1, in_len, {B, T, C, 1}, 0, 0, {}, tokens, out_len, score, nullptr, ws}, stream);
 }
 
 extern "C" int sca_ctc_beam_decode(const float* logits, const int* in_len, int B, int T, int C, int beam_width,
                                    int collapse_repeats, int* tokens, int* out_len, float* score, void* ws,
                                    void* stream) {
-  if (!dec_dims_ok(B, T, C, beam_width) || !logits || !in_len || !tokens || !out_len || !score || !ws) {
-    sca_set_error("sca_ctc_beam_decode: bad arguments (B, T >= 1, 1 <= C <= 8192, 1 <= beam_width <= 32)");
-    return SCA_ERR_ARG;
-  }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const DecDims d{B, T, C, beam_width};
-  const DecWs w(ws, d);
-  const DecHeads hx = dec_one_head(logits);
-  const long rows = (long)B * T;
-  sca_ctc_rowstat_launch(logits, w.rowstat, rows, C, st);
-  hipLaunchKernelGGL(ctc_topk_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, hx, 1, in_len, d, w);
-  hipLaunchKernelGGL(ctc_beam_kernel<false>, dim3(B), dim3(64), 0, st, hx, in_len, d, collapse_repeats != 0, 0, tokens,
-                     out_len, score, static_cast<int*>(nullptr), w, DecLm{});
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_ctc_beam_decode: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  const sca_decode_heads one = {{logits}};
+  return dec_decode("sca_ctc_beam_decode", false,
+                    {DEC_BEAM, &one, 1, in_len, {B, T, C, beam_width}, collapse_repeats != 0, 0, {}, tokens, out_len,
+                     score, nullptr, ws},
+                    stream);
 }
 
 extern "C" int sca_ctc_greedy_decode_heads(const sca_decode_heads* heads, int G, const int* in_len, int B, int T,
                                            int C, int* tokens, int* out_len, float* score, void* ws, void* stream) {
-  if (!dec_heads_ok(heads, G, B, T, C, 1) || !in_len || !tokens || !out_len || !score || !ws) {
-    sca_set_error("sca_ctc_greedy_decode_heads: bad arguments (1 <= G <= 8 non-null tensors, B, T >= 1, "
-                  "1 <= C <= 8192)");
-    return SCA_ERR_ARG;
-  }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const DecDims d{B, T, C, 1};
-  const DecWs w(ws, d, G);
-  const DecHeads hx = dec_heads_of(heads, G);
-  const long rows = (long)G * B * T;
-  hipLaunchKernelGGL(ctc_rowstat_heads_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, hx, w.rowstat, rows,
-                     (long)B * T, C);
-  hipLaunchKernelGGL(ctc_greedy_kernel, dim3(B, G), dim3(64 * GREEDY_WAVES), 0, st, hx, in_len, d, tokens, out_len,
-                     score, w);
-  if (hipGetLastError() != hipSuccess) {
-    sca_set_error("sca_ctc_greedy_decode_heads: launch failed");
-    return SCA_ERR_LAUNCH;
-  }
-  return SCA_OK;
+  return dec_decode("sca_ctc_greedy_decode_heads", true,
+                    {DEC_GREEDY, heads, G, in_len, {B, T, C, 1}, 0, 0, {}, tokens, out_len, score, nullptr, ws},
+                    stream);
 }
 
 extern "C" int sca_ctc_beam_decode_heads(const sca_decode_heads* heads, int G, const int* in_len, int B, int T, int C,
                                          int beam_width, int collapse_repeats, int* tokens, int* out_len, float* score,
                                          void* ws, void* stream) {
-  if (!dec_heads_ok(heads, G, B, T, C, beam_width) || !in_len || !tokens || !out_len || !score || !ws) {
-    sca_set_error("sca_ctc_beam_decode_heads: bad arguments (1 <= G <= 8 non-null tensors, B, T >= 1, "
-                  "1 <= C <= 8192, 1 <= beam_width <= 32)");
-    return SCA_ERR_ARG;
-  }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const DecDims d{B, T, C, beam_width};
-  const DecWs w(ws, d, G);
-  const DecHeads hx = dec_heads_of(heads, G);
-  const long rows = (long)G * B * T;
-  const dim3 row_grid((unsigned)((rows + 3) / 4));
-  hipLaunchKernelGGL(ctc_rowstat_heads_kernel, row_grid, dim3(256), 0, st, hx, w.rowstat, rows, (long)B * T, C);
-  hipLaunchKernelGGL(ctc_topk_kernel, row_grid, dim3(256), 0, st, hx, G, in_len, d, w);
-  hipLaunchKernelGGL(ctc_beam_kernel<false>, dim3(B, G), dim3(64), 0, st, hx, in_len, d, collapse_repeats != 0, 0,
-                     tokens, out_len, score, static_cast<int*>(nullptr), w, DecLm{});
-  if (hipGetLastError() != hipSuccess) {
-    sca_set_error("sca_ctc_beam_decode_heads: launch failed");
-    return SCA_ERR_LAUNCH;
-  }
-  return SCA_OK;
+  return dec_decode("sca_ctc_beam_decode_heads", true,
+                    {DEC_BEAM, heads, G, in_len, {B, T, C, beam_width}, collapse_repeats != 0, 0, {}, tokens, out_len,
+                     score, nullptr, ws},
+                    stream);
 }
 
 extern "C" int sca_wer_counts(const int* ref, const int* ref_len, const int* hyp, const int* hyp_len, int N,
@@ -1089,98 +1105,32 @@ extern "C" int sca_eval_accumulate(const int* tokens, const int* hyp_len, int G,
 extern "C" int sca_ctc_beam_decode_nbest(const float* logits, const int* in_len, int B, int T, int C, int beam_width,
                                          int nbest, int collapse_repeats, int* tokens, int* out_len, float* score,
                                          int* count, void* ws, void* stream) {
-  if (!dec_dims_ok(B, T, C, beam_width) || nbest < 1 || nbest > beam_width || !logits || !in_len || !tokens ||
-      !out_len || !score || !count || !ws) {
-    sca_set_error("sca_ctc_beam_decode_nbest: bad arguments (B, T >= 1, 1 <= C <= 8192, "
-                  "1 <= nbest <= beam_width <= 32)");
-    return SCA_ERR_ARG;
-  }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const DecDims d{B, T, C, beam_width};
-  const DecWs w(ws, d);
-  const DecHeads hx = dec_one_head(logits);
-  const long rows = (long)B * T;
-  sca_ctc_rowstat_launch(logits, w.rowstat, rows, C, st);
-  hipLaunchKernelGGL(ctc_topk_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, hx, 1, in_len, d, w);
-  hipLaunchKernelGGL(ctc_beam_kernel<true>, dim3(B), dim3(64), 0, st, hx, in_len, d, collapse_repeats != 0, nbest,
-                     tokens, out_len, score, count, w, DecLm{});
-  if (hipGetLastError() != hipSuccess) {
-    sca_set_error("sca_ctc_beam_decode_nbest: launch failed");
-    return SCA_ERR_LAUNCH;
-  }
-  return SCA_OK;
+  const sca_decode_heads one = {{logits}};
+  return dec_decode("sca_ctc_beam_decode_nbest", false,
+                    {DEC_NBEST, &one, 1, in_len, {B, T, C, beam_width}, collapse_repeats != 0, nbest, {}, tokens,
+                     out_len, score, count, ws},
+                    stream);
 }
 
 extern "C" int sca_ctc_beam_decode_heads_nbest(const sca_decode_heads* heads, int G, const int* in_len, int B, int T,
                                                int C, int beam_width, int nbest, int collapse_repeats, int* tokens,
                                                int* out_len, float* score, int* count, void* ws, void* stream) {
-  if (!dec_heads_ok(heads, G, B, T, C, beam_width) || nbest < 1 || nbest > beam_width || !in_len || !tokens ||
-      !out_len || !score || !count || !ws) {
-    sca_set_error("sca_ctc_beam_decode_heads_nbest: bad arguments (1 <= G <= 8 non-null tensors, B, T >= 1, "
-                  "1 <= C <= 8192, 1 <= nbest <= beam_width <= 32)");
-    return SCA_ERR_ARG;
-  }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const DecDims d{B, T, C, beam_width};
-  const DecWs w(ws, d, G);
-  const DecHeads hx = dec_heads_of(heads, G);
-  const long rows = (long)G * B * T;
-  const dim3 row_grid((unsigned)((rows + 3) / 4));
-  hipLaunchKernelGGL(ctc_rowstat_heads_kernel, row_grid, dim3(256), 0, st, hx, w.rowstat, rows, (long)B * T, C);
-  hipLaunchKernelGGL(ctc_topk_kernel, row_grid, dim3(256), 0, st, hx, G, in_len, d, w);
-  hipLaunchKernelGGL(ctc_beam_kernel<true>, dim3(B, G), dim3(64), 0, st, hx, in_len, d, collapse_repeats != 0, nbest,
-                     tokens, out_len, score, count, w, DecLm{});
-  if (hipGetLastError() != hipSuccess) {
-    sca_set_error("sca_ctc_beam_decode_heads_nbest: launch failed");
-    return SCA_ERR_LAUNCH;
-  }
-  return SCA_OK;
+  return dec_decode("sca_ctc_beam_decode_heads_nbest", true,
+                    {DEC_NBEST, heads, G, in_len, {B, T, C, beam_width}, collapse_repeats != 0, nbest, {}, tokens,
+                     out_len, score, count, ws},
+                    stream);
 }
 
-// ---- shallow fusion: the bigram model inside the search (include/scatten.h) ----
-namespace {
-
-bool fused_args_ok(int nbest, int beam_width, float lm_weight, float length_bonus, const void* in_len,
-                   const void* tokens, const void* out_len, const void* score, const void* count, const void* ws) {
-  return nbest >= 1 && nbest <= beam_width && lm_weight - lm_weight == 0.0f && length_bonus - length_bonus == 0.0f &&
-         in_len && tokens && out_len && score && count && ws;
-}
-
-// two launches: the row statistics, then the frame recursion (no shared label list to precompute)
-int fused_launch(const char* what, DecHeads hx, int G, const int* in_len, DecDims d, int nbest, int collapse,
-                 DecLm f, int* tokens, int* out_len, float* score, int* count, void* ws, hipStream_t st) {
-  const DecWs w(ws, d, G);
-  const long rows = (long)G * d.B * d.T;
-  hipLaunchKernelGGL(ctc_rowstat_heads_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, hx, w.rowstat, rows,
-                     (long)d.B * d.T, d.C);
-  hipLaunchKernelGGL((ctc_beam_kernel<true, true>), dim3(d.B, G), dim3(64), 0, st, hx, in_len, d, collapse, nbest,
-                     tokens, out_len, score, count, w, f);
-  if (hipGetLastError() != hipSuccess) {
-    sca_set_error(what);
-    return SCA_ERR_LAUNCH;
-  }
-  return SCA_OK;
-}
-
-}  // namespace
-
-extern "C" long sca_ctc_fused_workspace_bytes(int G, int B, int T, int C, int W) {
-  return sca_ctc_decode_heads_workspace_bytes(G, B, T, C, W);  // the same layout; cls holds the tail's rows only
-}
-
+// shallow fusion: the bigram model inside the search (include/scatten.h)
 extern "C" int sca_ctc_beam_decode_fused_nbest(const float* logits, const int* in_len, int B, int T, int C,
                                                int beam_width, int nbest, int collapse_repeats, const float* lm,
                                                float lm_weight, float length_bonus, int* tokens, int* out_len,
                                                float* score, int* count, void* ws, void* stream) {
-  if (!dec_dims_ok(B, T, C, beam_width) || !logits ||
-      !fused_args_ok(nbest, beam_width, lm_weight, length_bonus, in_len, tokens, out_len, score, count, ws)) {
-    sca_set_error("sca_ctc_beam_decode_fused_nbest: bad arguments (B, T >= 1, 1 <= C <= 8192, "
-                  "1 <= nbest <= beam_width <= 32, finite weights)");
-    return SCA_ERR_ARG;
-  }
-  return fused_launch("sca_ctc_beam_decode_fused_nbest: launch failed", dec_one_head(logits), 1, in_len,
-                      DecDims{B, T, C, beam_width}, nbest, collapse_repeats != 0, DecLm{lm, lm_weight, length_bonus},
-                      tokens, out_len, score, count, ws, reinterpret_cast<hipStream_t>(stream));
+  const sca_decode_heads one = {{logits}};
+  return dec_decode("sca_ctc_beam_decode_fused_nbest", false,
+                    {DEC_FUSED, &one, 1, in_len, {B, T, C, beam_width}, collapse_repeats != 0, nbest,
+                     {lm, lm_weight, length_bonus}, tokens, out_len, score, count, ws},
+                    stream);
 }
 
 extern "C" int sca_ctc_beam_decode_heads_fused_nbest(const sca_decode_heads* heads, int G, const int* in_len, int B,
@@ -1188,15 +1138,10 @@ extern "C" int sca_ctc_beam_decode_heads_fused_nbest(const sca_decode_heads* hea
                                                      const float* lm, float lm_weight, float length_bonus,
                                                      int* tokens, int* out_len, float* score, int* count, void* ws,
                                                      void* stream) {
-  if (!dec_heads_ok(heads, G, B, T, C, beam_width) ||
-      !fused_args_ok(nbest, beam_width, lm_weight, length_bonus, in_len, tokens, out_len, score, count, ws)) {
-    sca_set_error("sca_ctc_beam_decode_heads_fused_nbest: bad arguments (1 <= G <= 8 non-null tensors, B, T >= 1, "
-                  "1 <= C <= 8192, 1 <= nbest <= beam_width <= 32, finite weights)");
-    return SCA_ERR_ARG;
-  }
-  return fused_launch("sca_ctc_beam_decode_heads_fused_nbest: launch failed", dec_heads_of(heads, G), G, in_len,
-                      DecDims{B, T, C, beam_width}, nbest, collapse_repeats != 0, DecLm{lm, lm_weight, length_bonus},
-                      tokens, out_len, score, count, ws, reinterpret_cast<hipStream_t>(stream));
+  return dec_decode("sca_ctc_beam_decode_heads_fused_nbest", true,
+                    {DEC_FUSED, heads, G, in_len, {B, T, C, beam_width}, collapse_repeats != 0, nbest,
+                     {lm, lm_weight, length_bonus}, tokens, out_len, score, count, ws},
+                    stream);
 }
 
 extern "C" int sca_nbest_rescore(const int* tokens, const int* out_len, const float* score, const int* count, int G,

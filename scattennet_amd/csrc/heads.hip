@@ -69,17 +69,7 @@ __global__ __launch_bounds__(256) void ctc_rowstat_kernel(const float* __restric
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= rows) return;
-  const float* xr = x + row * C;
-  float m = NEG_INF;
-  for (int c = lane; c < C; c += 64) m = fmaxf(m, xr[c]);
-  m = wave_max(m);
-  float s = 0.0f;
-  for (int c = lane; c < C; c += 64) s += __expf(xr[c] - m);
-  s = wave_sum(s);
-  if (lane == 0) {
-    rowstat[2 * row] = m;
-    rowstat[2 * row + 1] = __logf(s);
-  }
+  ctc_row_stat(x + row * C, C, lane, rowstat + 2 * row);
 }
 
 // grid (B, 2): y = 0 runs the alpha (forward) recursion, y = 1 the beta (backward) one

@@ -21,7 +21,7 @@ import torch
 from torch import nn
 
 from . import _lib as L
-from .decode import _check_device, _check_logits
+from .decode import check_heads, check_on_device
 from .model import _LOGITS
 from .precision import fp32_compute
 
@@ -62,9 +62,8 @@ class _Ensembler(nn.Module):
         G = len(xs)
         B, T, C = xs[0].shape
         out = torch.empty_like(xs[0])
-        hx, wx = L.DecodeHeads(), L.EnsembleWeights()
-        for g, x in enumerate(xs):
-            hx.logits[g] = x.data_ptr()
+        hx, wx = L.decode_heads(xs), L.EnsembleWeights()
+        for g in range(G):
             wx.w[g] = weights[g]
         L.check(L.lib().sca_ensemble_log_probs(ctypes.byref(hx), G, ctypes.byref(wx), mode, B, T, C, L.ptr(out),
                                                L.stream_handle()), "sca_ensemble_log_probs")
@@ -74,23 +73,6 @@ class _Ensembler(nn.Module):
 _ensembler = _Ensembler()
 
 
-def _check_heads(logits_list):
-    xs = list(logits_list)
-    if not 1 <= len(xs) <= MAX_HEADS:
-        raise ValueError(f"ensemble_log_probs: between 1 and {MAX_HEADS} logit tensors, got {len(xs)}")
-    for x in xs:
-        _check_logits(x)
-    first = xs[0]
-    for x in xs[1:]:
-        if x.shape != first.shape or x.dtype != first.dtype or x.device != first.device:
-            raise ValueError("ensemble_log_probs: every head must have the same shape, dtype and device; got "
-                             f"{tuple(first.shape)} {first.dtype} {first.device} and {tuple(x.shape)} {x.dtype} "
-                             f"{x.device}")
-    if first.numel() == 0:
-        raise ValueError(f"ensemble_log_probs: empty logits {tuple(first.shape)}")
-    return xs
-
-
 def ensemble_log_probs(logits_list, weights=None, mode="prob"):
     """The ensemble of G heads' posteriors as normalised log-probabilities, in one launch
     (`sca_ensemble_log_probs`).  `logits_list`: 1..8 tensors of one shape (B, T, C); `weights`:
@@ -98,10 +80,12 @@ def ensemble_log_probs(logits_list, weights=None, mode="prob"):
     arithmetic mean of the posteriors (log sum_g w_g softmax(x_g)), or "logprob", the log-linear
     mean renormalised (log_softmax(sum_g w_g log_softmax(x_g))).  With G = 1 both are the rows'
     log_softmax.  Returns a detached (B, T, C) device tensor.  No host sync; capturable."""
-    xs = _check_heads(logits_list)
+    xs = check_heads(logits_list, "ensemble_log_probs")
+    if xs[0].numel() == 0:
+        raise ValueError(f"ensemble_log_probs: empty logits {tuple(xs[0].shape)}")
     ws = _check_weights(weights, len(xs), "ensemble_log_probs")
     m = _check_mode(mode, "ensemble_log_probs")
-    _check_device(xs[0])
+    check_on_device(None, xs[0])
     return _ensembler(ws, m, *xs)
 
 

@@ -2,9 +2,8 @@
 every evaluated head in one grouped launch, WER counts and the pass's totals, with no host
 read until the pass is over.
 
-* `ctc_decode_heads_device` — `sca_ctc_beam_decode_heads` / `sca_ctc_greedy_decode_heads`: the
-  G logit tensors of one forward decoded together, bitwise what `ctc_decode_device` gives per
-  head.
+* `ctc_decode_heads_device` (decode.py, exported here too) — the G logit tensors of one forward
+  decoded together.
 * `EvalState` — the pass's device state (`sca_eval_state`, include/scatten.h): per-head WER
   totals, float64 loss sums, the OR of the finite guard's flag words, and an optional log of
   every hypothesis.  `read()` is the single host read and returns the dict `evaluate_fn`
@@ -31,18 +30,16 @@ import ctypes
 
 import numpy as np
 import torch
-from torch import nn
 
 from . import _lib as L
 from .bucketed import BucketedStep, check_buckets
 from .align import alignment_lists, ctc_align_heads_device
-from .decode import MAX_BEAM, WER_MAX_LEN, _check_device, _check_lengths, _check_logits, wer_from_counts
+from .decode import WER_MAX_LEN, ctc_decode_heads_device, wer_from_counts
 from .encoder import n_pool_of
 from .ensemble import add_ensembles, check_ensembles
 from .heads import _dev_i32, labels_2d
 from .model import _LOGITS, _students_of, deferred_check, first_error, flag_names
 from .nbest import check_rescoring, rescored_decode
-from .precision import fp32_compute
 
 MAX_HEADS = L.EVAL_MAX_HEADS
 
@@ -71,71 +68,6 @@ def check_head_keys(heads, what):
 def loss_names(students=()):
     """The loss words of `finite_report` that a pass sums, in report order."""
     return ["alignment_loss", "fuse_coord_loss"] + [f"{s}_distill_loss" for s in students] + ["total_loss"]
-
-
-# ------------------------------------------------------------------------ grouped decoding
-class _HeadsDecoder(nn.Module):
-    """Parameter-free module, so that fp16 / bf16 logits take the fp32 view of fp32_compute."""
-
-    @fp32_compute()
-    def forward(self, in_len, beam, collapse, *logits):
-        xs = [x.detach().contiguous() for x in logits]
-        L.require_device(*xs)
-        G = len(xs)
-        B, T, C = xs[0].shape
-        lib = L.lib()
-        nbytes = lib.sca_ctc_decode_heads_workspace_bytes(G, B, T, C, max(beam, 1))
-        dev = xs[0].device
-        tokens = torch.empty(G, B, T, dtype=torch.int32, device=dev)
-        lengths = torch.empty(G, B, dtype=torch.int32, device=dev)
-        scores = xs[0].new_empty(G, B)
-        ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.int64, device=dev)
-        hx = L.DecodeHeads()
-        for g, x in enumerate(xs):
-            hx.logits[g] = x.data_ptr()
-        if beam == 0:
-            L.check(lib.sca_ctc_greedy_decode_heads(ctypes.byref(hx), G, L.ptr(in_len), B, T, C, L.ptr(tokens),
-                                                    L.ptr(lengths), L.ptr(scores), L.ptr(ws), L.stream_handle()),
-                    "sca_ctc_greedy_decode_heads")
-        else:
-            L.check(lib.sca_ctc_beam_decode_heads(ctypes.byref(hx), G, L.ptr(in_len), B, T, C, beam, int(collapse),
-                                                  L.ptr(tokens), L.ptr(lengths), L.ptr(scores), L.ptr(ws),
-                                                  L.stream_handle()), "sca_ctc_beam_decode_heads")
-        return tokens, lengths, scores
-
-
-_heads_decoder = _HeadsDecoder()
-
-
-def _check_heads(logits_list):
-    xs = list(logits_list)
-    if not 1 <= len(xs) <= MAX_HEADS:
-        raise ValueError(f"ctc_decode_heads: between 1 and {MAX_HEADS} logit tensors, got {len(xs)}")
-    for x in xs:
-        _check_logits(x)
-    first = xs[0]
-    for x in xs[1:]:
-        if x.shape != first.shape or x.dtype != first.dtype or x.device != first.device:
-            raise ValueError("ctc_decode_heads: every head must have the same shape, dtype and device; got "
-                             f"{tuple(first.shape)} {first.dtype} {first.device} and {tuple(x.shape)} {x.dtype} "
-                             f"{x.device}")
-    return xs
-
-
-def ctc_decode_heads_device(logits_list, input_lengths, beam_size=1, collapse_repeats=True):
-    """`ctc_decode_device` over the G heads of one forward in one grouped call
-    (`sca_ctc_beam_decode_heads`; `beam_size=0`: `sca_ctc_greedy_decode_heads`).  `logits_list`:
-    1..8 tensors of one shape (B, T, C), all decoded with `input_lengths` (B).  Returns (tokens
-    (G, B, T) int32 padded with 0, lengths (G, B) int32, scores (G, B)) on the device: row g is
-    bitwise what the single-head call returns for `logits_list[g]`.  No host sync; capturable."""
-    xs = _check_heads(logits_list)
-    beam = int(beam_size)
-    if beam and not 1 <= beam <= MAX_BEAM:
-        raise ValueError(f"ctc_decode: beam_size must lie in [1, {MAX_BEAM}], got {beam}")
-    B, T, _ = xs[0].shape
-    il = _check_lengths(input_lengths, B, T)
-    _check_device(xs[0])
-    return _heads_decoder(_dev_i32(il, xs[0].device), beam, bool(collapse_repeats), *xs)
 
 
 # ------------------------------------------------------------------------------ the state

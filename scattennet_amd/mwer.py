@@ -17,10 +17,10 @@ import torch
 from torch.autograd import Function
 
 from . import _lib as L
-from .decode import MAX_BEAM, WER_MAX_LEN, _check_device, _check_lengths, _check_logits
+from .decode import MAX_BEAM, WER_MAX_LEN, _check_lengths, _check_logits, check_on_device
 from .heads import _dev_i32
 from .model import _LOGITS
-from .nbest import MAX_CLASSES, _check_beam, _check_nbest, _check_on_device, _finite, ctc_decode_nbest_device
+from .nbest import MAX_CLASSES, _check_beam, _check_nbest, _finite, ctc_decode_nbest_device
 
 
 class MWERLossOp(Function):
@@ -115,13 +115,13 @@ def mwer_loss(gloss_logits, input_lengths, gloss_labels, gloss_lengths, nbest=No
                                f"{tuple(nbest.tokens.shape)}")
         if H > WER_MAX_LEN:
             raise ValueError(f"{what}: hypotheses of up to {H} tokens exceed the WER kernel's {WER_MAX_LEN}")
-    _check_device(gloss_logits)
+    check_on_device(None, gloss_logits)
     dev = gloss_logits.device
     in_len = _dev_i32(il, dev)
     if nbest is None:
         nbest = ctc_decode_nbest_device(gloss_logits, in_len, beam, n, collapse_repeats=False)
     else:
-        _check_on_device(what, nbest.tokens, nbest.lengths, nbest.count)
+        check_on_device(what, nbest.tokens, nbest.lengths, nbest.count)
     x = gloss_logits if gloss_logits.dtype == torch.float32 else gloss_logits.float()
     loss, loglik, posterior, errors, risk = MWERLossOp.apply(
         x, in_len, _dev_i32(nbest.tokens, dev), _dev_i32(nbest.lengths, dev), _dev_i32(nbest.count, dev),

@@ -25,17 +25,14 @@ No call reads the device or allocates outside the caching allocator: everything 
 entries are merged and the list re-sorted, so entry 0 may differ from `ctc_decode_device`'s result.
 """
 import collections
-import ctypes
 import math
 
 import numpy as np
 import torch
-from torch import nn
 
 from . import _lib as L
-from .decode import MAX_BEAM, WER_MAX_LEN, _check_device, _check_lengths, _check_logits
+from .decode import MAX_BEAM, WER_MAX_LEN, _check_lengths, _check_logits, _decoder, check_heads, check_on_device
 from .heads import _dev_i32
-from .precision import fp32_compute
 
 MAX_HEADS = L.EVAL_MAX_HEADS
 MAX_CLASSES = 8192  # SCA_CTC_MAX_C
@@ -45,91 +42,6 @@ NBest = collections.namedtuple("NBest", "tokens lengths scores count")
 
 
 # ------------------------------------------------------------------------------ the decode
-class _NBestDecoder(nn.Module):
-    """Parameter-free module, so that fp16 / bf16 logits take the fp32 view of fp32_compute."""
-
-    @fp32_compute()
-    def forward(self, in_len, beam, nbest, collapse, *logits):
-        xs = [x.detach().contiguous() for x in logits]
-        L.require_device(*xs)
-        G = len(xs)
-        B, T, C = xs[0].shape
-        lib = L.lib()
-        nbytes = lib.sca_ctc_decode_heads_workspace_bytes(G, B, T, C, beam)
-        dev = xs[0].device
-        tokens = torch.empty(G, B, nbest, T, dtype=torch.int32, device=dev)
-        lengths = torch.empty(G, B, nbest, dtype=torch.int32, device=dev)
-        scores = xs[0].new_empty(G, B, nbest)
-        count = torch.empty(G, B, dtype=torch.int32, device=dev)
-        ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.int64, device=dev)
-        hx = L.DecodeHeads()
-        for g, x in enumerate(xs):
-            hx.logits[g] = x.data_ptr()
-        L.check(lib.sca_ctc_beam_decode_heads_nbest(ctypes.byref(hx), G, L.ptr(in_len), B, T, C, beam, nbest,
-                                                    int(collapse), L.ptr(tokens), L.ptr(lengths), L.ptr(scores),
-                                                    L.ptr(count), L.ptr(ws), L.stream_handle()),
-                "sca_ctc_beam_decode_heads_nbest")
-        return tokens, lengths, scores, count
-
-
-class _NBestDecoderOne(nn.Module):
-    """The single-head entry point (`sca_ctc_beam_decode_nbest`)."""
-
-    @fp32_compute()
-    def forward(self, logits, in_len, beam, nbest, collapse):
-        x = logits.detach().contiguous()
-        L.require_device(x)
-        B, T, C = x.shape
-        lib = L.lib()
-        nbytes = lib.sca_ctc_decode_workspace_bytes(B, T, C, beam)
-        tokens = torch.empty(B, nbest, T, dtype=torch.int32, device=x.device)
-        lengths = torch.empty(B, nbest, dtype=torch.int32, device=x.device)
-        scores = x.new_empty(B, nbest)
-        count = torch.empty(B, dtype=torch.int32, device=x.device)
-        ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.int64, device=x.device)
-        L.check(lib.sca_ctc_beam_decode_nbest(L.ptr(x), L.ptr(in_len), B, T, C, beam, nbest, int(collapse),
-                                              L.ptr(tokens), L.ptr(lengths), L.ptr(scores), L.ptr(count), L.ptr(ws),
-                                              L.stream_handle()), "sca_ctc_beam_decode_nbest")
-        return tokens, lengths, scores, count
-
-
-class _FusedDecoder(nn.Module):
-    """`sca_ctc_beam_decode_heads_fused_nbest`, or with `grouped=False` the single-head entry
-    point on `logits[0]`.  `table` is a keyword so that the logits decide the module's dtype."""
-
-    @fp32_compute()
-    def forward(self, in_len, beam, nbest, collapse, lm_weight, length_bonus, grouped, *logits, table=None):
-        xs = [x.detach().contiguous() for x in logits]
-        L.require_device(*xs)
-        G = len(xs)
-        B, T, C = xs[0].shape
-        lib = L.lib()
-        nbytes = lib.sca_ctc_fused_workspace_bytes(G, B, T, C, beam)
-        dev = xs[0].device
-        lead = (G, B) if grouped else (B,)
-        tokens = torch.empty(lead + (nbest, T), dtype=torch.int32, device=dev)
-        lengths = torch.empty(lead + (nbest,), dtype=torch.int32, device=dev)
-        scores = xs[0].new_empty(lead + (nbest,))
-        count = torch.empty(lead, dtype=torch.int32, device=dev)
-        ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.int64, device=dev)
-        lm = None if table is None else L.ptr(table)
-        tail = (B, T, C, beam, nbest, int(collapse), lm, lm_weight, length_bonus, L.ptr(tokens), L.ptr(lengths),
-                L.ptr(scores), L.ptr(count), L.ptr(ws), L.stream_handle())
-        if grouped:
-            hx = L.DecodeHeads()
-            for g, x in enumerate(xs):
-                hx.logits[g] = x.data_ptr()
-            L.check(lib.sca_ctc_beam_decode_heads_fused_nbest(ctypes.byref(hx), G, L.ptr(in_len), *tail),
-                    "sca_ctc_beam_decode_heads_fused_nbest")
-        else:
-            L.check(lib.sca_ctc_beam_decode_fused_nbest(L.ptr(xs[0]), L.ptr(in_len), *tail),
-                    "sca_ctc_beam_decode_fused_nbest")
-        return tokens, lengths, scores, count
-
-
-_decoder_heads, _decoder_one, _decoder_fused = _NBestDecoder(), _NBestDecoderOne(), _FusedDecoder()
-
-
 def _check_beam(beam_size, nbest):
     beam = int(beam_size)
     if not 1 <= beam <= MAX_BEAM:
@@ -139,21 +51,6 @@ def _check_beam(beam_size, nbest):
     if not 1 <= n <= beam:
         raise ValueError(f"ctc_decode_nbest: nbest must lie in [1, beam_size = {beam}], got {n}")
     return beam, n
-
-
-def _check_heads(logits_list):
-    xs = list(logits_list)
-    if not 1 <= len(xs) <= MAX_HEADS:
-        raise ValueError(f"ctc_decode_nbest_heads: between 1 and {MAX_HEADS} logit tensors, got {len(xs)}")
-    for x in xs:
-        _check_logits(x)
-    first = xs[0]
-    for x in xs[1:]:
-        if x.shape != first.shape or x.dtype != first.dtype or x.device != first.device:
-            raise ValueError("ctc_decode_nbest_heads: every head must have the same shape, dtype and device; got "
-                             f"{tuple(first.shape)} {first.dtype} {first.device} and {tuple(x.shape)} {x.dtype} "
-                             f"{x.device}")
-    return xs
 
 
 def ctc_decode_nbest_device(gloss_logits, input_lengths, beam_size, nbest=None, collapse_repeats=True):
@@ -167,20 +64,21 @@ def ctc_decode_nbest_device(gloss_logits, input_lengths, beam_size, nbest=None, 
     B, T, _ = gloss_logits.shape
     beam, n = _check_beam(beam_size, nbest)
     il = _check_lengths(input_lengths, B, T)
-    _check_device(gloss_logits)
-    return NBest(*_decoder_one(gloss_logits, _dev_i32(il, gloss_logits.device), beam, n, bool(collapse_repeats)))
+    check_on_device(None, gloss_logits)
+    return NBest(*_decoder("nbest", _dev_i32(il, gloss_logits.device), beam, n, bool(collapse_repeats), 0.0, 0.0,
+                           False, gloss_logits))
 
 
 def ctc_decode_nbest_heads_device(logits_list, input_lengths, beam_size, nbest=None, collapse_repeats=True):
     """`ctc_decode_nbest_device` over the G heads of one forward in one grouped call: an `NBest`
     of tokens (G, B, N, T), lengths (G, B, N), scores (G, B, N), count (G, B); row g is bitwise
     the single-head call's for `logits_list[g]`."""
-    xs = _check_heads(logits_list)
+    xs = check_heads(logits_list, "ctc_decode_nbest_heads")
     beam, n = _check_beam(beam_size, nbest)
     B, T, _ = xs[0].shape
     il = _check_lengths(input_lengths, B, T)
-    _check_device(xs[0])
-    return NBest(*_decoder_heads(_dev_i32(il, xs[0].device), beam, n, bool(collapse_repeats), *xs))
+    check_on_device(None, xs[0])
+    return NBest(*_decoder("nbest", _dev_i32(il, xs[0].device), beam, n, bool(collapse_repeats), 0.0, 0.0, True, *xs))
 
 
 def nbest_lists(tokens, lengths, values, count, extra=None, order=None):
@@ -251,10 +149,10 @@ def ctc_decode_fused_nbest_device(gloss_logits, input_lengths, beam_size, lm, lm
     beam, n = _check_beam(beam_size, nbest)
     il = _check_lengths(input_lengths, B, T)
     lw, lb = _check_fusion(lm, lm_weight, length_bonus, C, what)
-    _check_device(gloss_logits)
+    check_on_device(None, gloss_logits)
     table = _fusion_table(lm, gloss_logits.device, what)
-    return NBest(*_decoder_fused(_dev_i32(il, gloss_logits.device), beam, n, bool(collapse_repeats), lw, lb, False,
-                                 gloss_logits, table=table))
+    return NBest(*_decoder("fused", _dev_i32(il, gloss_logits.device), beam, n, bool(collapse_repeats), lw, lb, False,
+                           gloss_logits, table=table))
 
 
 def ctc_decode_fused_nbest_heads_device(logits_list, input_lengths, beam_size, lm, lm_weight=0.0, length_bonus=0.0,
@@ -262,15 +160,15 @@ def ctc_decode_fused_nbest_heads_device(logits_list, input_lengths, beam_size, l
     """`ctc_decode_fused_nbest_device` over the G heads of one forward in one grouped call, shaped
     like `ctc_decode_nbest_heads_device`'s result; row g is bitwise the single-head call's."""
     what = "ctc_decode_fused_nbest_heads"
-    xs = _check_heads(logits_list)
+    xs = check_heads(logits_list, "ctc_decode_nbest_heads")
     beam, n = _check_beam(beam_size, nbest)
     B, T, C = xs[0].shape
     il = _check_lengths(input_lengths, B, T)
     lw, lb = _check_fusion(lm, lm_weight, length_bonus, C, what)
-    _check_device(xs[0])
+    check_on_device(None, xs[0])
     table = _fusion_table(lm, xs[0].device, what)
-    return NBest(*_decoder_fused(_dev_i32(il, xs[0].device), beam, n, bool(collapse_repeats), lw, lb, True, *xs,
-                                 table=table))
+    return NBest(*_decoder("fused", _dev_i32(il, xs[0].device), beam, n, bool(collapse_repeats), lw, lb, True, *xs,
+                           table=table))
 
 
 def ctc_decode_fused_nbest(gloss_logits, beam_size, input_lengths, lm, lm_weight=0.0, length_bonus=0.0, nbest=None,
@@ -354,13 +252,6 @@ def _check_nbest(nb, what):
     return G, B, N, T
 
 
-def _check_on_device(what, *tensors):
-    for t in tensors:
-        if not t.is_cuda:
-            raise RuntimeError(f"{what}: scattennet_amd ops run only on ROCm (MI355X) tensors; got {t.device} "
-                               f"{t.dtype}.  There is no CPU fallback.")
-
-
 def _i32(t):
     return t.to(torch.int32).contiguous()
 
@@ -388,9 +279,9 @@ def rescore_nbest_device(nb, lm=None, lm_weight=0.0, length_bonus=0.0, posterior
         raise ValueError(f"{what}: lm must be a BigramLM or None, got {type(lm).__name__}")
     lw, lb, ps = (_finite(n, v, what) for n, v in (("lm_weight", lm_weight), ("length_bonus", length_bonus),
                                                    ("posterior_scale", posterior_scale)))
-    _check_on_device(what, *nb)
+    check_on_device(what, *nb)
     if lm is not None:
-        _check_on_device(what, lm.table)
+        check_on_device(what, lm.table)
     tokens, lengths, count = _i32(nb.tokens), _i32(nb.lengths), _i32(nb.count)
     scores = _f32(nb.scores)
     total, posterior = torch.empty_like(scores), torch.empty_like(scores)
@@ -413,7 +304,7 @@ def mbr_select_device(nb, posterior):
         raise ValueError(f"{what}: hypotheses of up to {T} tokens exceed the WER kernel's {WER_MAX_LEN}")
     if not torch.is_tensor(posterior) or posterior.shape != nb.lengths.shape:
         raise RuntimeError(f"{what}: posterior must be a tensor shaped like the list's scores {tuple(nb.lengths.shape)}")
-    _check_on_device(what, *nb, posterior)
+    check_on_device(what, *nb, posterior)
     tokens, lengths, count, post = _i32(nb.tokens), _i32(nb.lengths), _i32(nb.count), _f32(posterior)
     loss = torch.empty(tuple(lengths.shape) + (N,), dtype=torch.int32, device=tokens.device)
     risk = torch.empty_like(post)
@@ -431,7 +322,7 @@ def select_device(nb, values, index):
     lead = tuple(nb.count.shape)
     if tuple(index.shape) not in (lead, lead + (N,)) or values.shape != nb.lengths.shape:
         raise RuntimeError(f"{what}: index must be shaped {lead} or {lead + (N,)} and values {tuple(nb.lengths.shape)}")
-    _check_on_device(what, *nb, values, index)
+    check_on_device(what, *nb, values, index)
     stride = N if index.dim() == nb.lengths.dim() else 1
     tokens, lengths, idx, val = _i32(nb.tokens), _i32(nb.lengths), _i32(index), _f32(values)
     tokens1 = torch.empty(lead + (T,), dtype=torch.int32, device=tokens.device)
@@ -513,7 +404,7 @@ def rescored_decode(logits_list, input_lengths, beam_size, rescoring, what="resc
     `nbest_tokens` (G, B, N, T), `nbest_lengths`, `nbest_totals`, `nbest_posterior`, `nbest_order`
     (G, B, N), `nbest_count` (G, B), and with "mbr" `nbest_risk` (G, B, N), `nbest_best` (G, B).
     No host read."""
-    xs = _check_heads(logits_list)
+    xs = check_heads(logits_list, "ctc_decode_nbest_heads")
     check_rescoring(rescoring, beam_size, what, xs[0].shape[2], xs[0].shape[1])
     if rescoring.fusion:
         nb = ctc_decode_fused_nbest_heads_device(xs, input_lengths, beam_size, rescoring.lm, rescoring.lm_weight,

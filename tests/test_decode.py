@@ -112,6 +112,93 @@ def test_argument_validation_makes_no_gpu_call():
     assert all(a < b for a, b in zip(by_t, by_t[1:])) and all(a < b for a, b in zip(by_w, by_w[1:]))
 
 
+# The eight decoders: name -> (grouped, mode, the text sca_last_error() holds after a rejection).
+_ONE, _HEADS = "B, T >= 1, 1 <= C <= 8192", "1 <= G <= 8 non-null tensors, B, T >= 1, 1 <= C <= 8192"
+DECODERS = {
+    "sca_ctc_greedy_decode": (False, "greedy", f"sca_ctc_greedy_decode: bad arguments ({_ONE})"),
+    "sca_ctc_beam_decode": (False, "beam", f"sca_ctc_beam_decode: bad arguments ({_ONE}, 1 <= beam_width <= 32)"),
+    "sca_ctc_greedy_decode_heads": (True, "greedy", f"sca_ctc_greedy_decode_heads: bad arguments ({_HEADS})"),
+    "sca_ctc_beam_decode_heads": (True, "beam",
+                                  f"sca_ctc_beam_decode_heads: bad arguments ({_HEADS}, 1 <= beam_width <= 32)"),
+    "sca_ctc_beam_decode_nbest": (False, "nbest", f"sca_ctc_beam_decode_nbest: bad arguments ({_ONE}, "
+                                                  "1 <= nbest <= beam_width <= 32)"),
+    "sca_ctc_beam_decode_heads_nbest": (True, "nbest", f"sca_ctc_beam_decode_heads_nbest: bad arguments ({_HEADS}, "
+                                                       "1 <= nbest <= beam_width <= 32)"),
+    "sca_ctc_beam_decode_fused_nbest": (False, "fused", f"sca_ctc_beam_decode_fused_nbest: bad arguments ({_ONE}, "
+                                                        "1 <= nbest <= beam_width <= 32, finite weights)"),
+    "sca_ctc_beam_decode_heads_fused_nbest": (True, "fused",
+                                              f"sca_ctc_beam_decode_heads_fused_nbest: bad arguments ({_HEADS}, "
+                                              "1 <= nbest <= beam_width <= 32, finite weights)"),
+}
+
+
+def _bad_decoder_calls(grouped, mode):
+    """The overrides of one valid call (G = 2, B = 2, T = 8, C = 16, W = 5, nbest = 3) that each
+    make it unsupported."""
+    bad = [{"B": 0}, {"T": 0}, {"C": 0}, {"C": 8193}]
+    bad += [{k: None} for k in ("in_len", "tokens", "out_len", "score", "ws", "heads" if grouped else "logits")]
+    if mode != "greedy":
+        bad += [{"W": 0, "N": 0}, {"W": 33}]
+    if mode in ("nbest", "fused"):
+        bad += [{"N": 0}, {"N": 6}, {"count": None}]
+    if mode == "fused":
+        bad += [{"lw": float("inf")}, {"lw": float("nan")}, {"lb": float("-inf")}, {"lb": float("nan")}]
+    if grouped:
+        bad += [{"G": 0}, {"G": 9}, {"hole": 0}, {"hole": 1}]
+    return bad
+
+
+@pytest.mark.parametrize("name", sorted(DECODERS))
+def test_every_decoder_rejects_the_same_bad_arguments_before_any_gpu_call(name):
+    """One matrix of unsupported arguments over the eight decoder entry points: each case is
+    SCA_ERR_ARG (nothing valid is ever passed, so a launch would crash) and leaves exactly the
+    entry point's own message in sca_last_error()."""
+    from scattennet_amd import _lib as L
+    lib = ctypes.CDLL(L.LIB_PATH)
+    for sym in (name, "sca_wer_counts", "sca_last_error"):
+        getattr(lib, sym).argtypes, getattr(lib, sym).restype = L.EXPORTS[sym]
+    grouped, mode, message = DECODERS[name]
+    p = ctypes.c_void_p(0x1000)  # never dereferenced
+    for over in _bad_decoder_calls(grouped, mode):
+        a = dict(G=2, B=2, T=8, C=16, W=5, N=3, lw=0.5, lb=0.25, hole=None, heads=L.DecodeHeads(), logits=p, in_len=p,
+                 tokens=p, out_len=p, score=p, count=p, ws=p)
+        a.update(over)
+        if a["heads"] is not None:
+            for g in range(min(max(a["G"], 0), 8)):
+                a["heads"].logits[g] = None if g == a["hole"] else 0x1000
+        args = [None if a["heads"] is None else ctypes.byref(a["heads"]), a["G"]] if grouped else [a["logits"]]
+        args += [a["in_len"], a["B"], a["T"], a["C"]]
+        args += {"greedy": [], "beam": [a["W"], 1], "nbest": [a["W"], a["N"], 1],
+                 "fused": [a["W"], a["N"], 1, p, a["lw"], a["lb"]]}[mode]
+        args += [a["tokens"], a["out_len"], a["score"]] + ([a["count"]] if mode in ("nbest", "fused") else [])
+        assert lib.sca_wer_counts(None, None, None, None, 0, 0, 0, None, None) == ERR_ARG  # another message
+        assert lib.sca_last_error().decode() != message
+        assert getattr(lib, name)(*args, a["ws"], None) == ERR_ARG, over
+        assert lib.sca_last_error().decode() == message, over
+
+
+def test_the_three_workspace_size_functions_are_one_formula():
+    from scattennet_amd import _lib as L
+    lib = ctypes.CDLL(L.LIB_PATH)
+    one, heads, fused = (getattr(lib, n) for n in ("sca_ctc_decode_workspace_bytes",
+                                                   "sca_ctc_decode_heads_workspace_bytes",
+                                                   "sca_ctc_fused_workspace_bytes"))
+    for fn, n in ((one, 4), (heads, 5), (fused, 5)):
+        fn.argtypes, fn.restype = [ctypes.c_int] * n, ctypes.c_long
+    for B, T, C, W in [(1, 1, 1, 1), (2, 8, 16, 5), (8, 64, 1124, 5), (3, 37, 8192, 32), (5, 400, 2, 1)]:
+        want = 4 * (2 * B * T + 2 * B * T * (W + 1)) + 8 * B * (T * W + 1)  # rowstat, cls, clp; the arena
+        assert one(B, T, C, W) == heads(1, B, T, C, W) == fused(1, B, T, C, W) == want
+        for G in (2, 8):  # the single-head layout over G B clips
+            assert heads(G, B, T, C, W) == fused(G, B, T, C, W) == one(G * B, T, C, W)
+    for B, T, C, W in [(0, 8, 16, 5), (2, 0, 16, 5), (2, 8, 0, 5), (2, 8, 8193, 5), (2, 8, 16, 0), (2, 8, 16, 33),
+                       (-1, 8, 16, 5)]:
+        assert one(B, T, C, W) == 0
+        for G in (1, 2):
+            assert heads(G, B, T, C, W) == 0 and fused(G, B, T, C, W) == 0
+    for G in (0, 9, -1):
+        assert heads(G, 2, 8, 16, 5) == 0 and fused(G, 2, 8, 16, 5) == 0
+
+
 @pytest.mark.parametrize("T,C", [(4, 3), (2, 6)])
 def test_restatement_matches_exhaustive_enumeration(T, C):
     """All prefixes fit a beam of 32, so the search is exact: it must return the arg-max
