@@ -11,18 +11,10 @@
 // needs are asked for ALN_AHEAD frames earlier.  A back-pointer is two bits, packed by ballot
 // into two 64-bit words per (frame, 64 states); they stay in LDS when they fit.  No atomics
 // on floats; every sum runs in a fixed order: results are deterministic.
-#include "common.h"
-#include "../../include/scatten.h"
-
-extern "C" void sca_set_error(const char* msg);
-// decode.hip: max and log-sum-exp of every (g, b, t) row of the G heads, one wave per row
-__attribute__((visibility("hidden"))) void sca_ctc_rowstat_heads_launch(const sca_decode_heads* heads, int G,
-                                                                        float* rowstat, long rows_per_head, int C,
-                                                                        hipStream_t st);
+#include "ctc.h"
 
 namespace {
 
-constexpr float NEG_INF = -__builtin_huge_valf();
 constexpr int ALN_MAX_L = 2 * SCA_CTC_MAX_S + 1;  // 2047 extended states
 constexpr int ALN_AHEAD = 4;                      // frames of logits in flight
 constexpr int ALN_BP_LDS = 1024;                  // (frame, 64-state chunk) pairs of back-pointers kept in LDS
@@ -32,35 +24,13 @@ struct AlnDims {
   int B, T, C, S;
 };
 
-struct AlnHeads {
-  const float* x[SCA_EVAL_MAX_HEADS];
-};
-
-// head g's tensor: a uniform select chain, so the by-value table stays in scalar registers
-__device__ __forceinline__ const float* aln_head(const AlnHeads& h, int g) {
-  const float* p = h.x[0];
-#pragma unroll
-  for (int i = 1; i < SCA_EVAL_MAX_HEADS; ++i) p = g == i ? h.x[i] : p;
-  return p;
-}
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
-// LDS hand-off inside ONE wave: the wave's LDS operations execute in order, so only the
-// compiler has to be kept from moving them across
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __host__ __device__ __forceinline__ int aln_chunks(int S) { return (2 * S + 1 + 63) / 64; }
 
 // One workgroup per (clip, head): grid (B, G).  Thread tid owns the extended states tid and
 // tid + NT for the whole clip (their class and whether the skip transition is allowed stay in
 // registers), so a wave is one aligned chunk of 64 states and its back-pointers are two ballots.
 template <int NT>
-__global__ __launch_bounds__(NT) void ctc_align_kernel(AlnHeads hx, const int* __restrict__ in_len,
+__global__ __launch_bounds__(NT) void ctc_align_kernel(CtcHeads hx, const int* __restrict__ in_len,
                                                        const int* __restrict__ labels,
                                                        const int* __restrict__ lab_len, int per_head, AlnDims d,
                                                        int* __restrict__ frame_label, int* __restrict__ spans,
@@ -80,7 +50,7 @@ __global__ __launch_bounds__(NT) void ctc_align_kernel(AlnHeads hx, const int* _
   const int Sb = clampi(lab_len[lrow], 0, S);
   const int* __restrict__ lab = labels + (long)lrow * S;
   const int L = 2 * Sb + 1, nchunk = aln_chunks(S);
-  const float* __restrict__ x = aln_head(hx, g) + (long)b * T * C;  // the clip's (T, C) logits
+  const float* __restrict__ x = ctc_head(hx, g) + (long)b * T * C;  // the clip's (T, C) logits
   const float* __restrict__ rs = rowstat + 2 * (long)slot * T;
   unsigned long long* __restrict__ bpg = bp_g + 2 * (long)slot * T * nchunk;
   int* __restrict__ fl = frame_label + (long)slot * T;
@@ -151,7 +121,7 @@ __global__ __launch_bounds__(NT) void ctc_align_kernel(AlnHeads hx, const int* _
               int k = 0;
               if (b1 > best) { best = b1; k = 1; }
               if (c2 > best) { best = c2; k = 2; }
-              if (in) s_v[cur][s] = ((xv[i] - m) - ls) + best;
+              if (in) s_v[cur][s] = ctc_lp_raw(xv[i], m, ls) + best;
               if (t > 0) {
                 const unsigned long long k0 = __ballot(k & 1), k1 = __ballot(k >> 1);
                 if (lane == 0) {
@@ -220,7 +190,7 @@ __global__ __launch_bounds__(NT) void ctc_align_kernel(AlnHeads hx, const int* _
       en = s_end[j];
       const int c = clampi(lab[j], 1, C - 1);
       float sum = 0.0f;
-      for (int t = st; t < en; ++t) sum += __expf((x[(long)t * C + c] - rs[2 * t]) - rs[2 * t + 1]);
+      for (int t = st; t < en; ++t) sum += __expf(ctc_lp_raw(x[(long)t * C + c], rs[2 * t], rs[2 * t + 1]));
       cv = en > st ? sum / (float)(en - st) : 0.0f;
     }
     spans[2 * ((long)slot * S + j)] = st;
@@ -275,8 +245,7 @@ extern "C" int sca_ctc_align_heads(const sca_decode_heads* heads, int G, const i
   }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const AlnDims d{B, T, C, S};
-  AlnHeads hx = {};
-  for (int g = 0; g < SCA_EVAL_MAX_HEADS; ++g) hx.x[g] = heads->logits[g < G ? g : 0];
+  const CtcHeads hx = ctc_heads_of(heads, G);
   float* rowstat = static_cast<float*>(ws);
   const long NT = (long)G * B * T;
   unsigned long long* bp = reinterpret_cast<unsigned long long*>(rowstat + 2 * NT);  // 8 NT bytes in front
@@ -288,8 +257,7 @@ extern "C" int sca_ctc_align_heads(const sca_decode_heads* heads, int G, const i
   else
     hipLaunchKernelGGL(ctc_align_kernel<1024>, dim3(B, G), dim3(1024), 0, st, hx, in_len, labels, lab_len,
                        labels_per_head != 0, d, frame_label, spans, conf, score, rowstat, bp, bp_lds);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_ctc_align_heads: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status("sca_ctc_align_heads");
 }
 
 extern "C" int sca_eval_log_alignments(const int* spans, const float* conf, const float* score, int G, int B, int S,
@@ -302,9 +270,5 @@ extern "C" int sca_eval_log_alignments(const int* spans, const float* conf, cons
   }
   hipLaunchKernelGGL(eval_log_align_kernel, dim3(B, G), dim3(128), 0, reinterpret_cast<hipStream_t>(stream), spans,
                      conf, score, S, state, span_log, conf_log, score_log, capacity, log_width);
-  if (hipGetLastError() != hipSuccess) {
-    sca_set_error("sca_eval_log_alignments: launch failed");
-    return SCA_ERR_LAUNCH;
-  }
-  return SCA_OK;
+  return sca_launch_status("sca_eval_log_alignments");
 }

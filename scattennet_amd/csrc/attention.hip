@@ -837,15 +837,11 @@ __global__ __launch_bounds__(256, FB_OCC) void attn_bwd_fused_kernel(const BwdAr
         // lane (q, grp') holding keys 4grp' .. 4grp' + 3 of row q
 #pragma unroll
         for (int r = 0; r < 4; ++r) tw[(4 * grp + r) * FB_TS + kj] = ds[r];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         const f32x4 dsv = ld4(&tw[kj * FB_TS + 4 * grp]);
 #pragma unroll
         for (int r = 0; r < 4; ++r) dq = mfma16(ktf[i][r], dsv[r], dq);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // reads done before the tile is rewritten
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();  // reads done before the tile is rewritten
       }
       // partial dQ^T[d = 4grp + r][q = 16t + kj] over this wave's keys
       st4(&dQr[w][(16 * t + kj) * HD + 4 * grp], dq);
@@ -1076,9 +1072,7 @@ __global__ __launch_bounds__(64 * KW, 1) void attn_bwd_kblk_kernel(const BwdArgs
       for (int r = 0; r < 4; ++r) tw[(4 * grp + r) * FB_TS + kj] = ds[r];
     }
     // dS^T through the wave-private tiles (one per key tile): one wave barrier for both
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
 #pragma unroll
     for (int i = 0; i < TPW; ++i) {
       const int g = (k0 >> 4) + own(i);
@@ -1090,9 +1084,7 @@ __global__ __launch_bounds__(64 * KW, 1) void attn_bwd_kblk_kernel(const BwdArgs
 #pragma unroll
         for (int r = 0; r < 4; ++r) dq[dd] = mfma16(ktf[i][dd][r], dsv[r], dq[dd]);
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // reads done before the tiles are rewritten
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();  // reads done before the tiles are rewritten
     // partial dQ^T[d = 16 dd + 4grp + r][q = 16t + kj] over this wave's keys
 #pragma unroll
     for (int dd = 0; dd < ND; ++dd) st4(&dQr[w][(16 * t + kj) * HD + 16 * dd + 4 * grp], dq[dd]);
@@ -1212,8 +1204,6 @@ void launch_bwd(const BwdArgs& a, dim3 gq, dim3 gk, hipStream_t st, bool drop) {
 
 }  // namespace
 
-extern "C" void sca_set_error(const char* msg);
-
 // floats of dq_part per problem the fused hd-32 backward needs (0: that path does not apply)
 extern "C" long sca_attn_bwd_workspace(int B, int H, int Tq, int Tk, int hd) {
   if (hd != 32 || B < 1 || H < 1 || Tq < 1 || Tk < 1) return 0;
@@ -1266,8 +1256,7 @@ extern "C" int sca_attn_fwd(int nprob, const sca_attn_fwd_problem* probs, int B,
   else if (hd == 32) am ? launch_fwd<32, true>(a, grid, st, drop) : launch_fwd<32, false>(a, grid, st, drop);
   else if (hd == 64) am ? launch_fwd<64, true>(a, grid, st, drop) : launch_fwd<64, false>(a, grid, st, drop);
   else am ? launch_fwd<128, true>(a, grid, st, drop) : launch_fwd<128, false>(a, grid, st, drop);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_attn_fwd: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status("sca_attn_fwd");
 }
 
 extern "C" int sca_attn_bwd(int nprob, const sca_attn_bwd_problem* probs, int B, int H, int Tq, int Tk, int hd,
@@ -1316,6 +1305,5 @@ extern "C" int sca_attn_bwd(int nprob, const sca_attn_bwd_problem* probs, int B,
   else if (hd == 32) am ? launch_bwd<32, true>(a, gq, gk, st, drop) : launch_bwd<32, false>(a, gq, gk, st, drop);
   else if (hd == 64) am ? launch_bwd<64, true>(a, gq, gk, st, drop) : launch_bwd<64, false>(a, gq, gk, st, drop);
   else am ? launch_bwd<128, true>(a, gq, gk, st, drop) : launch_bwd<128, false>(a, gq, gk, st, drop);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_attn_bwd: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status("sca_attn_bwd");
 }

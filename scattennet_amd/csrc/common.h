@@ -2,6 +2,22 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
+
+#include "../../include/scatten.h"
+
+// capi.cpp: the calling thread's message behind sca_last_error()
+extern "C" void sca_set_error(const char* msg);
+
+// The check behind an entry point's launches: SCA_OK, or "<name>: launch failed" as the thread's
+// message and SCA_ERR_LAUNCH.
+inline int sca_launch_status(const char* name) {
+  if (hipGetLastError() == hipSuccess) return SCA_OK;
+  char msg[256];
+  snprintf(msg, sizeof(msg), "%s: launch failed", name);
+  sca_set_error(msg);
+  return SCA_ERR_LAUNCH;
+}
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -82,6 +98,16 @@ __device__ __forceinline__ void lds_barrier() {
   __builtin_amdgcn_sched_barrier(0);
 }
 
+// LDS hand-off inside ONE wave (a lane reads cells that other lanes of its own wave wrote, or
+// rewrites cells they have read): the LDS executes one wave's operations in order, so no
+// s_barrier and no wait is needed, and only the compiler has to be kept from moving the LDS
+// accesses across this point.  The wavefront-scope fences do that and emit no instruction.
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
 }
@@ -101,27 +127,6 @@ __host__ __device__ __forceinline__ uint32_t sca_mix32(uint32_t x) {
 }
 
 extern "C" const unsigned long long* sca_drop_offset_ptr(void);
-
-// One wave over one row xr of C logits: lane 0 writes stat[0] = max and stat[1] =
-// log(sum exp(x - max)).  The row pass of the CTC loss (heads.hip, ctc_rowstat_kernel) and of
-// the CTC decoders (decode.hip, ctc_rowstat_heads_kernel): one body, so the two agree bitwise.
-__device__ __forceinline__ void ctc_row_stat(const float* xr, int C, int lane, float* stat) {
-  float m = -__builtin_huge_valf();
-  for (int c = lane; c < C; c += 64) m = fmaxf(m, xr[c]);
-  m = wave_max(m);
-  float s = 0.0f;
-  for (int c = lane; c < C; c += 64) s += __expf(xr[c] - m);
-  s = wave_sum(s);
-  if (lane == 0) {
-    stat[0] = m;
-    stat[1] = __logf(s);
-  }
-}
-
-// heads.hip: ctc_row_stat over the rows of one tensor, rowstat (rows, 2); the CTC loss, the MWER
-// loss (mwer.hip) and a decoder call over one tensor (decode.hip) use it
-__attribute__((visibility("hidden"))) void sca_ctc_rowstat_launch(const float* x, float* rowstat, long rows, int C,
-                                                                  hipStream_t st);
 
 struct DropMask {
   uint32_t key, thr;

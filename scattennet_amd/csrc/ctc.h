@@ -1,0 +1,104 @@
+// What the recognition-head files share: the CTC arithmetic of heads.hip (CTC loss), decode.hip
+// (decoders), align.hip (forced alignment), ensemble.hip (head ensemble) and mwer.hip (MWER
+// loss), which must agree bitwise, the row-statistics pass and the by-value head table.
+//
+// The three lattice recursions are NOT here, on purpose: the CTC loss's 256-thread alpha / beta
+// kernel (S <= 1023, one workgroup per clip), MWER's wave-private recursion (H <= 128, one wave
+// per hypothesis) and the aligner's banded Viterbi (max with back-pointers instead of a sum)
+// parallelise differently.  Merging them would change kernels, not share code.
+#pragma once
+#include "common.h"
+
+constexpr float NEG_INF = -__builtin_huge_valf();
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+
+// log-sum-exp of a lattice cell's three predecessors; all -inf stays -inf
+__device__ __forceinline__ float lse3(float a, float b, float c) {
+  float m = fmaxf(a, fmaxf(b, c));
+  if (m == NEG_INF) m = 0.0f;
+  return __logf(__expf(a - m) + __expf(b - m) + __expf(c - m)) + m;
+}
+
+// log_softmax(x) from the row statistics, with torch's (x - max) - log(sum) order, and the
+// log_probs element of the CTC loss, clamp(log_softmax(x), -100, 0)
+__device__ __forceinline__ float ctc_lp_raw(float x, float m, float ls) { return (x - m) - ls; }
+__device__ __forceinline__ float ctc_lp(float raw) { return fminf(fmaxf(raw, -100.0f), 0.0f); }
+
+// log(exp(l1) + exp(l2)) of the two end states of the last frame; -inf: the labels do not fit
+__device__ __forceinline__ float ctc_end_loglik(float l1, float l2) {
+  float m = fmaxf(l1, l2);
+  if (m == NEG_INF) m = 0.0f;
+  return __logf(__expf(l1 - m) + __expf(l2 - m)) + m;
+}
+
+// One wave over one row xr of C logits: lane 0 writes stat[0] = max and stat[1] =
+// log(sum exp(x - max)).  One body under both row passes below, so they agree bitwise.
+__device__ __forceinline__ void ctc_row_stat(const float* xr, int C, int lane, float* stat) {
+  float m = NEG_INF;
+  for (int c = lane; c < C; c += 64) m = fmaxf(m, xr[c]);
+  m = wave_max(m);
+  float s = 0.0f;
+  for (int c = lane; c < C; c += 64) s += __expf(xr[c] - m);
+  s = wave_sum(s);
+  if (lane == 0) {
+    stat[0] = m;
+    stat[1] = __logf(s);
+  }
+}
+
+// heads.hip: ctc_row_stat over the rows of one tensor, rowstat (rows, 2); the CTC loss, the MWER
+// loss and a decoder call over one tensor use it
+__attribute__((visibility("hidden"))) void sca_ctc_rowstat_launch(const float* x, float* rowstat, long rows, int C,
+                                                                  hipStream_t st);
+// decode.hip: the same over every (g, b, t) row of G heads, rowstat (G, rows_per_head, 2); the
+// grouped decoders (G > 1) and the aligner use it.  The caller validates heads and G.
+__attribute__((visibility("hidden"))) void sca_ctc_rowstat_heads_launch(const sca_decode_heads* heads, int G,
+                                                                        float* rowstat, long rows_per_head, int C,
+                                                                        hipStream_t st);
+
+// The logit tensors of the G heads one launch works on, by value in the kernel arguments.  A
+// (head, clip) pair is "clip" n = g B + b of the workspaces and the outputs, so a single-head
+// entry point is the case G = 1.  The slots past G repeat head 0.
+struct CtcHeads {
+  const float* x[SCA_EVAL_MAX_HEADS];
+};
+
+// head g's tensor: a uniform select chain, so the by-value table stays in scalar registers
+__device__ __forceinline__ const float* ctc_head(const CtcHeads& h, int g) {
+  const float* p = h.x[0];
+#pragma unroll
+  for (int i = 1; i < SCA_EVAL_MAX_HEADS; ++i) p = g == i ? h.x[i] : p;
+  return p;
+}
+
+inline CtcHeads ctc_heads_of(const sca_decode_heads* heads, int G) {
+  CtcHeads h = {};
+  for (int g = 0; g < SCA_EVAL_MAX_HEADS; ++g) h.x[g] = heads->logits[g < G ? g : 0];
+  return h;
+}
+
+// The tail of a gradient row of a loss over log_probs = clamp(log_softmax(x), -100, 0), by a
+// workgroup of NT threads: g[c] = g_of(c, raw) is d loss / d log_probs[c], the clamp's backward
+// closes it where raw = log_softmax(x)[c] is outside [-100, 0], and the log-softmax backward is
+// dx[c] = g[c] - softmax(x)[c] sum g, the sum over the waves in index order.  g_s holds C floats
+// of LDS (g_of may read its own cell), red one per wave.
+template <int NT, class GradOf>
+__device__ __forceinline__ void ctc_grad_row_tail(const float* __restrict__ xr, float* __restrict__ dr, int C, float m,
+                                                  float ls, float* g_s, float* red, int tid, GradOf g_of) {
+  float part = 0.0f;
+  for (int c = tid; c < C; c += NT) {
+    const float raw = ctc_lp_raw(xr[c], m, ls);
+    float g = g_of(c, raw);
+    if (!(raw >= -100.0f && raw <= 0.0f)) g = 0.0f;  // clamp(-100, 0) backward
+    g_s[c] = g;
+    part += g;
+  }
+  part = wave_sum(part);
+  if ((tid & 63) == 0) red[tid >> 6] = part;
+  __syncthreads();
+  float G = red[0];
+#pragma unroll
+  for (int w = 1; w < NT / 64; ++w) G += red[w];
+  for (int c = tid; c < C; c += NT) dr[c] = g_s[c] - __expf(ctc_lp_raw(xr[c], m, ls)) * G;
+}

@@ -15,22 +15,11 @@
 // so a clip is one workgroup; everything that does not depend on the beam (row normaliser,
 // the W + 1 best classes of every frame) is computed beforehand by row-parallel launches.
 // No float atomics; every sum runs in a fixed order: results are deterministic.
-#include <cstdio>
-
-#include "common.h"
+#include "ctc.h"
 #include "wer_pair.h"
-#include "../../include/scatten.h"
-
-extern "C" void sca_set_error(const char* msg);
-// the grouped row pass of the decoders (G > 1) and of align.hip (which validates heads and G): rowstat
-// (G, rows_per_head, 2)
-__attribute__((visibility("hidden"))) void sca_ctc_rowstat_heads_launch(const sca_decode_heads* heads, int G,
-                                                                        float* rowstat, long rows_per_head, int C,
-                                                                        hipStream_t st);
 
 namespace {
 
-constexpr float NEG_INF = -__builtin_huge_valf();
 constexpr int NONE = 0x7fffffff;
 constexpr int DEC_MAX_W = SCA_CTC_MAX_BEAM;
 constexpr int DEC_MAX_ITEMS = DEC_MAX_W * (DEC_MAX_W + 1) + DEC_MAX_W;  // candidates + updated beams
@@ -42,21 +31,6 @@ constexpr int DEC_FUSE_CHUNK = 24;  // fused search: labels per lane loaded toge
 struct DecDims {
   int B, T, C, W;
 };
-
-// The logit tensors of the G heads decoded by one launch, by value in the kernel arguments.
-// A (head, clip) pair is "clip" n = g B + b of the workspace and of the outputs, so the
-// single-head entry points are the case G = 1.
-struct DecHeads {
-  const float* x[SCA_EVAL_MAX_HEADS];
-};
-
-// head g's tensor: a uniform select chain, so the by-value table stays in scalar registers
-__device__ __forceinline__ const float* dec_head(const DecHeads& h, int g) {
-  const float* p = h.x[0];
-#pragma unroll
-  for (int i = 1; i < SCA_EVAL_MAX_HEADS; ++i) p = g == i ? h.x[i] : p;
-  return p;
-}
 
 // workspace layout, N = G B clips: rowstat float[2 NT] | cls int[NT (W+1)] | clp float[NT (W+1)] |
 // arena u64[N (T W + 1)] (dec_pl words).  The greedy path keeps its per-frame arg-max in cls.
@@ -73,8 +47,6 @@ struct DecWs {
     arena = reinterpret_cast<unsigned long long*>(clp + BT * K);  // 2 BT (K + 1) floats in front: 8-byte aligned
   }
 };
-
-__device__ __forceinline__ float dec_lp(float x, float m, float ls) { return (x - m) - ls; }
 
 // The bigram model of the fused search (sca_ctc_beam_decode_fused_nbest): lm (C, C) or NULL.
 struct DecLm {
@@ -94,8 +66,6 @@ __device__ __forceinline__ float logaddexp_tail(float a, float b) {
   if (lo == NEG_INF) return hi;
   return hi + log1pf(expf(lo - hi));
 }
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 // (v, c) beats (w, d): larger value, ties to the lower index
 __device__ __forceinline__ bool beats(float v, int c, float w, int d) { return v > w || (v == w && c < d); }
@@ -123,7 +93,7 @@ __device__ __forceinline__ int dec_ord_key(unsigned long long o) { return NONE -
 // the same value wherever it is evaluated.  lp and the bigram term go out as they enter the
 // candidate.  fuse_ord: the same from the rows (row NULL: no table), as a dec_ord word with c.
 __device__ __forceinline__ float fuse_key(float xv, float lmv, float weight, float m, float ls, float& lp, float& bg) {
-  lp = dec_lp(xv, m, ls);
+  lp = ctc_lp_raw(xv, m, ls);
   bg = weight * lmv;
   return __fmaf_rn(weight, lmv, lp);
 }
@@ -149,20 +119,20 @@ __device__ __forceinline__ int dec_par(unsigned long long v) { return (int)(v >>
 __device__ __forceinline__ int dec_lab(unsigned long long v) { return (int)(v & 0xffffffffull); }
 
 // One wave per (g, b, t) row: max and log-sum-exp of the logits row, the CTC loss's row pass
-// (ctc_row_stat, common.h) over the rows of G tensors.  A grouped decoder's first launch.
-__global__ __launch_bounds__(256) void ctc_rowstat_heads_kernel(DecHeads hx, float* __restrict__ rowstat, long rows,
+// (ctc_row_stat, ctc.h) over the rows of G tensors.  A grouped decoder's first launch.
+__global__ __launch_bounds__(256) void ctc_rowstat_heads_kernel(CtcHeads hx, float* __restrict__ rowstat, long rows,
                                                                 long rows_per_head, int C) {
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= rows) return;
   const int g = (int)(row / rows_per_head);
-  ctc_row_stat(dec_head(hx, g) + (row - g * rows_per_head) * C, C, lane, rowstat + 2 * row);
+  ctc_row_stat(ctc_head(hx, g) + (row - g * rows_per_head) * C, C, lane, rowstat + 2 * row);
 }
 
 // One wave per (g, b, t) row: the K = min(W + 1, C - 1) labels (c != 0) with the largest
 // log-probability, in descending order, ties to the lower class.  Round k takes the best
 // element strictly after round k - 1's pick in that order, so nothing is marked as taken.
-__global__ __launch_bounds__(256) void ctc_topk_kernel(DecHeads hx, int G, const int* __restrict__ in_len, DecDims d,
+__global__ __launch_bounds__(256) void ctc_topk_kernel(CtcHeads hx, int G, const int* __restrict__ in_len, DecDims d,
                                                        DecWs w) {
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
@@ -170,7 +140,7 @@ __global__ __launch_bounds__(256) void ctc_topk_kernel(DecHeads hx, int G, const
   const int n = (int)(row / d.T), t = (int)(row - (long)n * d.T);  // n = g B + b
   const int g = n / d.B, b = n - g * d.B;
   if (t >= clampi(in_len[b], 0, d.T)) return;
-  const float* xr = dec_head(hx, g) + ((long)b * d.T + t) * d.C;
+  const float* xr = ctc_head(hx, g) + ((long)b * d.T + t) * d.C;
   const float m = w.rowstat[2 * row], ls = w.rowstat[2 * row + 1];
   const int K = min(d.W + 1, d.C - 1);
   float pv = 0.0f;
@@ -179,7 +149,7 @@ __global__ __launch_bounds__(256) void ctc_topk_kernel(DecHeads hx, int G, const
     float bv = NEG_INF;
     int bc = NONE;
     for (int c = 1 + lane; c < d.C; c += 64) {
-      const float v = dec_lp(xr[c], m, ls);
+      const float v = ctc_lp_raw(xr[c], m, ls);
       const bool open = k == 0 || v < pv || (v == pv && c > pc);
       if (open && v > bv) { bv = v; bc = c; }  // ascending c: the first of equal values stays
     }
@@ -231,7 +201,7 @@ __global__ __launch_bounds__(256) void ctc_topk_kernel(DecHeads hx, int G, const
 // (the closing bigram included) and the tail takes entry n from beam p_src[n].  The unfused
 // instantiations contain none of this: every fused statement is under `if constexpr`.
 template <bool NBEST, bool FUSED = false>
-__global__ __launch_bounds__(64) void ctc_beam_kernel(DecHeads hx, const int* __restrict__ in_len, DecDims d,
+__global__ __launch_bounds__(64) void ctc_beam_kernel(CtcHeads hx, const int* __restrict__ in_len, DecDims d,
                                                       int collapse, int nbest, int* __restrict__ tokens,
                                                       int* __restrict__ out_len, float* __restrict__ score,
                                                       int* __restrict__ count, DecWs w, DecLm f) {
@@ -262,7 +232,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(DecHeads hx, const int* __
   const int slot = (int)blockIdx.y * d.B + (int)blockIdx.x;  // the (head, clip)'s place in workspace and outputs
   const int T = d.T, C = d.C, W = d.W, KS = W + 1, K = min(W + 1, C - 1);
   const int Tb = clampi(in_len[blockIdx.x], 0, T);
-  const float* __restrict__ x = dec_head(hx, blockIdx.y) + (long)blockIdx.x * T * C;  // the clip's (T, C) logits
+  const float* __restrict__ x = ctc_head(hx, blockIdx.y) + (long)blockIdx.x * T * C;  // the clip's (T, C) logits
   unsigned long long* arena = w.arena + (long)slot * ((long)T * W + 1);
   int nn = 1, nb = 1, cur = 0;  // arena nodes, active beams, state buffer (all wave-uniform)
   double offset = 0.0;
@@ -291,7 +261,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(DecHeads hx, const int* __
   }
   __syncthreads();
   for (int t = 0; t < Tb; ++t) {
-    const float m = pm, ls = pls, lp0 = dec_lp(px0, pm, pls);
+    const float m = pm, ls = pls, lp0 = ctc_lp_raw(px0, pm, pls);
     const int nxt = cur ^ 1;
     if constexpr (!FUSED) {
       if (lane < K) { f_cls[lane] = pcls; f_clp[lane] = pclp; }
@@ -313,7 +283,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(DecHeads hx, const int* __
       const float nlb = s_tot[cur][lane] + lp0;
       float nll = NEG_INF;
       if (par >= 0) {
-        const float lpe = dec_lp(s_xe[cur][lane], m, ls);
+        const float lpe = ctc_lp_raw(s_xe[cur][lane], m, ls);
         nll = s_ll[cur][lane] + lpe;
         int pj = -1;  // the parent prefix's slot: node ids of active beams are distinct
 #pragma unroll 8
@@ -675,7 +645,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(DecHeads hx, const int* __
 // arg-max (ties to the lowest class; a frame is a chain of dependent loads, so frames run side
 // by side), then wave 0 collapses repeats and drops blanks with a ballot scan.
 constexpr int GREEDY_WAVES = 16;
-__global__ __launch_bounds__(64 * GREEDY_WAVES) void ctc_greedy_kernel(DecHeads hx,
+__global__ __launch_bounds__(64 * GREEDY_WAVES) void ctc_greedy_kernel(CtcHeads hx,
                                                                         const int* __restrict__ in_len, DecDims d,
                                                                         int* __restrict__ tokens,
                                                                         int* __restrict__ out_len,
@@ -686,7 +656,7 @@ __global__ __launch_bounds__(64 * GREEDY_WAVES) void ctc_greedy_kernel(DecHeads 
   const int slot = (int)blockIdx.y * d.B + (int)blockIdx.x;
   const int T = d.T, C = d.C;
   const int Tb = clampi(in_len[blockIdx.x], 0, T);
-  const float* __restrict__ x = dec_head(hx, blockIdx.y) + (long)blockIdx.x * T * C;
+  const float* __restrict__ x = ctc_head(hx, blockIdx.y) + (long)blockIdx.x * T * C;
   int* amax = w.cls + (long)slot * T;
   float acc = 0.0f;
   for (int t = wave; t < Tb; t += GREEDY_WAVES) {
@@ -701,7 +671,7 @@ __global__ __launch_bounds__(64 * GREEDY_WAVES) void ctc_greedy_kernel(DecHeads 
     wave_argmax(bv, bc);
     if (bc == NONE) bc = 0;
     if (lane == 0) amax[t] = bc;
-    acc += dec_lp(xr[bc], w.rowstat[2 * row], w.rowstat[2 * row + 1]);
+    acc += ctc_lp_raw(xr[bc], w.rowstat[2 * row], w.rowstat[2 * row + 1]);
   }
   if (lane == 0) part[wave] = acc;
   __syncthreads();
@@ -928,12 +898,6 @@ bool dec_heads_ok(const sca_decode_heads* heads, int G, int B, int T, int C, int
   return true;
 }
 
-DecHeads dec_heads_of(const sca_decode_heads* heads, int G) {
-  DecHeads h = {};
-  for (int g = 0; g < SCA_EVAL_MAX_HEADS; ++g) h.x[g] = heads->logits[g < G ? g : 0];
-  return h;
-}
-
 // the single-head layout over N = G B clips; 0 for unsupported sizes
 long dec_ws_bytes(int G, int B, int T, int C, int W) {
   if (G < 1 || G > SCA_EVAL_MAX_HEADS || !dec_dims_ok(B, T, C, W)) return 0;
@@ -972,7 +936,7 @@ bool dec_call_ok(const DecCall& c) {
 void dec_launch(const DecCall& c, hipStream_t st) {
   const DecDims d = c.d;
   const DecWs w(c.ws, d, c.G);
-  const DecHeads hx = dec_heads_of(c.heads, c.G);
+  const CtcHeads hx = ctc_heads_of(c.heads, c.G);
   const long rows = (long)c.G * d.B * d.T;
   const dim3 clips(d.B, c.G);
   // one tensor: the CTC loss's launch of the same row body, without the head select (measured:
@@ -998,30 +962,25 @@ void dec_launch(const DecCall& c, hipStream_t st) {
 int dec_decode(const char* name, bool grouped, const DecCall& c, void* stream) {
   static const char* const limits[] = {"", ", 1 <= beam_width <= 32", ", 1 <= nbest <= beam_width <= 32",
                                        ", 1 <= nbest <= beam_width <= 32, finite weights"};
-  char msg[256];
   if (!dec_call_ok(c)) {
+    char msg[256];
     snprintf(msg, sizeof(msg), "%s: bad arguments (%sB, T >= 1, 1 <= C <= 8192%s)", name,
              grouped ? "1 <= G <= 8 non-null tensors, " : "", limits[c.mode]);
     sca_set_error(msg);
     return SCA_ERR_ARG;
   }
   dec_launch(c, reinterpret_cast<hipStream_t>(stream));
-  if (hipGetLastError() != hipSuccess) {
-    snprintf(msg, sizeof(msg), "%s: launch failed", name);
-    sca_set_error(msg);
-    return SCA_ERR_LAUNCH;
-  }
-  return SCA_OK;
+  return sca_launch_status(name);
 }
 
 }  // namespace
 
-__attribute__((visibility("hidden"))) void sca_ctc_rowstat_heads_launch(const sca_decode_heads* heads, int G,
-                                                                        float* rowstat, long rows_per_head, int C,
-                                                                        hipStream_t st) {
+// the row max / log-sum-exp pass of G heads (ctc.h)
+void sca_ctc_rowstat_heads_launch(const sca_decode_heads* heads, int G, float* rowstat, long rows_per_head, int C,
+                                  hipStream_t st) {
   const long rows = (long)G * rows_per_head;
   hipLaunchKernelGGL(ctc_rowstat_heads_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st,
-                     dec_heads_of(heads, G), rowstat, rows, rows_per_head, C);
+                     ctc_heads_of(heads, G), rowstat, rows, rows_per_head, C);
 }
 
 extern "C" long sca_ctc_decode_workspace_bytes(int B, int T, int C, int W) { return dec_ws_bytes(1, B, T, C, W); }
@@ -1075,8 +1034,7 @@ extern "C" int sca_wer_counts(const int* ref, const int* ref_len, const int* hyp
   }
   hipLaunchKernelGGL(wer_kernel, dim3(N), dim3(128), 0, reinterpret_cast<hipStream_t>(stream), ref, ref_len, hyp,
                      hyp_len, Rmax, Hmax, counts);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_wer_counts: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status("sca_wer_counts");
 }
 
 extern "C" int sca_eval_accumulate(const int* tokens, const int* hyp_len, int G, int B, int Hmax, const int* ref,
@@ -1098,8 +1056,7 @@ extern "C" int sca_eval_accumulate(const int* tokens, const int* hyp_len, int G,
                      state, lg);
   hipLaunchKernelGGL(eval_advance_kernel, dim3(1), dim3(64), 0, st, static_cast<const unsigned*>(report), nflags, nloss,
                      B, state);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_eval_accumulate: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status("sca_eval_accumulate");
 }
 
 extern "C" int sca_ctc_beam_decode_nbest(const float* logits, const int* in_len, int B, int T, int C, int beam_width,
@@ -1157,8 +1114,7 @@ extern "C" int sca_nbest_rescore(const int* tokens, const int* out_len, const fl
   hipLaunchKernelGGL(nbest_rescore_kernel, dim3((unsigned)(G * B)), dim3(64), 0, reinterpret_cast<hipStream_t>(stream),
                      tokens, out_len, score, count, N, T, lm, C, lm_weight, length_bonus, posterior_scale, total,
                      posterior, order);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_nbest_rescore: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status("sca_nbest_rescore");
 }
 
 extern "C" int sca_nbest_mbr(const int* tokens, const int* out_len, const int* count, const float* posterior, int G,
@@ -1173,8 +1129,7 @@ extern "C" int sca_nbest_mbr(const int* tokens, const int* out_len, const int* c
                      count, N, T, loss);
   hipLaunchKernelGGL(nbest_risk_kernel, dim3((unsigned)(G * B)), dim3(64), 0, st, loss, posterior, count, N, risk,
                      best);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_nbest_mbr: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status("sca_nbest_mbr");
 }
 
 extern "C" int sca_nbest_gather(const int* tokens, const int* out_len, const float* value, const int* sel,
@@ -1187,6 +1142,5 @@ extern "C" int sca_nbest_gather(const int* tokens, const int* out_len, const flo
   }
   hipLaunchKernelGGL(nbest_gather_kernel, dim3((unsigned)(G * B)), dim3(64), 0, reinterpret_cast<hipStream_t>(stream),
                      tokens, out_len, value, sel, sel_stride, N, T, tokens1, out_len1, value1);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_nbest_gather: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status("sca_nbest_gather");
 }

@@ -12,20 +12,17 @@
 // on a 16-byte boundary and C is a multiple of 4; any other row takes the scalar path.
 // No atomics, no LDS; every sum runs in a fixed order and a row's result depends on nothing
 // but the row, so a replayed capture is bitwise the eager call.
-#include "common.h"
-#include "../../include/scatten.h"
-
-extern "C" void sca_set_error(const char* msg);
+#include "ctc.h"
 
 namespace {
 
-constexpr float NEG_INF = -__builtin_huge_valf();
 constexpr int G_MAX = SCA_EVAL_MAX_HEADS;
 
 // The G row sources and their weights, by value in the kernel arguments (scalar registers).
-// w[g] = w_g / sum w; lw[g] = log of it ("prob" adds it to the head's log-probabilities).
+// x: the head table of the decoders (ctc.h), slots past G filled the same way; w[g] = w_g / sum w;
+// lw[g] = log of it ("prob" adds it to the head's log-probabilities).
 struct EnsHeads {
-  const float* x[G_MAX];
+  CtcHeads x;
   float w[G_MAX];
   float lw[G_MAX];
 };
@@ -70,7 +67,7 @@ __device__ __forceinline__ void ensemble_row(const EnsHeads& h, int G, int mode,
     m[g] = 0.0f;
     ls[g] = 0.0f;
     if (g < G) {
-      const float* xr = h.x[g] + off;
+      const float* xr = h.x.x[g] + off;
       float mx = NEG_INF;
       for (int c = lane * V; c < C; c += 64 * V) {
         const Pack<V> x = ldv<V>(xr + c);
@@ -101,10 +98,10 @@ __device__ __forceinline__ void ensemble_row(const EnsHeads& h, int G, int mode,
 #pragma unroll
       for (int g = 0; g < G_MAX; ++g) {
         if (g < G) {
-          const Pack<V> x = ldv<V>(h.x[g] + off + c);
+          const Pack<V> x = ldv<V>(h.x.x[g] + off + c);
 #pragma unroll
           for (int i = 0; i < V; ++i) {
-            a[g][i] = ((x.v[i] - m[g]) - ls[g]) + h.lw[g];
+            a[g][i] = ctc_lp_raw(x.v[i], m[g], ls[g]) + h.lw[g];
             M[i] = fmaxf(M[i], a[g][i]);
           }
         }
@@ -133,9 +130,9 @@ __device__ __forceinline__ void ensemble_row(const EnsHeads& h, int G, int mode,
 #pragma unroll
     for (int g = 0; g < G_MAX; ++g) {
       if (g < G) {
-        const Pack<V> x = ldv<V>(h.x[g] + off + c);
+        const Pack<V> x = ldv<V>(h.x.x[g] + off + c);
 #pragma unroll
-        for (int i = 0; i < V; ++i) u.v[i] = fmaf(h.w[g], (x.v[i] - m[g]) - ls[g], u.v[i]);
+        for (int i = 0; i < V; ++i) u.v[i] = fmaf(h.w[g], ctc_lp_raw(x.v[i], m[g], ls[g]), u.v[i]);
       }
     }
 #pragma unroll
@@ -170,7 +167,7 @@ __global__ __launch_bounds__(256) void ensemble_log_probs_kernel(EnsHeads h, int
   uintptr_t bits = reinterpret_cast<uintptr_t>(outr) | (uintptr_t)(C & 3);
 #pragma unroll
   for (int g = 0; g < G_MAX; ++g)
-    if (g < G) bits |= reinterpret_cast<uintptr_t>(h.x[g] + off);
+    if (g < G) bits |= reinterpret_cast<uintptr_t>(h.x.x[g] + off);
   if ((bits & 15) == 0)
     ensemble_row<4>(h, G, mode, off, outr, C, lane);
   else
@@ -196,15 +193,13 @@ extern "C" int sca_ensemble_log_probs(const sca_decode_heads* heads, int G, cons
     return SCA_ERR_ARG;
   }
   EnsHeads h;
+  h.x = ctc_heads_of(heads, G);
   for (int g = 0; g < G_MAX; ++g) {
-    const int s = g < G ? g : 0;
-    const double w = (double)weights->w[s] / sum;
-    h.x[g] = heads->logits[s];
+    const double w = (double)weights->w[g < G ? g : 0] / sum;
     h.w[g] = (float)w;
     h.lw[g] = (float)log(w);
   }
   hipLaunchKernelGGL(ensemble_log_probs_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), h, G, mode, out, rows, C);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_ensemble_log_probs: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status("sca_ensemble_log_probs");
 }

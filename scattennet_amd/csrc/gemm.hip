@@ -210,9 +210,7 @@ __device__ __forceinline__ void acc_to_rows(const f32x16& acc, float* scratch, i
   const int col = lane & 31, rowh = 4 * (lane >> 5);
 #pragma unroll
   for (int r = 0; r < 16; ++r) scratch[((r & 3) + 8 * (r >> 2) + rowh) * EPI_LD + col] = acc[r];
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_lds_sync();
 #pragma unroll
   for (int i = 0; i < 4; ++i) v[i] = ld4(scratch + ((lane >> 3) + 8 * i) * EPI_LD + 4 * (lane & 7));
 }
@@ -1477,9 +1475,7 @@ __global__ __launch_bounds__(256, 1) void gemm_ntb_kernel(const GemmArgs args) {
     for (int j = 0; j < NQ; ++j)
 #pragma unroll
       for (int r = 0; r < 4; ++r) img[(16 * i + 4 * kg + r) * NB_LD + 16 * j + li] = acc[i][j][r] * alpha;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_lds_sync();
   const int n = n0 + wn + 4 * (lane % LR);
   if (n >= P.N) return;
   DropMask dm;
@@ -2049,9 +2045,7 @@ __global__ __launch_bounds__(LgCfg<BM>::NW * 64) void gemm_ln_kernel(const GemmL
       ilv_read<0, 4, 4, 4>();
       __builtin_amdgcn_sched_barrier(0);
       // this wave has read its rows of the B image (no other wave reads or writes them)
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_sync();
       __builtin_amdgcn_sched_barrier(0);
       if constexpr (WR) {
         store2();
@@ -2066,9 +2060,7 @@ __global__ __launch_bounds__(LgCfg<BM>::NW * 64) void gemm_ln_kernel(const GemmL
           for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int r = 0; r < 4; ++r) scratch[(16 * i + 4 * kg + r) * EPI_LD + 16 * j + li] = acc2[i][j][r];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         f32x4 rows[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) rows[q] = ld4(scratch + ((lane >> 3) + 8 * q) * EPI_LD + 4 * (lane & 7));
@@ -2080,14 +2072,10 @@ __global__ __launch_bounds__(LgCfg<BM>::NW * 64) void gemm_ln_kernel(const GemmL
         for (int i = 0; i < 2; ++i)
 #pragma unroll
           for (int j = 0; j < 2; ++j) acc2[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // scratch reads done before the next pass
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();  // scratch reads done before the next pass
       }
       // this wave's rows of the next B tile are in LDS
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_sync();
     };
     int u = 0;
 #pragma unroll 1
@@ -2847,8 +2835,6 @@ extern "C" int sca_gemm_clk(unsigned long long* out, int n) {
 }
 #endif
 
-extern "C" void sca_set_error(const char* msg);
-
 extern "C" int sca_gemm_tile_override(int layout, int tile) {
   if (layout < 0 || layout > 2 || !valid_tile(layout, tile)) {
     sca_set_error("sca_gemm_tile_override: unknown layout or kernel variant id");
@@ -2857,8 +2843,6 @@ extern "C" int sca_gemm_tile_override(int layout, int tile) {
   g_tile_override[layout] = tile;
   return SCA_OK;
 }
-
-extern "C" void sca_set_error(const char* msg);
 
 namespace {
 // the requested variant of a launch: the caller's, the process-wide override, or the heuristic
@@ -3148,8 +3132,7 @@ extern "C" int sca_gemm_ln(int nprob, const sca_gemm_problem* probs, const sca_g
     else
       hipLaunchKernelGGL((gemm_ln_kernel<GL_A32, false, 1>), dim3((maxM + 31) / 32, 1, nprob), dim3(512), 0, st, a);
   }
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_gemm_ln: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status("sca_gemm_ln");
 }
 
 extern "C" int sca_gemm_lnb_blocks(int M) { return M > 0 ? (M + LB_BM - 1) / LB_BM : 0; }
@@ -3211,6 +3194,5 @@ extern "C" int sca_gemm_lnb(int nprob, const sca_gemm_problem* probs, const sca_
   else if (reg) hipLaunchKernelGGL((gemm_lnb_kernel<1, true>), dim3((maxM + LB_BM - 1) / LB_BM, 1, nprob), dim3(512), 0, st, a);
   else if (N == LG_BN) hipLaunchKernelGGL(gemm_lnb_kernel<1>, dim3((maxM + LB_BM - 1) / LB_BM, 1, nprob), dim3(512), 0, st, a);
   else hipLaunchKernelGGL(gemm_lnb_kernel<2>, dim3((maxM + LB_BM - 1) / LB_BM, 1, nprob), dim3(512), 0, st, a);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_gemm_lnb: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status("sca_gemm_lnb");
 }

@@ -15,8 +15,6 @@
 #include "../../include/scatten.h"
 #include "common.h"
 
-extern "C" void sca_set_error(const char* msg);
-
 namespace {
 
 constexpr int GUARD_THREADS = 256;
@@ -144,13 +142,11 @@ extern "C" int sca_finite_scan(int ntensors, const float* const* ptrs, const lon
   // once the host had made enough pageable copies in between (evaluation step)
   hipLaunchKernelGGL(flags_clear_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, flags, ntensors);
   if (chunks == 0) {
-    if (hipGetLastError() != hipSuccess) { sca_set_error("sca_finite_scan: launch failed"); return SCA_ERR_LAUNCH; }
-    return SCA_OK;
+    return sca_launch_status("sca_finite_scan");
   }
   const int grid = chunks < GUARD_MAX_BLOCKS ? (int)chunks : GUARD_MAX_BLOCKS;
   hipLaunchKernelGGL(finite_scan_kernel, dim3(grid), dim3(GUARD_THREADS), 0, (hipStream_t)stream, a, flags);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_finite_scan: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status("sca_finite_scan");
 }
 
 extern "C" int sca_step_report(const unsigned* flags, int nflags, const float* alignment_loss,
@@ -169,6 +165,5 @@ extern "C" int sca_step_report(const unsigned* flags, int nflags, const float* a
   }
   hipLaunchKernelGGL(step_report_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, flags, nflags, alignment_loss,
                      fuse_coord_loss, d, total_loss, static_cast<uint32_t*>(report));
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_step_report: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status("sca_step_report");
 }

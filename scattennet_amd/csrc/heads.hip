@@ -9,26 +9,12 @@
 // All of it is latency-bound (one sample's alpha row depends on the previous frame's); the
 // HBM traffic is a few (B, T, C) passes.  Batch-major logits (B, T, C): the reference's
 // permute(1, 0, 2) (:245) is a view and never materialised.
-#include "common.h"
-#include "../../include/scatten.h"
-
-extern "C" void sca_set_error(const char* msg);
+#include "ctc.h"
 
 namespace {
 
 constexpr int CTC_THREADS = 256;
 constexpr int CTC_MAX_L = 2 * SCA_CTC_MAX_S + 1;
-constexpr float NEG_INF = -__builtin_huge_valf();
-
-__device__ __forceinline__ float lse3(float a, float b, float c) {
-  float m = fmaxf(a, fmaxf(b, c));
-  if (m == NEG_INF) m = 0.0f;
-  return __logf(__expf(a - m) + __expf(b - m) + __expf(c - m)) + m;
-}
-
-// log_probs element = clamp(log_softmax(x), -100, 0) with torch's (x - max) - log(sum) order
-__device__ __forceinline__ float ctc_lp_raw(float x, float m, float ls) { return (x - m) - ls; }
-__device__ __forceinline__ float ctc_lp(float raw) { return fminf(fmaxf(raw, -100.0f), 0.0f); }
 
 struct CtcDims {
   int B, T, C, S;
@@ -56,11 +42,9 @@ __device__ __forceinline__ void ctc_lengths(const int* in_len, const int* tgt_le
   Tb = min(Tb, d.T);
 }
 
-__device__ __forceinline__ int ctc_label(const int* lab, int Sb, int s, int C) {
+__device__ __forceinline__ int ctc_label(const int* lab, int s, int C) {
   if (!(s & 1)) return 0;
-  const int c = lab[(s - 1) >> 1];
-  (void)Sb;
-  return min(max(c, 0), C - 1);
+  return clampi(lab[(s - 1) >> 1], 0, C - 1);
 }
 
 // one wave per (b, t) row: max and log-sum-exp of the logits row
@@ -88,7 +72,7 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_alpha_beta_kernel(const float
   const int L = 2 * Sb + 1;
   const long Lm = 2L * d.S + 1;
   const int* lab = labels + (long)b * d.S;
-  for (int s = tid; s < L; s += CTC_THREADS) lab_s[s] = ctc_label(lab, Sb, s, d.C);
+  for (int s = tid; s < L; s += CTC_THREADS) lab_s[s] = ctc_label(lab, s, d.C);
   __syncthreads();
   const float* xb = x + (long)b * d.T * d.C;
   const float* rs = w.rowstat + 2L * b * d.T;
@@ -131,10 +115,7 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_alpha_beta_kernel(const float
   }
   if (!beta_pass && tid == 0) {
     // nll = -log(exp(alpha[Tb-1][L-1]) + exp(alpha[Tb-1][L-2])); zero_infinity
-    const float l1 = buf[cur][L - 1], l2 = buf[cur][L - 2];
-    float m = fmaxf(l1, l2);
-    if (m == NEG_INF) m = 0.0f;
-    w.nll[b] = -(__logf(__expf(l1 - m) + __expf(l2 - m)) + m);  // +inf kept: zero_infinity below
+    w.nll[b] = -ctc_end_loglik(buf[cur][L - 1], buf[cur][L - 2]);  // +inf kept: zero_infinity below
   }
 }
 
@@ -199,48 +180,38 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_grad_kernel(const float* __re
   if (tid < 64) {  // wave 0: the blank (every even state, plus odd states whose label is 0)
     float m = NEG_INF;
     for (int s = tid; s < L; s += 64)
-      if (!(s & 1) || ctc_label(lab, Sb, s, d.C) == 0) m = fmaxf(m, ab[s]);
+      if (!(s & 1) || ctc_label(lab, s, d.C) == 0) m = fmaxf(m, ab[s]);
     m = wave_max(m);
     float acc = 0.0f;
     if (m != NEG_INF)
       for (int s = tid; s < L; s += 64)
-        if (!(s & 1) || ctc_label(lab, Sb, s, d.C) == 0) acc += __expf(ab[s] - m);
+        if (!(s & 1) || ctc_label(lab, s, d.C) == 0) acc += __expf(ab[s] - m);
     acc = wave_sum(acc);
     if (tid == 0) g_s[0] = m == NEG_INF ? NEG_INF : __logf(acc) + m;
   } else {  // other waves: one thread per distinct non-blank label (its first occurrence)
     for (int j = tid - 64; j < Sb; j += CTC_THREADS - 64) {
-      const int c = ctc_label(lab, Sb, 2 * j + 1, d.C);
+      const int c = ctc_label(lab, 2 * j + 1, d.C);
       bool first = c != 0;
-      for (int k = 0; k < j && first; ++k) first = ctc_label(lab, Sb, 2 * k + 1, d.C) != c;
+      for (int k = 0; k < j && first; ++k) first = ctc_label(lab, 2 * k + 1, d.C) != c;
       if (!first) continue;
       float m = NEG_INF;
       for (int k = j; k < Sb; ++k)
-        if (ctc_label(lab, Sb, 2 * k + 1, d.C) == c) m = fmaxf(m, ab[2 * k + 1]);
+        if (ctc_label(lab, 2 * k + 1, d.C) == c) m = fmaxf(m, ab[2 * k + 1]);
       float acc = 0.0f;
       if (m != NEG_INF)
         for (int k = j; k < Sb; ++k)
-          if (ctc_label(lab, Sb, 2 * k + 1, d.C) == c) acc += __expf(ab[2 * k + 1] - m);
+          if (ctc_label(lab, 2 * k + 1, d.C) == c) acc += __expf(ab[2 * k + 1] - m);
       g_s[c] = m == NEG_INF ? NEG_INF : __logf(acc) + m;
     }
   }
   __syncthreads();
   const float m = w.rowstat[2 * row], ls = w.rowstat[2 * row + 1];
   const float nll = w.nll[b];
-  float part = 0.0f;
-  for (int c = tid; c < d.C; c += CTC_THREADS) {
-    const float raw = ctc_lp_raw(xr[c], m, ls);
+  ctc_grad_row_tail<CTC_THREADS>(xr, dr, d.C, m, ls, g_s, red, tid, [&](int c, float raw) {
     const float lp = ctc_lp(raw);
     // torch ctc_loss_backward: (exp(lp) - exp(lcab + nll - lp)) * grad_out
-    float g = (__expf(lp) - __expf(g_s[c] + nll - lp)) * gr;
-    if (!(raw >= -100.0f && raw <= 0.0f)) g = 0.0f;  // clamp(-100, 0) backward
-    g_s[c] = g;
-    part += g;
-  }
-  part = wave_sum(part);
-  if ((tid & 63) == 0) red[tid >> 6] = part;
-  __syncthreads();
-  const float G = red[0] + red[1] + red[2] + red[3];
-  for (int c = tid; c < d.C; c += CTC_THREADS) dr[c] = g_s[c] - __expf(ctc_lp_raw(xr[c], m, ls)) * G;
+    return (__expf(lp) - __expf(g_s[c] + nll - lp)) * gr;
+  });
 }
 
 // ------------------------------------------------------------------------------------ SeqKD
@@ -472,7 +443,7 @@ bool ctc_dims_ok(int B, int T, int C, int S) {
 
 }  // namespace
 
-// the row max / log-sum-exp pass, shared with the CTC decoders (decode.hip)
+// the row max / log-sum-exp pass of one tensor (ctc.h)
 void sca_ctc_rowstat_launch(const float* x, float* rowstat, long rows, int C, hipStream_t st) {
   hipLaunchKernelGGL(ctc_rowstat_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, x, rowstat, rows, C);
 }
@@ -495,8 +466,7 @@ extern "C" int sca_ctc_loss_fwd(const float* logits, const int* labels, const in
   hipLaunchKernelGGL(ctc_alpha_beta_kernel, dim3(B, 2), dim3(CTC_THREADS), 0, st, logits, labels, in_len, tgt_len,
                      d, ws);
   hipLaunchKernelGGL(ctc_finalize_kernel, dim3(1), dim3(256), 0, st, d, ws, nll, loss);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_ctc_loss_fwd: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status("sca_ctc_loss_fwd");
 }
 
 extern "C" int sca_ctc_loss_bwd(const float* logits, const int* labels, const int* in_len, const int* tgt_len, int B,
@@ -509,8 +479,7 @@ extern "C" int sca_ctc_loss_bwd(const float* logits, const int* labels, const in
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(ctc_grad_kernel, dim3(T, B), dim3(CTC_THREADS), 0, st, logits, labels, in_len, tgt_len,
                      CtcDims{B, T, C, S}, ws, dloss, dlogits);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_ctc_loss_bwd: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status("sca_ctc_loss_bwd");
 }
 
 extern "C" long sca_seqkd_workspace_floats(int R) { return 5L * R + 1; }
@@ -519,70 +488,68 @@ namespace {
 
 bool valid_args_ok(int T, const int* valid, int shift) { return T >= 1 && valid && shift >= 0 && shift <= 30; }
 
+int bad_arguments(const char* name) {
+  char msg[128];
+  snprintf(msg, sizeof(msg), "%s: bad arguments", name);
+  sca_set_error(msg);
+  return SCA_ERR_ARG;
+}
+
 template <bool VALID>
 int seqkd_fwd(const float* student, const float* teacher, int R, int C, int start, float temp, float weight,
               float lo, float hi, float* loss, float* ws, int T, const int* valid, int shift, void* stream,
-              const char* bad, const char* failed) {
+              const char* name) {
   if (R < 1 || C < 1 || start < 0 || start >= C || !(temp > 0.0f) || !student || !teacher || !loss || !ws ||
       (VALID && (!valid_args_ok(T, valid, shift) || R % T != 0))) {
-    sca_set_error(bad);
-    return SCA_ERR_ARG;
+    return bad_arguments(name);
   }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const KdArgs a{student, teacher, R, C, start, 1.0f / temp, weight * temp * temp, lo, hi, T, valid, shift};
   hipLaunchKernelGGL(kd_row_kernel<VALID>, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, st, a, ws);
   hipLaunchKernelGGL(kd_finalize_kernel<VALID>, dim3(1), dim3(256), 0, st, a, ws, loss);
-  if (hipGetLastError() != hipSuccess) { sca_set_error(failed); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status(name);
 }
 
 template <bool VALID>
 int seqkd_bwd(const float* student, const float* teacher, int R, int C, int start, float temp, const float* dloss,
               const float* ws, float* dstudent, float* dteacher, int T, const int* valid, int shift, void* stream,
-              const char* bad, const char* failed) {
+              const char* name) {
   if (R < 1 || C < 1 || start < 0 || start >= C || !(temp > 0.0f) || !student || !teacher || !dloss || !ws ||
       (!dstudent && !dteacher) || (VALID && (!valid_args_ok(T, valid, shift) || R % T != 0))) {
-    sca_set_error(bad);
-    return SCA_ERR_ARG;
+    return bad_arguments(name);
   }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const KdArgs a{student, teacher, R, C, start, 1.0f / temp, 0.0f, 0.0f, 0.0f, T, valid, shift};
   hipLaunchKernelGGL(kd_grad_kernel<VALID>, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, st, a, ws, dloss, dstudent,
                      dteacher);
-  if (hipGetLastError() != hipSuccess) { sca_set_error(failed); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status(name);
 }
 
 template <bool VALID>
 int lstm_cell_fwd(const float* gates, float* act, float* c, float* y, float* hp, int B, int T, int H, int ndir,
-                  int step, const int* valid, int shift, void* stream, const char* bad, const char* failed) {
+                  int step, const int* valid, int shift, void* stream, const char* name) {
   if (B < 1 || T < 1 || H < 1 || ndir < 1 || ndir > 2 || step < 0 || step >= T || !gates || !act || !c || !y ||
       !hp || (VALID && !valid_args_ok(T, valid, shift))) {
-    sca_set_error(bad);
-    return SCA_ERR_ARG;
+    return bad_arguments(name);
   }
   LstmArgs a{gates, act, c, y, hp, nullptr, nullptr, nullptr, nullptr, B, T, H, ndir, step, valid, shift};
   hipLaunchKernelGGL(lstm_cell_fwd_kernel<VALID>, dim3((B * H + 255) / 256, ndir), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), a);
-  if (hipGetLastError() != hipSuccess) { sca_set_error(failed); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status(name);
 }
 
 template <bool VALID>
 int lstm_cell_bwd(const float* dh, const float* dy, const float* act, const float* c, float* dc, float* dg, int B,
-                  int T, int H, int ndir, int step, const int* valid, int shift, void* stream, const char* bad,
-                  const char* failed) {
+                  int T, int H, int ndir, int step, const int* valid, int shift, void* stream, const char* name) {
   if (B < 1 || T < 1 || H < 1 || ndir < 1 || ndir > 2 || step < 0 || step >= T || !dy || !act || !c || !dc ||
       !dg || (step > 0 && !dh) || (VALID && !valid_args_ok(T, valid, shift))) {
-    sca_set_error(bad);
-    return SCA_ERR_ARG;
+    return bad_arguments(name);
   }
   LstmArgs a{nullptr, const_cast<float*>(act), const_cast<float*>(c), nullptr, nullptr, dh, dy, dc, dg,
              B, T, H, ndir, step, valid, shift};
   hipLaunchKernelGGL(lstm_cell_bwd_kernel<VALID>, dim3((B * H + 255) / 256, ndir), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), a);
-  if (hipGetLastError() != hipSuccess) { sca_set_error(failed); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status(name);
 }
 
 }  // namespace
@@ -590,27 +557,27 @@ int lstm_cell_bwd(const float* dh, const float* dy, const float* act, const floa
 extern "C" int sca_seqkd_fwd(const float* student, const float* teacher, int R, int C, int start, float temp,
                              float weight, float lo, float hi, float* loss, float* ws, void* stream) {
   return seqkd_fwd<false>(student, teacher, R, C, start, temp, weight, lo, hi, loss, ws, 1, nullptr, 0, stream,
-                          "sca_seqkd_fwd: bad arguments", "sca_seqkd_fwd: launch failed");
+                          "sca_seqkd_fwd");
 }
 
 extern "C" int sca_seqkd_valid_fwd(const float* student, const float* teacher, int R, int C, int start, float temp,
                                    float weight, float lo, float hi, float* loss, float* ws, int T,
                                    const int* valid_frames, int shift, void* stream) {
   return seqkd_fwd<true>(student, teacher, R, C, start, temp, weight, lo, hi, loss, ws, T, valid_frames, shift,
-                         stream, "sca_seqkd_valid_fwd: bad arguments", "sca_seqkd_valid_fwd: launch failed");
+                         stream, "sca_seqkd_valid_fwd");
 }
 
 extern "C" int sca_seqkd_bwd(const float* student, const float* teacher, int R, int C, int start, float temp,
                              const float* dloss, const float* ws, float* dstudent, float* dteacher, void* stream) {
   return seqkd_bwd<false>(student, teacher, R, C, start, temp, dloss, ws, dstudent, dteacher, 1, nullptr, 0, stream,
-                          "sca_seqkd_bwd: bad arguments", "sca_seqkd_bwd: launch failed");
+                          "sca_seqkd_bwd");
 }
 
 extern "C" int sca_seqkd_valid_bwd(const float* student, const float* teacher, int R, int C, int start, float temp,
                                    const float* dloss, const float* ws, float* dstudent, float* dteacher, int T,
                                    const int* valid_frames, int shift, void* stream) {
   return seqkd_bwd<true>(student, teacher, R, C, start, temp, dloss, ws, dstudent, dteacher, T, valid_frames, shift,
-                         stream, "sca_seqkd_valid_bwd: bad arguments", "sca_seqkd_valid_bwd: launch failed");
+                         stream, "sca_seqkd_valid_bwd");
 }
 
 extern "C" int sca_clamp(const float* x, float* y, const float* dy, float* dx, long n, float lo, float hi,
@@ -623,31 +590,28 @@ extern "C" int sca_clamp(const float* x, float* y, const float* dy, float* dx, l
   const long blocks = (n + 255) / 256;
   hipLaunchKernelGGL(clamp_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), x, y, dy, dx, n, lo, hi);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_clamp: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status("sca_clamp");
 }
 
 extern "C" int sca_lstm_cell_fwd(const float* gates, float* act, float* c, float* y, float* hp, int B, int T, int H,
                                  int ndir, int step, void* stream) {
-  return lstm_cell_fwd<false>(gates, act, c, y, hp, B, T, H, ndir, step, nullptr, 0, stream,
-                              "sca_lstm_cell_fwd: bad arguments", "sca_lstm_cell_fwd: launch failed");
+  return lstm_cell_fwd<false>(gates, act, c, y, hp, B, T, H, ndir, step, nullptr, 0, stream, "sca_lstm_cell_fwd");
 }
 
 extern "C" int sca_lstm_cell_valid_fwd(const float* gates, float* act, float* c, float* y, float* hp, int B, int T,
                                        int H, int ndir, int step, const int* valid_frames, int shift, void* stream) {
   return lstm_cell_fwd<true>(gates, act, c, y, hp, B, T, H, ndir, step, valid_frames, shift, stream,
-                             "sca_lstm_cell_valid_fwd: bad arguments", "sca_lstm_cell_valid_fwd: launch failed");
+                             "sca_lstm_cell_valid_fwd");
 }
 
 extern "C" int sca_lstm_cell_bwd(const float* dh, const float* dy, const float* act, const float* c, float* dc,
                                  float* dg, int B, int T, int H, int ndir, int step, void* stream) {
-  return lstm_cell_bwd<false>(dh, dy, act, c, dc, dg, B, T, H, ndir, step, nullptr, 0, stream,
-                              "sca_lstm_cell_bwd: bad arguments", "sca_lstm_cell_bwd: launch failed");
+  return lstm_cell_bwd<false>(dh, dy, act, c, dc, dg, B, T, H, ndir, step, nullptr, 0, stream, "sca_lstm_cell_bwd");
 }
 
 extern "C" int sca_lstm_cell_valid_bwd(const float* dh, const float* dy, const float* act, const float* c, float* dc,
                                        float* dg, int B, int T, int H, int ndir, int step, const int* valid_frames,
                                        int shift, void* stream) {
   return lstm_cell_bwd<true>(dh, dy, act, c, dc, dg, B, T, H, ndir, step, valid_frames, shift, stream,
-                             "sca_lstm_cell_valid_bwd: bad arguments", "sca_lstm_cell_valid_bwd: launch failed");
+                             "sca_lstm_cell_valid_bwd");
 }

@@ -9,31 +9,16 @@
 //        then the clamp gate and the log-softmax backward: ONE dense pass for the N hypotheses
 // No float atomics; every sum over entries, states and clips runs in a fixed order, so the
 // results are deterministic and a replayed capture is bitwise the eager call.
-#include "common.h"
+#include "ctc.h"
 #include "wer_pair.h"
-#include "../../include/scatten.h"
-
-extern "C" void sca_set_error(const char* msg);
 
 namespace {
 
-constexpr float NEG_INF = -__builtin_huge_valf();
 constexpr int MW_MAX_L = 2 * SCA_WER_MAX_LEN + 1;  // states of the longest hypothesis
 constexpr int MW_K = (MW_MAX_L + 63) / 64;         // states per lane of the recursion's wave
 constexpr int MW_PAD = 2;                          // -inf cells either side of an LDS state row
 constexpr int MW_GRAD_THREADS = 256;
 constexpr int MW_CLIPS_ONE_GROUP = 64;  // batches up to this size: per-clip statistics and the loss in one workgroup
-
-// the arithmetic of the CTC loss (heads.hip): log-sum-exp of the three predecessors, and
-// log_probs = clamp(log_softmax(x), -100, 0) with torch's (x - max) - log(sum) order
-__device__ __forceinline__ float lse3(float a, float b, float c) {
-  float m = fmaxf(a, fmaxf(b, c));
-  if (m == NEG_INF) m = 0.0f;
-  return __logf(__expf(a - m) + __expf(b - m) + __expf(c - m)) + m;
-}
-__device__ __forceinline__ float lp_raw(float x, float m, float ls) { return (x - m) - ls; }
-__device__ __forceinline__ float lp_clamp(float raw) { return fminf(fmaxf(raw, -100.0f), 0.0f); }
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 struct MwDims {
   int B, N, T, C, H, R;
@@ -55,13 +40,6 @@ struct MwWs {
     lossb = w + BN;
   }
 };
-
-// orders this wave's LDS writes before its later LDS reads (other lanes' cells): the LDS
-// executes one wave's operations in order, the fence keeps the compiler from moving them
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
 
 // One wave64 per (entry, clip, direction) of mwer_entry_kernel: z = 0 the alpha recursion over
 // the frames [0, in_len), z = 1 the beta one.  Lane l holds states l, l + 64, ..; a frame's row
@@ -108,7 +86,7 @@ __device__ __forceinline__ void mwer_alpha_beta(const float* __restrict__ x, con
   const float* rs = w.rowstat + 2L * b * d.T;
   float* out = (beta_pass ? w.beta : w.alpha) + e * d.T * w.Lm;
   auto emit = [&](int t, int k) {
-    return lp_clamp(lp_raw(xb[(long)t * d.C + lab[k]], rs[2 * t], rs[2 * t + 1]));
+    return ctc_lp(ctc_lp_raw(xb[(long)t * d.C + lab[k]], rs[2 * t], rs[2 * t + 1]));
   };
   if (lane < MW_PAD) {
     buf[0][lane] = buf[1][lane] = NEG_INF;
@@ -157,10 +135,7 @@ __device__ __forceinline__ void mwer_alpha_beta(const float* __restrict__ x, con
   wave_lds_sync();
   if (!beta_pass && lane == 0) {
     // ll = log(exp(alpha[Tb-1][L-1]) + exp(alpha[Tb-1][L-2])); the pad cell is -inf for L = 1
-    const float l1 = buf[cur][MW_PAD + L - 1], l2 = buf[cur][MW_PAD + L - 2];
-    float m = fmaxf(l1, l2);
-    if (m == NEG_INF) m = 0.0f;
-    w.ll[e] = __logf(__expf(l1 - m) + __expf(l2 - m)) + m;  // -inf: the hypothesis does not fit
+    w.ll[e] = ctc_end_loglik(buf[cur][MW_PAD + L - 1], buf[cur][MW_PAD + L - 2]);  // -inf: the hypothesis does not fit
   }
 }
 
@@ -255,8 +230,8 @@ __global__ __launch_bounds__(64) void mwer_loss_sum_kernel(MwDims d, const float
 
 // grid (T, B), one workgroup per logits row: g[c] = sum_n dloss w_n occ_n(t, c), n ascending;
 // every class of one entry is added by exactly one thread (the blank by thread 0, a label by
-// the thread of its first occurrence, which sums the later ones in order).  Then the clamp
-// gate, the row sum and the log-softmax backward, as ctc_grad_kernel (heads.hip).
+// the thread of its first occurrence, which sums the later ones in order).  Then the CTC
+// loss's row tail (ctc_grad_row_tail, ctc.h): the clamp gate, the row sum, the log-softmax backward.
 __global__ __launch_bounds__(MW_GRAD_THREADS) void mwer_grad_kernel(const float* __restrict__ x,
                                                                     const int* __restrict__ in_len,
                                                                     const int* __restrict__ tokens,
@@ -284,7 +259,7 @@ __global__ __launch_bounds__(MW_GRAD_THREADS) void mwer_grad_kernel(const float*
   }
   const float m = w.rowstat[2 * row], ls = w.rowstat[2 * row + 1];
   for (int c = tid; c < d.C; c += MW_GRAD_THREADS) g_s[c] = 0.0f;
-  const float lp0 = lp_clamp(lp_raw(xr[0], m, ls));
+  const float lp0 = ctc_lp(ctc_lp_raw(xr[0], m, ls));
   for (int n = 0; n < cnt; ++n) {
     const long e = (long)b * d.N + n;
     const float wn = w.w[e] * gl;
@@ -309,7 +284,7 @@ __global__ __launch_bounds__(MW_GRAD_THREADS) void mwer_grad_kernel(const float*
         bool first = c != 0;
         for (int k = 0; k < j && first; ++k) first = tok_s[k] != c;
         if (!first) continue;
-        const float lpc = lp_clamp(lp_raw(xr[c], m, ls));
+        const float lpc = ctc_lp(ctc_lp_raw(xr[c], m, ls));
         float acc = 0.0f;
         for (int k = j; k < len; ++k)
           if (tok_s[k] == c) acc += __expf(ab[2 * k + 1] - lpc);
@@ -318,19 +293,7 @@ __global__ __launch_bounds__(MW_GRAD_THREADS) void mwer_grad_kernel(const float*
     }
   }
   __syncthreads();
-  float part = 0.0f;
-  for (int c = tid; c < d.C; c += MW_GRAD_THREADS) {
-    const float raw = lp_raw(xr[c], m, ls);
-    float g = g_s[c];
-    if (!(raw >= -100.0f && raw <= 0.0f)) g = 0.0f;  // clamp(-100, 0) backward
-    g_s[c] = g;
-    part += g;
-  }
-  part = wave_sum(part);
-  if ((tid & 63) == 0) red[tid >> 6] = part;
-  __syncthreads();
-  const float G = red[0] + red[1] + red[2] + red[3];
-  for (int c = tid; c < d.C; c += MW_GRAD_THREADS) dr[c] = g_s[c] - __expf(lp_raw(xr[c], m, ls)) * G;
+  ctc_grad_row_tail<MW_GRAD_THREADS>(xr, dr, d.C, m, ls, g_s, red, tid, [&](int c, float) { return g_s[c]; });
 }
 
 bool mwer_dims_ok(int B, int N, int T, int C, int H, int R) {
@@ -366,8 +329,7 @@ extern "C" int sca_mwer_fwd(const float* logits, const int* in_len, const int* t
   hipLaunchKernelGGL(mwer_clip_kernel, dim3(groups), dim3(256), 0, st, count, errors, d, posterior_scale, ws, loglik,
                      posterior, risk, loss);
   if (groups > 1) hipLaunchKernelGGL(mwer_loss_sum_kernel, dim3(1), dim3(64), 0, st, d, ws, loss);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_mwer_fwd: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status("sca_mwer_fwd");
 }
 
 extern "C" int sca_mwer_bwd(const float* logits, const int* in_len, const int* tokens, const int* out_len,
@@ -380,6 +342,5 @@ extern "C" int sca_mwer_bwd(const float* logits, const int* in_len, const int* t
   }
   hipLaunchKernelGGL(mwer_grad_kernel, dim3(T, B), dim3(MW_GRAD_THREADS), 0, reinterpret_cast<hipStream_t>(stream),
                      logits, in_len, tokens, out_len, count, MwDims{B, N, T, C, H, 1}, ws, dloss, dlogits);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_mwer_bwd: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status("sca_mwer_bwd");
 }

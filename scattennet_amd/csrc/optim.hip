@@ -10,8 +10,6 @@
 #include "../../include/scatten.h"
 #include "common.h"
 
-extern "C" void sca_set_error(const char* msg);
-
 namespace {
 
 constexpr int OPT_THREADS = 256;
@@ -266,8 +264,7 @@ extern "C" int sca_optim_grad_sqnorm(const sca_optim_tensor* tensors, const sca_
   }
   hipLaunchKernelGGL(optim_grad_sqnorm_kernel, dim3(optim_grid(max_blocks, nchunks)), dim3(OPT_THREADS), 0,
                      (hipStream_t)stream, tensors, chunks, nchunks, loss, state, partials);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_optim_grad_sqnorm: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status("sca_optim_grad_sqnorm");
 }
 
 extern "C" int sca_optim_adam_step(const sca_optim_tensor* tensors, const sca_optim_chunk* chunks, int nchunks,
@@ -280,8 +277,7 @@ extern "C" int sca_optim_adam_step(const sca_optim_tensor* tensors, const sca_op
   const int grid = optim_grid(max_blocks, nchunks);  // also the number of partials of pass 1
   hipLaunchKernelGGL(optim_adam_step_kernel, dim3(grid), dim3(OPT_THREADS), 0, (hipStream_t)stream, tensors, chunks,
                      nchunks, groups, grid, max_norm, state, partials);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_optim_adam_step: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status("sca_optim_adam_step");
 }
 
 extern "C" int sca_optim_scale_grads(const sca_optim_tensor* tensors, const sca_optim_chunk* chunks, int nchunks,
@@ -294,8 +290,7 @@ extern "C" int sca_optim_scale_grads(const sca_optim_tensor* tensors, const sca_
   const int grid = optim_grid(max_blocks, nchunks);
   hipLaunchKernelGGL(optim_scale_grads_kernel, dim3(grid), dim3(OPT_THREADS), 0, (hipStream_t)stream, tensors, chunks,
                      nchunks, grid, max_norm, state, partials);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_optim_scale_grads: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status("sca_optim_scale_grads");
 }
 
 extern "C" int sca_optim_upload(void* dst, const void* src, long bytes, void* stream) {

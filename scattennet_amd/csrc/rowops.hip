@@ -809,9 +809,7 @@ __global__ __launch_bounds__(256) void normalize_parts_kernel(const NormArgs a) 
   } else {
     for (int e = lane; e < n2; e += 64) F[e] = src[e];
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_lds_sync();
   for (int p = 0; p < a.nparts; ++p) {
     const int j0 = a.part_off[p], j1 = a.part_off[p + 1];
     float mnx = INFINITY, mny = INFINITY, mxx = -INFINITY, mxy = -INFINITY;
@@ -843,9 +841,7 @@ __global__ __launch_bounds__(256) void normalize_parts_kernel(const NormArgs a) 
       if (ex != 0.f) F[2 * k] = (F[2 * k] - s0) / ex;
       if (ey != 0.f) F[2 * k + 1] = (F[2 * k + 1] - s1) / ey;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the next part may share joints
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();  // the next part may share joints
   }
   for (int e = lane; e < n2; e += 64) dst[e] = F[e];
 }
@@ -904,8 +900,6 @@ __global__ __launch_bounds__(256) void key_valid_kernel(const KeyValidArgs a) {
 }  // namespace
 
 // ------------------------------------------------------------------------------ C ABI
-extern "C" void sca_set_error(const char* msg);
-
 extern "C" int sca_layernorm_fwd(int nprob, const sca_ln_fwd_problem* probs, int rows, int N, int r_mod,
                                  int r_off, float eps, void* stream) {
   if (nprob < 1 || nprob > SCA_LN_MAX_PROBLEMS || N < 1 || rows < 0 || r_mod < 1) {
@@ -933,8 +927,7 @@ extern "C" int sca_layernorm_fwd(int nprob, const sca_ln_fwd_problem* probs, int
     case 4: hipLaunchKernelGGL(ln_fwd_kernel<4>, grid, dim3(256), 0, st, a); break;
     default: hipLaunchKernelGGL(ln_fwd_kernel<0>, grid, dim3(256), 0, st, a); break;
   }
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_layernorm_fwd: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status("sca_layernorm_fwd");
 }
 
 extern "C" int sca_maxpool_t_fwd(int nprob, const sca_pool_problem* probs, int B, int T, int C, void* stream) {
@@ -949,8 +942,7 @@ extern "C" int sca_maxpool_t_fwd(int nprob, const sca_pool_problem* probs, int B
   if (n == 0) return SCA_OK;
   const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
   hipLaunchKernelGGL(maxpool_t_fwd_kernel, dim3(blocks, nprob), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_maxpool_t_fwd: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status("sca_maxpool_t_fwd");
 }
 
 extern "C" int sca_maxpool_t_bwd(int nprob, const sca_pool_problem* probs, int B, int T, int C, void* stream) {
@@ -965,8 +957,7 @@ extern "C" int sca_maxpool_t_bwd(int nprob, const sca_pool_problem* probs, int B
   if (n == 0) return SCA_OK;
   const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
   hipLaunchKernelGGL(maxpool_t_bwd_kernel, dim3(blocks, nprob), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_maxpool_t_bwd: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status("sca_maxpool_t_bwd");
 }
 
 template <bool BWD, bool VALID = false>
@@ -1001,8 +992,7 @@ int launch_softmax(int nprob, const sca_softmax_problem* probs, int rows, int N,
     default: SCA_SM(0) break;
   }
 #undef SCA_SM
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_softmax_rows: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status("sca_softmax_rows");
 }
 
 extern "C" int sca_softmax_rows_fwd(int nprob, const sca_softmax_problem* probs, int rows, int N, void* stream) {
@@ -1038,8 +1028,7 @@ extern "C" int sca_gelu_bwd(int nprob, const sca_gelu_bwd_problem* probs, long n
   const long blocks = (n / 4 + 255) / 256;
   dim3 grid((unsigned)(blocks < 2048 ? (blocks > 0 ? blocks : 1) : 2048), nprob);
   hipLaunchKernelGGL(gelu_bwd_kernel, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_gelu_bwd: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status("sca_gelu_bwd");
 }
 
 extern "C" int sca_sum_tensors(int nprob, const sca_sum_problem* probs, long n, void* stream) {
@@ -1067,8 +1056,7 @@ extern "C" int sca_sum_tensors(int nprob, const sca_sum_problem* probs, long n, 
   const long blocks = (n / 4 + 255) / 256;
   dim3 grid((unsigned)(blocks < 1024 ? (blocks > 0 ? blocks : 1) : 1024), nprob);
   hipLaunchKernelGGL(sum_tensors_kernel, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_sum_tensors: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status("sca_sum_tensors");
 }
 
 extern "C" int sca_layernorm_bwd_blocks(int rows) { return (rows + LN_BWD_ROWS - 1) / LN_BWD_ROWS; }
@@ -1092,7 +1080,7 @@ extern "C" int sca_layernorm_bwd(int nprob, const sca_ln_bwd_problem* probs, int
     case 4: hipLaunchKernelGGL(ln_bwd_kernel<4>, dim3(a.nblk, nprob), dim3(256), 0, st, a); break;
     default: hipLaunchKernelGGL(ln_bwd_kernel<0>, dim3(a.nblk, nprob), dim3(256), 0, st, a); break;
   }
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_layernorm_bwd: launch failed"); return SCA_ERR_LAUNCH; }
+  if (sca_launch_status("sca_layernorm_bwd") != SCA_OK) return SCA_ERR_LAUNCH;
   // dgamma / dbeta = fixed-order sums of the per-workgroup partial rows (problems with
   // dgamma == NULL leave them in `partial` for the caller's own sca_reduce_rows)
   ReduceArgs r;
@@ -1141,8 +1129,7 @@ extern "C" int sca_coord_map_fwd(int nprob, const sca_coord_map_problem* probs, 
   a.rows = rows; a.K_all = K_all; a.N = N;
   dim3 grid((rows + MAP_ROWS - 1) / MAP_ROWS, nprob);
   hipLaunchKernelGGL(coord_map_fwd_kernel, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_coord_map_fwd: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status("sca_coord_map_fwd");
 }
 
 extern "C" int sca_coord_map_bwd_chunks(int rows) { return (rows + MAP_CHUNK - 1) / MAP_CHUNK; }
@@ -1164,7 +1151,7 @@ extern "C" int sca_coord_map_bwd(int nprob, const sca_coord_map_bwd_problem* pro
   bool any_dkp = false;
   for (int i = 0; i < nprob; ++i) any_dkp |= probs[i].dkp != nullptr;
   if (any_dkp) hipLaunchKernelGGL(coord_map_bwd_kp_kernel, dim3((rows + 3) / 4, nprob), dim3(256), 0, st, a);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_coord_map_bwd: launch failed"); return SCA_ERR_LAUNCH; }
+  if (sca_launch_status("sca_coord_map_bwd") != SCA_OK) return SCA_ERR_LAUNCH;
   // dW = fixed-order sum over row chunks, all problems in one launch
   int maxK = 0;
   for (int i = 0; i < nprob; ++i) maxK = maxK > probs[i].K ? maxK : probs[i].K;
@@ -1195,8 +1182,7 @@ extern "C" int sca_dropout(int nprob, const sca_dropout_problem* probs, long row
   const long want = (a.n / 4 + 255) / 256;
   const int blocks = (int)(want < 2048 ? (want > 0 ? want : 1) : 2048);
   hipLaunchKernelGGL(dropout_kernel, dim3(blocks, nprob), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_dropout: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status("sca_dropout");
 }
 
 extern "C" int sca_key_valid(const void* mask, int dtype, float* key_valid, long n, void* stream) {
@@ -1209,8 +1195,7 @@ extern "C" int sca_key_valid(const void* mask, int dtype, float* key_valid, long
   const int blocks = (int)(want < 1024 ? want : 1024);
   hipLaunchKernelGGL(key_valid_kernel, dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                      KeyValidArgs{mask, key_valid, n, dtype});
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_key_valid: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status("sca_key_valid");
 }
 
 // p[0 .. n) = 0: float4 stores over the 16-byte-aligned body, scalar stores at the ends
@@ -1236,8 +1221,7 @@ extern "C" int sca_zero(float* p, long n, void* stream) {
   const long want = (n4 + 255) / 256;
   const int blocks = (int)(want < 1 ? 1 : (want < 2048 ? want : 2048));
   hipLaunchKernelGGL(zero_kernel, dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, n, head, n4);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_zero: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status("sca_zero");
 }
 
 extern "C" int sca_normalize_parts(const float* kp_in, float* kp_out, const int* lengths, int B, int T, int K_all,
@@ -1252,8 +1236,7 @@ extern "C" int sca_normalize_parts(const float* kp_in, float* kp_out, const int*
   NormArgs a{kp_in, kp_out, lengths, part_off, part_idx, B, T, K_all, nparts, nullptr, nullptr};
   hipLaunchKernelGGL(normalize_parts_kernel, dim3((unsigned)((frames + 3) / 4)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), a);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_normalize_parts: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status("sca_normalize_parts");
 }
 
 extern "C" int sca_prepare_keypoints(const float* raw, const int* src_row, const float* affine, const int* lengths,
@@ -1269,6 +1252,5 @@ extern "C" int sca_prepare_keypoints(const float* raw, const int* src_row, const
   NormArgs a{raw, kp_out, lengths, part_off, part_idx, B, T, K_all, nparts, src_row, affine};
   hipLaunchKernelGGL(normalize_parts_kernel, dim3((unsigned)((frames + 3) / 4)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), a);
-  if (hipGetLastError() != hipSuccess) { sca_set_error("sca_prepare_keypoints: launch failed"); return SCA_ERR_LAUNCH; }
-  return SCA_OK;
+  return sca_launch_status("sca_prepare_keypoints");
 }

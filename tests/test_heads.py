@@ -155,6 +155,46 @@ def test_hip_ctc_matches_oracle(B, T, C, S, concat):
     np.testing.assert_allclose(dx, ref_dx, **GRAD_TOL)
 
 
+def _clamp_gate_case():
+    """B = 2, T = 5, C = 7, S = 2.  Clip 0 (labels 3, 5): at frame 2 class 6 holds the row maximum,
+    the blank and label 3 lie 94 below it and label 5 lies 130 below it, so log_softmax of (0, 2, 5)
+    is under -100, the clamp's gate is closed there, and every path pays about 94 at that frame: the
+    paths through the clamped cell are e^-6 of the likelihood, which an open gate would show in the
+    gradient at 1e-3.  Clip 1 (label 2) has 3 of the 5 frames."""
+    x = np.zeros((2, 5, 7), np.float32)
+    x[0, :2, 3] = 8.0
+    x[0, 3:, 5] = 8.0
+    x[0, 2] = [-94.0, -110.0, -110.0, -94.0, -110.0, -130.0, 0.0]
+    x[1] = np.linspace(-1.0, 1.0, 35, dtype=np.float32).reshape(5, 7)
+    x[1, :3, 2] += 4.0
+    return {"logits": x, "labels": np.array([[3, 5], [2, 1]], np.int32), "in_len": np.array([5, 3], np.int32),
+            "tgt_len": np.array([2, 1], np.int32)}
+
+
+def test_clamp_gate_case_closes_the_gate_in_the_oracle():
+    f = _clamp_gate_case()
+    raw = torch.log_softmax(torch.from_numpy(f["logits"][0, 2]).double(), -1)
+    assert raw[5] < -100.0 and raw[0] > -100.0 and raw[3] > -100.0
+    loss, nll, dx = O.ctc_compute_loss(f["logits"], f["labels"], f["in_len"], f["tgt_len"])
+    assert 90.0 < nll[0] < 100.0 and 0.0 < loss < 100.0  # inside clamp(0, 100): the loss has a gradient
+    assert abs(dx[0, 2, 5]) < 1e-40  # gated: only the softmax term, ~exp(-130)
+    assert np.abs(dx[0, 2]).max() > 1e-3 and not dx[1, 3:].any()
+
+
+@pytest.mark.gpu
+def test_hip_ctc_clamp_gate_and_short_clip():
+    """The clamp(-100, 0) gate of the CTC gradient row, a clip shorter than T and C = 7 (most of the
+    row loop's 256 threads idle) against the oracle."""
+    f = _clamp_gate_case()
+    ref_loss, ref_nll, ref_dx = O.ctc_compute_loss(f["logits"], f["labels"], f["in_len"], f["tgt_len"])
+    loss, nll, dx = _hip_ctc(f)
+    np.testing.assert_allclose(nll, ref_nll, rtol=1e-5, atol=2e-4)
+    np.testing.assert_allclose(loss, ref_loss, **LOSS_TOL)
+    np.testing.assert_allclose(dx, ref_dx, **GRAD_TOL)
+    assert abs(float(dx[0, 2, 5])) < 1e-30  # the gated element: the softmax term alone
+    assert not dx[1, 3:].any() and np.abs(dx[1, :3]).max() > 0  # rows past the input length are exactly 0
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("path", KD_FIX, ids=os.path.basename)
 def test_hip_seqkd_matches_reference(path):
