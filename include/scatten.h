@@ -59,6 +59,9 @@
  *   sca_ctc_beam_decode*_nbest  (no counterpart; the interface of the decoder's top_paths) the N
  *   sca_nbest_rescore/mbr/gather  best labellings of the beam search, their rescoring with a
  *                          bigram gloss model, the posterior over the list and MBR selection
+ *   sca_mwer_fwd/bwd, sca_mwer_heads_fwd/bwd  (no counterpart) the minimum-WER training loss over
+ *                          an n-best list: one head, or G heads with the reference as one more
+ *                          entry and the gloss model's prior inside the posterior
  *   sca_finite_scan      the isnan().any() / isinf().any() tests of MSCA_Net.forward
  *                          (model/__init__.py:130-235), all tensors in one launch
  *   sca_step_report        total_loss (model/__init__.py:207,237), the loss terms the
@@ -829,6 +832,64 @@ int sca_mwer_fwd(const float* logits, const int* in_len, const int* tokens, cons
 int sca_mwer_bwd(const float* logits, const int* in_len, const int* tokens, const int* out_len, const int* count,
                  int B, int N, int T, int C, int H, const float* dloss, const float* ws, float* dlogits,
                  void* stream);
+
+/* ---- training: MWER with the reference in the list, the gloss model's prior, G heads --------
+ * sca_mwer_heads_fwd / sca_mwer_heads_bwd: the loss above over the logits of G heads in one
+ * call, 1 <= G <= SCA_EVAL_MAX_HEADS (fp32 (B, T, C) per head, by value in `heads`), optionally
+ * with the clip's reference as one more entry of its list and with sca_nbest_rescore's prior
+ * inside the posterior.  Inputs per head g and clip b: the list tokens (G, B, N, H), out_len
+ * (G, B, N), count (G, B); in_len (B) and the references ref (B, R), ref_len (B) are shared by
+ * the heads.  lp, ll_n, the fit rule, err_n and the clamping of lengths are exactly those of
+ * sca_mwer_fwd.
+ *   Slots: M = N + 1 with with_ref != 0, else M = N.  Slots 0 .. N-1 are the list's.  Slot N is
+ *     the reference of clip b: its labels ref[b, :ref_len_b], ll_N its exact CTC log-likelihood
+ *     over [0, in_len_b) (the same recursion; the reference may be longer than H: the lattice row
+ *     has 2 max(H, R) + 1 states), err_N = 0.
+ *   Slot N is valid iff ll_N is finite or NaN, as for any entry, AND the reference is not in the
+ *     list already: no entry n < count has err_n == 0.  Under the alignment's costs an error
+ *     count of 0 holds exactly when the two sequences are equal, and a list that held the
+ *     reference twice would double its mass.  ref_valid (G, B) int32 says whether slot N is in V
+ *     (0 without with_ref).  loglik[.., N] is the reference's ll whenever it fits and -inf
+ *     otherwise, also where the slot is a duplicate and not in V.  Where in_len >= ref_len +
+ *     adjacent repeats, so that the CTC loss's rule T_b = max(in_len, 1, S_b) changes nothing,
+ *     it is -nll of sca_ctc_loss_fwd for the clip.
+ *   Prior: lmterm_n = lm_weight * lm(h_n) + length_bonus * len(h_n), lm(h) being
+ *     sca_nbest_rescore's and the same device code: class 0 is the boundary, lm(empty) =
+ *     lm[0, 0], lm = NULL means lm(h) = 0.  It applies to the reference slot too.
+ *   z_n = posterior_scale * (ll_n + lmterm_n), post = softmax over V of z; ebar, d_n, risk,
+ *     loss_b and w_n as above over the enlarged V; loss (G): one mean over the B clips per head.
+ *     The prior is a constant of the posterior, so the gradient formula is unchanged; the
+ *     occupancies of slot N come from the reference's own lattice and are accumulated last.  A
+ *     clip whose only valid slot is the reference has zero rows.
+ * Outputs of fwd: loglik, posterior (G, B, M) fp32, errors (G, B, M) int32 (0 in slot N),
+ * ref_valid (G, B) int32, risk (G, B), loss (G).  bwd: dloss (G floats, device), dlogits: the G
+ * tensors (B, T, C) by value in a sca_mwer_grads; every element is written.  ws:
+ * sca_mwer_heads_workspace_floats(G, B, N, T, H, R, with_ref) floats (0 for sizes < 1), kept
+ * between the forward and the backward; bwd takes the forward's G, sizes and with_ref.
+ * With lm_weight = 0, length_bonus = 0 and a finite table every output is bitwise the lm = NULL
+ * call's; without with_ref and with lm = NULL, weight 0 and bonus 0, head g's outputs are
+ * bitwise sca_mwer_fwd / sca_mwer_bwd's on heads->logits[g]; head g of a grouped call is
+ * bitwise the G = 1 call on that head.
+ * Limits, validated before any GPU call: those of sca_mwer_fwd with G B <= 65535, and finite
+ * lm_weight and length_bonus; N = 32 with the reference gives 33 slots.  The launches are
+ * sca_mwer_fwd's, over (head, clip) pairs p = g B + b: three forward (four above 64 pairs), the
+ * reference slot one more x-index of the second and the prior computed beside the alignment, not
+ * on the recursions' chain; one backward.  The list is never copied.  Nothing allocates, copies
+ * or synchronises (capturable); no float atomics, every reduction runs in a fixed order, and a
+ * replayed capture is bitwise the eager call.                                                */
+typedef struct {
+  float* dlogits[SCA_EVAL_MAX_HEADS]; /* entries [G, 8) are ignored */
+} sca_mwer_grads;
+long sca_mwer_heads_workspace_floats(int G, int B, int N, int T, int H, int R, int with_ref);
+int sca_mwer_heads_fwd(const sca_decode_heads* heads, int G, const int* in_len, const int* tokens,
+                       const int* out_len, const int* count, const int* ref, const int* ref_len, int B, int N, int T,
+                       int C, int H, int R, int with_ref, const float* lm, float lm_weight, float length_bonus,
+                       float posterior_scale, float* loglik, float* posterior, int* errors, int* ref_valid,
+                       float* risk, float* loss, float* ws, void* stream);
+int sca_mwer_heads_bwd(const sca_decode_heads* heads, int G, const int* in_len, const int* tokens,
+                       const int* out_len, const int* count, const int* ref, const int* ref_len, int B, int N, int T,
+                       int C, int H, int R, int with_ref, const float* dloss, const float* ws,
+                       const sca_mwer_grads* dlogits, void* stream);
 
 /* ---- evaluation: CTC forced alignment (gloss spans and confidences) -----------------------
  * The best single path of G heads' logits through given label sequences: for every (head g,

@@ -148,6 +148,10 @@ class DecodeHeads(ctypes.Structure):
     _fields_ = [("logits", c_void_p * EVAL_MAX_HEADS)]
 
 
+class MwerGrads(ctypes.Structure):
+    _fields_ = [("dlogits", c_void_p * EVAL_MAX_HEADS)]
+
+
 class EnsembleWeights(ctypes.Structure):
     _fields_ = [("w", c_float * EVAL_MAX_HEADS)]
 
@@ -234,6 +238,10 @@ EXPORTS = {
     "sca_mwer_workspace_floats": ([c_int] * 4, c_long),
     "sca_mwer_fwd": ([c_void_p] * 7 + [c_int] * 6 + [c_float] + [c_void_p] * 7, c_int),
     "sca_mwer_bwd": ([c_void_p] * 5 + [c_int] * 5 + [c_void_p] * 4, c_int),
+    "sca_mwer_heads_workspace_floats": ([c_int] * 7, c_long),
+    "sca_mwer_heads_fwd": ([c_void_p, c_int] + [c_void_p] * 6 + [c_int] * 7 + [c_void_p] + [c_float] * 3 +
+                           [c_void_p] * 8, c_int),
+    "sca_mwer_heads_bwd": ([c_void_p, c_int] + [c_void_p] * 6 + [c_int] * 7 + [c_void_p] * 4, c_int),
     "sca_eval_accumulate": ([c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
                              c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p], c_int),
     "sca_ctc_align_workspace_bytes": ([c_int] * 4, c_long),

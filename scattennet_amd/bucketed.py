@@ -248,7 +248,9 @@ class BucketedTrainStep(BucketedStep):
     label count per clip (at most the CTC kernels' limit).  `step` uploads the optimizer's
     hyper-parameters before a replay when a scheduler changed them.  `mwer`: None or an `MWER`,
     handed to `train_step`; the added frames lie past `input_lengths`, so the MWER loss and its
-    gradients are those of the unpadded batch.
+    gradients are those of the unpadded batch; that holds for every form of the spec (several
+    heads, the reference as an entry, the gloss model's prior, the fused search): the padded
+    labels lie past `gloss_lengths` as the frames lie past `input_lengths`.
 
     Memory: every bucket keeps its own graph memory pool — all activations, gradients and
     workspaces of one step at (batch_size, bucket) stay reserved for the graph's lifetime, so

@@ -47,6 +47,24 @@ __device__ __forceinline__ void ctc_row_stat(const float* xr, int C, int lane, f
   }
 }
 
+// The prior of one labelling h of len tokens under the bigram gloss model (include/scatten.h,
+// sca_nbest_rescore), by one wave: lm_weight * lm(h) + length_bonus * len.  lm: NULL (lm(h) = 0)
+// or the dense (C, C) table; class 0 on either side is the sentence boundary, so lm(empty) =
+// lm[0, 0].  The lanes stride over the len + 1 independent gathers, a butterfly sums them in a
+// fixed order; every lane returns the value.  One body under the rescorer and the MWER loss.
+__device__ __forceinline__ float ctc_bigram_prior(const float* __restrict__ lm, int C, const int* __restrict__ h,
+                                                  int len, int lane, float lm_weight, float length_bonus) {
+  float acc = 0.0f;
+  if (lm) {
+    for (int i = lane; i <= len; i += 64) {
+      const int p = i == 0 ? 0 : clampi(h[i - 1], 0, C - 1), c = i == len ? 0 : clampi(h[i], 0, C - 1);
+      acc += lm[(long)p * C + c];
+    }
+    acc = wave_sum(acc);
+  }
+  return lm_weight * acc + length_bonus * (float)len;
+}
+
 // heads.hip: ctc_row_stat over the rows of one tensor, rowstat (rows, 2); the CTC loss, the MWER
 // loss and a decoder call over one tensor use it
 __attribute__((visibility("hidden"))) void sca_ctc_rowstat_launch(const float* x, float* rowstat, long rows, int C,

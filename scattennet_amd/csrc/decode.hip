@@ -785,15 +785,7 @@ __global__ __launch_bounds__(64) void nbest_rescore_kernel(const int* __restrict
   for (int n = 0; n < cnt; ++n) {
     const int len = clampi(out_len[s * N + n], 0, T);
     const int* h = tokens + (s * N + n) * T;
-    float acc = 0.0f;
-    if (lm) {
-      for (int i = lane; i <= len; i += 64) {  // class 0 on either side is the sentence boundary
-        const int p = i == 0 ? 0 : clampi(h[i - 1], 0, C - 1), c = i == len ? 0 : clampi(h[i], 0, C - 1);
-        acc += lm[(long)p * C + c];
-      }
-      acc = wave_sum(acc);
-    }
-    const float t = score[s * N + n] + (lm_weight * acc + length_bonus * (float)len);
+    const float t = score[s * N + n] + ctc_bigram_prior(lm, C, h, len, lane, lm_weight, length_bonus);
     mine = lane == n ? t : mine;
   }
   const bool valid = lane < cnt;

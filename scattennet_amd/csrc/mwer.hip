@@ -3,11 +3,16 @@
 // list, with exact CTC likelihoods, and its gradient with respect to the logits.  The reference
 // has none of this.
 //   fwd: row statistics (the pass the CTC loss and the decoders share) -> one launch with alpha
-//        and beta of every (clip, entry), one wave64 each, beside its error count, the alignment
-//        of wer_pair.h -> posterior, centred errors, gradient weights, risk, loss
+//        and beta of every (clip, slot), one wave64 each, beside its error count, the alignment
+//        of wer_pair.h, and its prior under the gloss model -> posterior, centred errors,
+//        gradient weights, risk, loss
 //   bwd: one workgroup per (clip, frame): sum_n w_n occ_n(t, .) in one LDS row, n ascending,
-//        then the clamp gate and the log-softmax backward: ONE dense pass for the N hypotheses
-// No float atomics; every sum over entries, states and clips runs in a fixed order, so the
+//        then the clamp gate and the log-softmax backward: ONE dense pass for the M slots
+// One set of kernels behind sca_mwer_fwd / bwd and sca_mwer_heads_fwd / bwd.  A "clip" of the
+// grids, the workspace and the outputs is the (head, clip) pair p = g B + b (CtcHeads, ctc.h);
+// a slot is an entry of the list or, with_ref, slot N: the clip's reference, read where it lies
+// (no copy of the list).  The old entry points are G = 1 without the reference and the prior.
+// No float atomics; every sum over slots, states and clips runs in a fixed order, so the
 // results are deterministic and a replayed capture is bitwise the eager call.
 #include "ctc.h"
 #include "wer_pair.h"
@@ -18,55 +23,101 @@ constexpr int MW_MAX_L = 2 * SCA_WER_MAX_LEN + 1;  // states of the longest hypo
 constexpr int MW_K = (MW_MAX_L + 63) / 64;         // states per lane of the recursion's wave
 constexpr int MW_PAD = 2;                          // -inf cells either side of an LDS state row
 constexpr int MW_GRAD_THREADS = 256;
-constexpr int MW_CLIPS_ONE_GROUP = 64;  // batches up to this size: per-clip statistics and the loss in one workgroup
+constexpr int MW_CLIPS_ONE_GROUP = 64;  // up to this many (head, clip) pairs: per-clip statistics and the losses in one workgroup
 
+// B clips per head, P = G B pairs; N entries and M = N + with_ref slots per pair; Hm = the longest
+// labelling of a slot (H, or max(H, R) with the reference); prior: lmterm is computed and added
 struct MwDims {
-  int B, N, T, C, H, R;
+  int B, N, T, C, H, R, P, M, Hm, with_ref, prior;
 };
 
-// workspace layout (floats): rowstat[B T 2] | alpha[B N T Lm] | beta[B N T Lm] | ll[B N] |
-// w[B N] | lossb[B], Lm = 2 H + 1
+MwDims mw_dims(int G, int B, int N, int T, int C, int H, int R, int with_ref, int prior) {
+  return MwDims{B, N, T, C, H, R, G * B, N + (with_ref ? 1 : 0), with_ref && R > H ? R : H, with_ref ? 1 : 0, prior};
+}
+
+// The gloss model of the prior (sca_nbest_rescore's arguments)
+struct MwPrior {
+  const float* lm;
+  float weight, bonus;
+};
+
+// d loss / d logits of the G heads, by value in the kernel arguments like CtcHeads
+struct MwGrads {
+  float* dx[SCA_EVAL_MAX_HEADS];
+};
+
+__device__ __forceinline__ float* mw_grad_head(const MwGrads& h, int g) {
+  float* p = h.dx[0];
+#pragma unroll
+  for (int i = 1; i < SCA_EVAL_MAX_HEADS; ++i) p = g == i ? h.dx[i] : p;
+  return p;
+}
+
+// workspace layout (floats): rowstat[P T 2] | alpha[P M T Lm] | beta[P M T Lm] | ll[P M] |
+// w[P M] | lossb[P] | lmterm[P M] (with the prior only), Lm = 2 Hm + 1
 struct MwWs {
-  float *rowstat, *alpha, *beta, *ll, *w, *lossb;
+  float *rowstat, *alpha, *beta, *ll, *w, *lossb, *lmterm;
   long Lm;
   __host__ __device__ MwWs(float* ws, MwDims d) {
-    const long BT = (long)d.B * d.T, BN = (long)d.B * d.N;
-    Lm = 2L * d.H + 1;
+    const long PT = (long)d.P * d.T, PM = (long)d.P * d.M;
+    Lm = 2L * d.Hm + 1;
     rowstat = ws;
-    alpha = rowstat + 2 * BT;
-    beta = alpha + BN * d.T * Lm;
-    ll = beta + BN * d.T * Lm;
-    w = ll + BN;
-    lossb = w + BN;
+    alpha = rowstat + 2 * PT;
+    beta = alpha + PM * d.T * Lm;
+    ll = beta + PM * d.T * Lm;
+    w = ll + PM;
+    lossb = w + PM;
+    lmterm = lossb + d.P;
   }
 };
 
-// One wave64 per (entry, clip, direction) of mwer_entry_kernel: z = 0 the alpha recursion over
+long mw_ws_floats(long P, long M, long T, long Hm, bool prior) {
+  return 2 * P * T + 2 * P * M * T * (2 * Hm + 1) + 2 * P * M + P + (prior ? P * M : 0);
+}
+
+// The labelling of slot n of pair p: entry n of the list, or (n = N) the reference of clip b
+struct MwSlot {
+  const int* tok;
+  int len;
+};
+
+__device__ __forceinline__ MwSlot mw_slot(const int* __restrict__ tokens, const int* __restrict__ out_len,
+                                          const int* __restrict__ ref, const int* __restrict__ ref_len, MwDims d,
+                                          int p, int b, int n) {
+  if (n == d.N) return MwSlot{ref + (long)b * d.R, clampi(ref_len[b], 0, d.R)};
+  const long el = (long)p * d.N + n;
+  return MwSlot{tokens + el * d.H, clampi(out_len[el], 0, d.H)};
+}
+
+// One wave64 per (slot, pair, direction) of mwer_entry_kernel: z = 0 the alpha recursion over
 // the frames [0, in_len), z = 1 the beta one.  Lane l holds states l, l + 64, ..; a frame's row
 // goes through a wave-private LDS row for the neighbours s -+ 1, s -+ 2, so a frame costs no
 // workgroup barrier.  The emissions lp[t, label(s)] do not depend on the recursion: the next
 // frame's gathers are issued before this frame's row is computed.
-__device__ __forceinline__ void mwer_alpha_beta(const float* __restrict__ x, const int* __restrict__ in_len,
+__device__ __forceinline__ void mwer_alpha_beta(const CtcHeads& heads, const int* __restrict__ in_len,
                                                 const int* __restrict__ tokens, const int* __restrict__ out_len,
-                                                const int* __restrict__ count, MwDims d, float* ws) {
+                                                const int* __restrict__ count, const int* __restrict__ ref,
+                                                const int* __restrict__ ref_len, MwDims d, float* ws) {
   __shared__ float buf[2][MW_MAX_L + 2 * MW_PAD];
   MwWs w(ws, d);
-  const int n = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
+  const int n = blockIdx.x, p = blockIdx.y, lane = threadIdx.x;
+  const int g = p / d.B, b = p - g * d.B;
   const bool beta_pass = blockIdx.z == 1;
-  const long e = (long)b * d.N + n;
-  const int cnt = clampi(count[b], 0, d.N);
+  const long e = (long)p * d.M + n;
+  const int cnt = clampi(count[p], 0, d.N);
   const int Tb = clampi(in_len[b], 0, d.T);
-  if (n >= cnt) {  // uniform: entries past count are ignored
+  if (n < d.N && n >= cnt) {  // uniform: entries past count are ignored
     if (!beta_pass && lane == 0) w.ll[e] = NEG_INF;
     return;
   }
-  const int len = clampi(out_len[e], 0, d.H);
+  const MwSlot slot = mw_slot(tokens, out_len, ref, ref_len, d, p, b, n);
+  const int len = slot.len;
   if (Tb == 0) {  // no frame: only the empty hypothesis fits, with likelihood 1
     if (!beta_pass && lane == 0) w.ll[e] = len == 0 ? 0.0f : NEG_INF;
     return;
   }
   const int L = 2 * len + 1;
-  const int* tok = tokens + e * d.H;
+  const int* tok = slot.tok;
   int lab[MW_K];
   bool skip[MW_K];  // the transition from s - 2 (alpha) / s + 2 (beta) exists
 #pragma unroll
@@ -82,8 +133,8 @@ __device__ __forceinline__ void mwer_alpha_beta(const float* __restrict__ x, con
       if (beta_pass && j + 1 < len) skip[k] = lab[k] != 0 && clampi(tok[j + 1], 0, d.C - 1) != lab[k];
     }
   }
-  const float* xb = x + (long)b * d.T * d.C;
-  const float* rs = w.rowstat + 2L * b * d.T;
+  const float* xb = ctc_head(heads, g) + (long)b * d.T * d.C;
+  const float* rs = w.rowstat + 2L * p * d.T;
   float* out = (beta_pass ? w.beta : w.alpha) + e * d.T * w.Lm;
   auto emit = [&](int t, int k) {
     return ctc_lp(ctc_lp_raw(xb[(long)t * d.C + lab[k]], rs[2 * t], rs[2 * t + 1]));
@@ -139,45 +190,62 @@ __device__ __forceinline__ void mwer_alpha_beta(const float* __restrict__ x, con
   }
 }
 
-// z = 2 of mwer_entry_kernel, one workgroup per (entry, clip): errors[b, n] = num_del + num_ins +
-// num_sub of reference b against entry n; 0 for the entries past count
+// z = 2 of mwer_entry_kernel, one workgroup per (slot, pair): errors[p, n] = num_del + num_ins +
+// num_sub of reference b against entry n; 0 for the entries past count and for the reference
+// slot, which needs no alignment.  With the prior, wave 1 computes the slot's lmterm once it has
+// left wer_pair's last barrier, beside thread 0's serial back-trace.
 __device__ __forceinline__ void mwer_pair(const int* __restrict__ tokens, const int* __restrict__ out_len,
                                           const int* __restrict__ count, const int* __restrict__ ref,
-                                          const int* __restrict__ ref_len, MwDims d, int* __restrict__ errors) {
+                                          const int* __restrict__ ref_len, MwDims d, MwPrior prior, float* ws,
+                                          int* __restrict__ errors) {
   __shared__ int c4[4];
-  const int n = blockIdx.x, b = blockIdx.y;
-  const long e = (long)b * d.N + n;
-  if (n >= clampi(count[b], 0, d.N)) {  // uniform over the workgroup
-    if (threadIdx.x == 0) errors[e] = 0;
-    return;
+  const int n = blockIdx.x, p = blockIdx.y;
+  const int b = p % d.B;
+  const long e = (long)p * d.M + n;
+  const bool listed = n < clampi(count[p], 0, d.N);  // uniform over the workgroup
+  if (listed) {
+    const long el = (long)p * d.N + n;
+    const int R = clampi(ref_len[b], 0, d.R), H = clampi(out_len[el], 0, d.H);
+    wer_pair(ref + (long)b * d.R, R, tokens + el * d.H, H, c4);
+    if (threadIdx.x == 0) errors[e] = c4[0] + c4[1] + c4[2];  // thread 0 wrote c4
+  } else if (threadIdx.x == 0) {
+    errors[e] = 0;
   }
-  const int R = clampi(ref_len[b], 0, d.R), H = clampi(out_len[e], 0, d.H);
-  wer_pair(ref + (long)b * d.R, R, tokens + e * d.H, H, c4);
-  if (threadIdx.x == 0) errors[e] = c4[0] + c4[1] + c4[2];  // thread 0 wrote c4
+  if (d.prior && threadIdx.x >= 64) {
+    const int lane = threadIdx.x - 64;
+    float v = 0.0f;
+    if (listed || n == d.N) {
+      const MwSlot slot = mw_slot(tokens, out_len, ref, ref_len, d, p, b, n);
+      v = ctc_bigram_prior(prior.lm, d.C, slot.tok, slot.len, lane, prior.weight, prior.bonus);
+    }
+    if (lane == 0) MwWs(ws, d).lmterm[e] = v;
+  }
 }
 
-// grid (N, B, 3), 128 threads: the three independent jobs of one (entry, clip) in ONE launch, so
-// that the alignment (an anti-diagonal sweep and a serial back-trace) runs beside the two
-// recursions instead of after them.  z = 0, 1: wave 0 runs the recursion, wave 1 leaves at once
-// (the recursion uses no workgroup barrier); z = 2: both waves run wer_pair.
-__global__ __launch_bounds__(128) void mwer_entry_kernel(const float* __restrict__ x, const int* __restrict__ in_len,
+// grid (M, P, 3), 128 threads: the three independent jobs of one (slot, pair) in ONE launch, so
+// that the alignment (an anti-diagonal sweep and a serial back-trace) and the prior run beside
+// the two recursions instead of after them.  z = 0, 1: wave 0 runs the recursion, wave 1 leaves
+// at once (the recursion uses no workgroup barrier); z = 2: both waves run wer_pair.
+__global__ __launch_bounds__(128) void mwer_entry_kernel(CtcHeads heads, const int* __restrict__ in_len,
                                                          const int* __restrict__ tokens,
                                                          const int* __restrict__ out_len,
                                                          const int* __restrict__ count, const int* __restrict__ ref,
-                                                         const int* __restrict__ ref_len, MwDims d, float* ws,
-                                                         int* __restrict__ errors) {
+                                                         const int* __restrict__ ref_len, MwDims d, MwPrior prior,
+                                                         float* ws, int* __restrict__ errors) {
   if (blockIdx.z == 2) {
-    mwer_pair(tokens, out_len, count, ref, ref_len, d, errors);
+    mwer_pair(tokens, out_len, count, ref, ref_len, d, prior, ws, errors);
   } else if (threadIdx.x < 64) {
-    mwer_alpha_beta(x, in_len, tokens, out_len, count, d, ws);
+    mwer_alpha_beta(heads, in_len, tokens, out_len, count, ref, ref_len, d, ws);
   }
 }
 
-// Workgroup g of four waves takes clips 4 g + wave, then strides by the grid, lane n holding
-// entry n: the posterior over the valid entries, the centred errors, the gradient weights w_n
-// (without dloss), risk and loss_b.  A NaN likelihood counts as valid, so that it reaches the
-// loss instead of dropping its entry.  With one workgroup (B <= MW_CLIPS_ONE_GROUP) wave 0 then
-// sums loss_b in index order; a larger batch gets mwer_loss_sum_kernel as one more launch.
+// Workgroup i of four waves takes pairs 4 i + wave, then strides by the grid, lane n holding
+// slot n (M <= 33): the posterior over the valid slots, the centred errors, the gradient weights
+// w_n (without dloss), risk and loss_b.  A NaN likelihood counts as valid, so that it reaches
+// the loss instead of dropping its entry.  The reference slot is valid iff it fits and no entry
+// of the list has error count 0 (the reference is not in the list already).  With one workgroup
+// (P <= MW_CLIPS_ONE_GROUP) wave j then sums loss_b of heads j, j + 4 in index order; a larger
+// batch gets mwer_loss_sum_kernel as one more launch.
 __device__ __forceinline__ void mwer_loss_sum(const float* lossb, int B, int lane, float* loss) {
   float acc = 0.0f;
   for (int b = lane; b < B; b += 64) acc += lossb[b];
@@ -189,70 +257,88 @@ __global__ __launch_bounds__(256) void mwer_clip_kernel(const int* __restrict__ 
                                                         const int* __restrict__ errors, MwDims d,
                                                         float posterior_scale, float* ws,
                                                         float* __restrict__ loglik, float* __restrict__ posterior,
-                                                        float* __restrict__ risk, float* __restrict__ loss) {
+                                                        int* __restrict__ ref_valid, float* __restrict__ risk,
+                                                        float* __restrict__ loss) {
   MwWs w(ws, d);
   const int lane = threadIdx.x & 63;
-  for (int b = blockIdx.x * 4 + (threadIdx.x >> 6); b < d.B; b += 4 * gridDim.x) {
-    const int cnt = clampi(count[b], 0, d.N);
-    const long e = (long)b * d.N + lane;
-    const float ll = lane < cnt ? w.ll[e] : NEG_INF;
-    const bool valid = ll != NEG_INF;
-    const float z = valid ? posterior_scale * ll : NEG_INF;
+  for (int p = blockIdx.x * 4 + (threadIdx.x >> 6); p < d.P; p += 4 * gridDim.x) {
+    const int cnt = clampi(count[p], 0, d.N);
+    const long e = (long)p * d.M + lane;
+    const bool is_ref = d.with_ref && lane == d.N;
+    const bool slot = lane < cnt || is_ref;
+    const float ll = slot ? w.ll[e] : NEG_INF;
+    const int en = lane < cnt ? errors[e] : 0;
+    bool valid = ll != NEG_INF;
+    int rv = 0;
+    if (d.with_ref) {  // uniform
+      const bool dup = __ballot(lane < cnt && en == 0) != 0ull;
+      valid = valid && !(is_ref && dup);
+      rv = __ballot(is_ref && valid) != 0ull;
+    }
+    if (ref_valid && lane == 0) ref_valid[p] = rv;
+    const float tot = d.prior && slot ? ll + w.lmterm[e] : ll;
+    const float z = valid ? posterior_scale * tot : NEG_INF;
     const float m = wave_max(z);
     const float ev = valid ? expf(z - m) : 0.0f;
     const float sum = wave_sum(ev);
     const float nv = wave_sum(valid ? 1.0f : 0.0f);
-    const float err = valid ? (float)errors[e] : 0.0f;
+    const float err = valid ? (float)en : 0.0f;
     const float ebar = nv > 0.0f ? wave_sum(err) / nv : 0.0f;
     const float post = valid ? ev / sum : 0.0f;
     const float dn = valid ? err - ebar : 0.0f;
     const float rk = wave_sum(post * err);
     const float lb = wave_sum(post * dn);
-    if (lane < d.N) {
+    if (lane < d.M) {
       loglik[e] = ll;
       posterior[e] = post;
       w.w[e] = nv > 1.0f ? posterior_scale * post * (dn - lb) / (float)d.B : 0.0f;
     }
     if (lane == 0) {
-      risk[b] = rk;
-      w.lossb[b] = lb;
+      risk[p] = rk;
+      w.lossb[p] = lb;
     }
   }
   if (gridDim.x > 1) return;  // uniform
   __syncthreads();
-  if (threadIdx.x < 64) mwer_loss_sum(w.lossb, d.B, lane, loss);
+  for (int g = threadIdx.x >> 6; g * d.B < d.P; g += 4) mwer_loss_sum(w.lossb + (long)g * d.B, d.B, lane, loss + g);
 }
 
+// grid (G): the loss of head g
 __global__ __launch_bounds__(64) void mwer_loss_sum_kernel(MwDims d, const float* ws, float* __restrict__ loss) {
   MwWs w(const_cast<float*>(ws), d);
-  mwer_loss_sum(w.lossb, d.B, threadIdx.x, loss);
+  mwer_loss_sum(w.lossb + (long)blockIdx.x * d.B, d.B, threadIdx.x, loss + blockIdx.x);
 }
 
-// grid (T, B), one workgroup per logits row: g[c] = sum_n dloss w_n occ_n(t, c), n ascending;
-// every class of one entry is added by exactly one thread (the blank by thread 0, a label by
-// the thread of its first occurrence, which sums the later ones in order).  Then the CTC
-// loss's row tail (ctc_grad_row_tail, ctc.h): the clamp gate, the row sum, the log-softmax backward.
-__global__ __launch_bounds__(MW_GRAD_THREADS) void mwer_grad_kernel(const float* __restrict__ x,
-                                                                    const int* __restrict__ in_len,
+// grid (T, P), one workgroup per logits row: g[c] = sum_n dloss w_n occ_n(t, c), n ascending, the
+// reference slot last; every class of one slot is added by exactly one thread (the blank by
+// thread 0, a label by the thread of its first occurrence, which sums the later ones in order).
+// Then the CTC loss's row tail (ctc_grad_row_tail, ctc.h): the clamp gate, the row sum, the
+// log-softmax backward.  dloss holds one float per head.
+__global__ __launch_bounds__(MW_GRAD_THREADS) void mwer_grad_kernel(CtcHeads heads, const int* __restrict__ in_len,
                                                                     const int* __restrict__ tokens,
                                                                     const int* __restrict__ out_len,
-                                                                    const int* __restrict__ count, MwDims d,
+                                                                    const int* __restrict__ count,
+                                                                    const int* __restrict__ ref,
+                                                                    const int* __restrict__ ref_len, MwDims d,
                                                                     const float* ws, const float* __restrict__ dloss,
-                                                                    float* __restrict__ dx) {
+                                                                    MwGrads grads) {
   __shared__ float ab[MW_MAX_L];
   __shared__ int tok_s[SCA_WER_MAX_LEN];
   __shared__ float g_s[SCA_CTC_MAX_C];
   __shared__ float red[4];
   MwWs w(const_cast<float*>(ws), d);
-  const int b = blockIdx.y, t = blockIdx.x, tid = threadIdx.x;
-  const long row = (long)b * d.T + t;
-  const float* xr = x + row * d.C;
-  float* dr = dx + row * d.C;
-  const int cnt = clampi(count[b], 0, d.N);
+  const int p = blockIdx.y, t = blockIdx.x, tid = threadIdx.x;
+  const int g = p / d.B, b = p - g * d.B;
+  const long hrow = (long)b * d.T + t;  // the row within head g's tensors
+  const long row = (long)p * d.T + t;
+  const float* xr = ctc_head(heads, g) + hrow * d.C;
+  float* dr = mw_grad_head(grads, g) + hrow * d.C;
+  const int cnt = clampi(count[p], 0, d.N);
   const int Tb = clampi(in_len[b], 0, d.T);
-  const float gl = dloss[0];
+  const float gl = dloss[g];
+  const int slots = cnt + d.with_ref;  // the list's entries, then the reference slot
   bool any = false;
-  for (int n = 0; n < cnt; ++n) any |= w.w[(long)b * d.N + n] * gl != 0.0f;
+  for (int k = 0; k < slots; ++k) any |= w.w[(long)p * d.M + (k < cnt ? k : d.N)] * gl != 0.0f;
   if (t >= Tb || !any) {  // uniform: frames past the input length, clips without a gradient
     for (int c = tid; c < d.C; c += MW_GRAD_THREADS) dr[c] = 0.0f;
     return;
@@ -260,17 +346,19 @@ __global__ __launch_bounds__(MW_GRAD_THREADS) void mwer_grad_kernel(const float*
   const float m = w.rowstat[2 * row], ls = w.rowstat[2 * row + 1];
   for (int c = tid; c < d.C; c += MW_GRAD_THREADS) g_s[c] = 0.0f;
   const float lp0 = ctc_lp(ctc_lp_raw(xr[0], m, ls));
-  for (int n = 0; n < cnt; ++n) {
-    const long e = (long)b * d.N + n;
+  for (int k = 0; k < slots; ++k) {
+    const int n = k < cnt ? k : d.N;
+    const long e = (long)p * d.M + n;
     const float wn = w.w[e] * gl;
     if (wn == 0.0f) continue;  // uniform
-    const int len = clampi(out_len[e], 0, d.H), L = 2 * len + 1;
+    const MwSlot slot = mw_slot(tokens, out_len, ref, ref_len, d, p, b, n);
+    const int len = slot.len, L = 2 * len + 1;
     const float ll = w.ll[e];
     const float* al = w.alpha + (e * d.T + t) * w.Lm;
     const float* be = w.beta + (e * d.T + t) * w.Lm;
-    __syncthreads();  // the previous entry's readers of ab, tok_s are done; g_s is zeroed
+    __syncthreads();  // the previous slot's readers of ab, tok_s are done; g_s is zeroed
     for (int s = tid; s < L; s += MW_GRAD_THREADS) ab[s] = (al[s] + be[s]) - ll;
-    for (int j = tid; j < len; j += MW_GRAD_THREADS) tok_s[j] = clampi(tokens[e * d.H + j], 0, d.C - 1);
+    for (int j = tid; j < len; j += MW_GRAD_THREADS) tok_s[j] = clampi(slot.tok[j], 0, d.C - 1);
     __syncthreads();
     if (tid < 64) {  // wave 0: the blank (every even state, plus odd states whose label is 0)
       float acc = 0.0f;
@@ -282,12 +370,12 @@ __global__ __launch_bounds__(MW_GRAD_THREADS) void mwer_grad_kernel(const float*
       for (int j = tid - 64; j < len; j += MW_GRAD_THREADS - 64) {
         const int c = tok_s[j];
         bool first = c != 0;
-        for (int k = 0; k < j && first; ++k) first = tok_s[k] != c;
+        for (int i = 0; i < j && first; ++i) first = tok_s[i] != c;
         if (!first) continue;
         const float lpc = ctc_lp(ctc_lp_raw(xr[c], m, ls));
         float acc = 0.0f;
-        for (int k = j; k < len; ++k)
-          if (tok_s[k] == c) acc += __expf(ab[2 * k + 1] - lpc);
+        for (int i = j; i < len; ++i)
+          if (tok_s[i] == c) acc += __expf(ab[2 * i + 1] - lpc);
         g_s[c] += wn * acc;
       }
     }
@@ -296,51 +384,118 @@ __global__ __launch_bounds__(MW_GRAD_THREADS) void mwer_grad_kernel(const float*
   ctc_grad_row_tail<MW_GRAD_THREADS>(xr, dr, d.C, m, ls, g_s, red, tid, [&](int c, float) { return g_s[c]; });
 }
 
-bool mwer_dims_ok(int B, int N, int T, int C, int H, int R) {
-  return B >= 1 && B <= 65535 && T >= 1 && C >= 1 && C <= SCA_CTC_MAX_C && N >= 1 && N <= SCA_CTC_MAX_BEAM &&
-         H >= 1 && H <= SCA_WER_MAX_LEN && R >= 1 && R <= SCA_WER_MAX_LEN;
+bool mwer_dims_ok(int G, int B, int N, int T, int C, int H, int R) {
+  return G >= 1 && G <= SCA_EVAL_MAX_HEADS && B >= 1 && (long)G * B <= 65535 && T >= 1 && C >= 1 &&
+         C <= SCA_CTC_MAX_C && N >= 1 && N <= SCA_CTC_MAX_BEAM && H >= 1 && H <= SCA_WER_MAX_LEN && R >= 1 &&
+         R <= SCA_WER_MAX_LEN;
 }
 
 #define MWER_LIMITS "bad arguments (1 <= B <= 65535, T >= 1, C <= 8192, 1 <= N <= 32, 1 <= H, R <= 128)"
+#define MWER_HEADS_LIMITS \
+  "bad arguments (1 <= G <= 8, B >= 1, G B <= 65535, T >= 1, C <= 8192, 1 <= N <= 32, 1 <= H, R <= 128, finite weights)"
+
+// The forward of every entry point, after validation: three launches, four above
+// MW_CLIPS_ONE_GROUP pairs.  ref_valid may be NULL without the reference.
+void mwer_fwd_launch(const CtcHeads& heads, const sca_decode_heads* table, int G, const int* in_len, const int* tokens,
+                     const int* out_len, const int* count, const int* ref, const int* ref_len, MwDims d,
+                     MwPrior prior, float posterior_scale, float* loglik, float* posterior, int* errors,
+                     int* ref_valid, float* risk, float* loss, float* ws, hipStream_t st) {
+  if (G == 1) {
+    sca_ctc_rowstat_launch(heads.x[0], ws, (long)d.B * d.T, d.C, st);
+  } else {
+    sca_ctc_rowstat_heads_launch(table, G, ws, (long)d.B * d.T, d.C, st);
+  }
+  hipLaunchKernelGGL(mwer_entry_kernel, dim3(d.M, d.P, 3), dim3(128), 0, st, heads, in_len, tokens, out_len, count,
+                     ref, ref_len, d, prior, ws, errors);
+  const int groups = d.P <= MW_CLIPS_ONE_GROUP ? 1 : (d.P + 3) / 4;
+  hipLaunchKernelGGL(mwer_clip_kernel, dim3(groups), dim3(256), 0, st, count, errors, d, posterior_scale, ws, loglik,
+                     posterior, ref_valid, risk, loss);
+  if (groups > 1) hipLaunchKernelGGL(mwer_loss_sum_kernel, dim3(G), dim3(64), 0, st, d, ws, loss);
+}
 
 }  // namespace
 
 extern "C" long sca_mwer_workspace_floats(int B, int N, int T, int H) {
   if (B < 1 || N < 1 || T < 1 || H < 1) return 0;
-  const long BT = (long)B * T, BN = (long)B * N;
-  return 2 * BT + 2 * BN * T * (2L * H + 1) + 2 * BN + B;
+  return mw_ws_floats(B, N, T, H, false);
+}
+
+extern "C" long sca_mwer_heads_workspace_floats(int G, int B, int N, int T, int H, int R, int with_ref) {
+  if (G < 1 || B < 1 || N < 1 || T < 1 || H < 1 || R < 1) return 0;
+  return mw_ws_floats((long)G * B, N + (with_ref ? 1 : 0), T, with_ref && R > H ? R : H, true);
 }
 
 extern "C" int sca_mwer_fwd(const float* logits, const int* in_len, const int* tokens, const int* out_len,
                             const int* count, const int* ref, const int* ref_len, int B, int N, int T, int C, int H,
                             int R, float posterior_scale, float* loglik, float* posterior, int* errors, float* risk,
                             float* loss, float* ws, void* stream) {
-  if (!mwer_dims_ok(B, N, T, C, H, R) || !logits || !in_len || !tokens || !out_len || !count || !ref || !ref_len ||
+  if (!mwer_dims_ok(1, B, N, T, C, H, R) || !logits || !in_len || !tokens || !out_len || !count || !ref || !ref_len ||
       !(posterior_scale == posterior_scale) || !loglik || !posterior || !errors || !risk || !loss || !ws) {
     sca_set_error("sca_mwer_fwd: " MWER_LIMITS);
     return SCA_ERR_ARG;
   }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const MwDims d{B, N, T, C, H, R};
-  sca_ctc_rowstat_launch(logits, ws, (long)B * T, C, st);
-  hipLaunchKernelGGL(mwer_entry_kernel, dim3(N, B, 3), dim3(128), 0, st, logits, in_len, tokens, out_len, count, ref,
-                     ref_len, d, ws, errors);
-  const int groups = B <= MW_CLIPS_ONE_GROUP ? 1 : (B + 3) / 4;
-  hipLaunchKernelGGL(mwer_clip_kernel, dim3(groups), dim3(256), 0, st, count, errors, d, posterior_scale, ws, loglik,
-                     posterior, risk, loss);
-  if (groups > 1) hipLaunchKernelGGL(mwer_loss_sum_kernel, dim3(1), dim3(64), 0, st, d, ws, loss);
+  sca_decode_heads table = {};
+  table.logits[0] = logits;
+  mwer_fwd_launch(ctc_heads_of(&table, 1), &table, 1, in_len, tokens, out_len, count, ref, ref_len,
+                  mw_dims(1, B, N, T, C, H, R, 0, 0), MwPrior{nullptr, 0.0f, 0.0f}, posterior_scale, loglik, posterior,
+                  errors, nullptr, risk, loss, ws, reinterpret_cast<hipStream_t>(stream));
   return sca_launch_status("sca_mwer_fwd");
 }
 
 extern "C" int sca_mwer_bwd(const float* logits, const int* in_len, const int* tokens, const int* out_len,
                             const int* count, int B, int N, int T, int C, int H, const float* dloss, const float* ws,
                             float* dlogits, void* stream) {
-  if (!mwer_dims_ok(B, N, T, C, H, 1) || !logits || !in_len || !tokens || !out_len || !count || !dloss || !ws ||
+  if (!mwer_dims_ok(1, B, N, T, C, H, 1) || !logits || !in_len || !tokens || !out_len || !count || !dloss || !ws ||
       !dlogits) {
     sca_set_error("sca_mwer_bwd: " MWER_LIMITS);
     return SCA_ERR_ARG;
   }
+  sca_decode_heads table = {};
+  table.logits[0] = logits;
+  MwGrads grads = {};
+  grads.dx[0] = dlogits;
   hipLaunchKernelGGL(mwer_grad_kernel, dim3(T, B), dim3(MW_GRAD_THREADS), 0, reinterpret_cast<hipStream_t>(stream),
-                     logits, in_len, tokens, out_len, count, MwDims{B, N, T, C, H, 1}, ws, dloss, dlogits);
+                     ctc_heads_of(&table, 1), in_len, tokens, out_len, count, nullptr, nullptr,
+                     mw_dims(1, B, N, T, C, H, 1, 0, 0), ws, dloss, grads);
   return sca_launch_status("sca_mwer_bwd");
+}
+
+extern "C" int sca_mwer_heads_fwd(const sca_decode_heads* heads, int G, const int* in_len, const int* tokens,
+                                  const int* out_len, const int* count, const int* ref, const int* ref_len, int B,
+                                  int N, int T, int C, int H, int R, int with_ref, const float* lm, float lm_weight,
+                                  float length_bonus, float posterior_scale, float* loglik, float* posterior,
+                                  int* errors, int* ref_valid, float* risk, float* loss, float* ws, void* stream) {
+  bool ok = heads && mwer_dims_ok(G, B, N, T, C, H, R) && in_len && tokens && out_len && count && ref && ref_len &&
+            lm_weight - lm_weight == 0.0f && length_bonus - length_bonus == 0.0f &&
+            posterior_scale == posterior_scale && loglik && posterior && errors && ref_valid && risk && loss && ws;
+  for (int g = 0; ok && g < G; ++g) ok = heads->logits[g] != nullptr;
+  if (!ok) {
+    sca_set_error("sca_mwer_heads_fwd: " MWER_HEADS_LIMITS);
+    return SCA_ERR_ARG;
+  }
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const MwDims d = mw_dims(G, B, N, T, C, H, R, with_ref, 1);
+  mwer_fwd_launch(ctc_heads_of(heads, G), heads, G, in_len, tokens, out_len, count, ref, ref_len, d,
+                  MwPrior{lm, lm_weight, length_bonus}, posterior_scale, loglik, posterior, errors, ref_valid, risk,
+                  loss, ws, st);
+  return sca_launch_status("sca_mwer_heads_fwd");
+}
+
+extern "C" int sca_mwer_heads_bwd(const sca_decode_heads* heads, int G, const int* in_len, const int* tokens,
+                                  const int* out_len, const int* count, const int* ref, const int* ref_len, int B,
+                                  int N, int T, int C, int H, int R, int with_ref, const float* dloss, const float* ws,
+                                  const sca_mwer_grads* dlogits, void* stream) {
+  bool ok = heads && dlogits && mwer_dims_ok(G, B, N, T, C, H, R) && in_len && tokens && out_len && count && ref &&
+            ref_len && dloss && ws;
+  for (int g = 0; ok && g < G; ++g) ok = heads->logits[g] != nullptr && dlogits->dlogits[g] != nullptr;
+  if (!ok) {
+    sca_set_error("sca_mwer_heads_bwd: " MWER_HEADS_LIMITS);
+    return SCA_ERR_ARG;
+  }
+  MwGrads grads = {};
+  for (int g = 0; g < SCA_EVAL_MAX_HEADS; ++g) grads.dx[g] = dlogits->dlogits[g < G ? g : 0];
+  const MwDims d = mw_dims(G, B, N, T, C, H, R, with_ref, 1);
+  hipLaunchKernelGGL(mwer_grad_kernel, dim3(T, d.P), dim3(MW_GRAD_THREADS), 0, reinterpret_cast<hipStream_t>(stream),
+                     ctc_heads_of(heads, G), in_len, tokens, out_len, count, ref, ref_len, d, ws, dloss, grads);
+  return sca_launch_status("sca_mwer_heads_bwd");
 }

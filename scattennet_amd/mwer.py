@@ -5,22 +5,29 @@ likelihoods, error counts from the project's WER alignment — as a differentiab
 reference has none of this.
 
 * `MWERLossOp` — the autograd Function over fp32 logits (B, T, C) and int32 device tensors.
+* `MWERHeadsLossOp` — the same over the logits of G heads in one call (`sca_mwer_heads_fwd` /
+  `sca_mwer_heads_bwd`), optionally with each clip's reference as one more entry of its list and
+  with the bigram gloss model's prior inside the posterior.
 * `mwer_loss` — the validated entry point: decodes the detached logits into an uncollapsed
-  n-best list (`ctc_decode_nbest_device`) unless the caller hands one over.
+  n-best list (`ctc_decode_nbest_device`, or the fused search) unless the caller hands one over.
 * `MWER` — the validated spec that `train_step(..., mwer=)` and `BucketedTrainStep(..., mwer=)`
   take; `mwer_guard` is the scalar they hand to `FusedAdam.step`.
 
 No call reads the device or allocates outside the caching allocator: everything is usable under
 `torch.cuda.graph` capture.
 """
+import ctypes
+
 import torch
 from torch.autograd import Function
 
 from . import _lib as L
-from .decode import MAX_BEAM, WER_MAX_LEN, _check_lengths, _check_logits, check_on_device
+from .decode import MAX_BEAM, WER_MAX_LEN, _check_lengths, _check_logits, check_heads, check_on_device
 from .heads import _dev_i32
 from .model import _LOGITS
-from .nbest import MAX_CLASSES, _check_beam, _check_nbest, _finite, ctc_decode_nbest_device
+from .nbest import (MAX_CLASSES, MAX_HEADS, BigramLM, _check_beam, _check_fusion, _check_nbest, _finite,
+                    _fusion_table, ctc_decode_fused_nbest_device, ctc_decode_fused_nbest_heads_device,
+                    ctc_decode_nbest_device, ctc_decode_nbest_heads_device)
 
 
 class MWERLossOp(Function):
@@ -61,6 +68,64 @@ class MWERLossOp(Function):
         return dx, None, None, None, None, None, None, None
 
 
+class MWERHeadsLossOp(Function):
+    """(loss (G), loglik, posterior, errors (G, B, M), ref_valid (G, B), risk (G, B)) of
+    `sca_mwer_heads_fwd` on the G batch-major fp32 logits `*logits`, each (B, T, C); with
+    `grouped=False` (one tensor) the results have no head axis and `loss` is 0-dim, so that the
+    caller's backward needs no indexing kernels; in_len (B),
+    tokens (G, B, N, H), out_len (G, B, N), count (G, B), ref (B, R), ref_len (B) int32 device
+    tensors; `with_ref`: the reference is slot N of every list (M = N + 1, else M = N); `table`:
+    the (C, C) fp32 device table of the prior or None, with `lm_weight` and `length_bonus`.
+    Only `loss` is differentiable, with respect to every head's logits; the workspace is kept for
+    the backward."""
+
+    @staticmethod
+    def forward(ctx, in_len, tokens, out_len, count, ref, ref_len, posterior_scale, with_ref, table, lm_weight,
+                length_bonus, grouped, *logits):
+        xs = [x.contiguous() for x in logits]
+        L.require_device(*xs, table)
+        G = len(xs)
+        B, T, C = xs[0].shape
+        N, H = tokens.shape[-2], tokens.shape[-1]
+        R, M = ref.shape[1], N + int(with_ref)
+        lib, x = L.lib(), xs[0]
+        ws = x.new_empty(max(lib.sca_mwer_heads_workspace_floats(G, B, N, T, H, R, int(with_ref)), 1))
+        if not grouped and G != 1:
+            raise RuntimeError("MWERHeadsLossOp: grouped=False takes one logits tensor")
+        lead = (G, B) if grouped else (B,)
+        loss = x.new_empty(lead[:-1])
+        loglik, posterior = x.new_empty(lead + (M,)), x.new_empty(lead + (M,))
+        errors = torch.empty(lead + (M,), dtype=torch.int32, device=x.device)
+        ref_valid = torch.empty(lead, dtype=torch.int32, device=x.device)
+        risk = x.new_empty(lead)
+        hx = L.decode_heads(xs)
+        L.check(lib.sca_mwer_heads_fwd(ctypes.byref(hx), G, L.ptr(in_len), L.ptr(tokens), L.ptr(out_len), L.ptr(count),
+                                       L.ptr(ref), L.ptr(ref_len), B, N, T, C, H, R, int(with_ref), L.ptr(table),
+                                       lm_weight, length_bonus, posterior_scale, L.ptr(loglik), L.ptr(posterior),
+                                       L.ptr(errors), L.ptr(ref_valid), L.ptr(risk), L.ptr(loss), L.ptr(ws),
+                                       L.stream_handle()), "sca_mwer_heads_fwd")
+        ctx.save_for_backward(in_len, tokens, out_len, count, ref, ref_len, ws, *xs)
+        ctx.with_ref = int(with_ref)
+        ctx.mark_non_differentiable(loglik, posterior, errors, ref_valid, risk)
+        return loss, loglik, posterior, errors, ref_valid, risk
+
+    @staticmethod
+    def backward(ctx, dloss, *_):
+        in_len, tokens, out_len, count, ref, ref_len, ws, *xs = ctx.saved_tensors
+        G = len(xs)
+        B, T, C = xs[0].shape
+        dloss = dloss.contiguous() if dloss is not None else xs[0].new_zeros(G)
+        dxs = [torch.empty_like(x) for x in xs]
+        hx, gx = L.decode_heads(xs), L.MwerGrads()
+        for g, dx in enumerate(dxs):
+            gx.dlogits[g] = dx.data_ptr()
+        L.check(L.lib().sca_mwer_heads_bwd(ctypes.byref(hx), G, L.ptr(in_len), L.ptr(tokens), L.ptr(out_len),
+                                           L.ptr(count), L.ptr(ref), L.ptr(ref_len), B, tokens.shape[-2], T, C,
+                                           tokens.shape[-1], ref.shape[1], ctx.with_ref, L.ptr(dloss), L.ptr(ws),
+                                           ctypes.byref(gx), L.stream_handle()), "sca_mwer_heads_bwd")
+        return (None,) * 12 + tuple(dxs)
+
+
 def _check_refs(labels, lengths, B, C, what):
     """`heads._validate_ctc`'s checks for the references, with an empty reference allowed; values
     are checked only where that needs no device read (host tensors)."""
@@ -83,8 +148,89 @@ def _check_refs(labels, lengths, B, C, what):
             raise RuntimeError(f"target values must lie in [0, {C}); got [{lo}, {hi}]")
 
 
+def _check_prior(lm, lm_weight, length_bonus, fusion, num_classes, what):
+    """The prior's arguments, validated on the host: (lm as a BigramLM or None, lm_weight,
+    length_bonus).  `lm` may also be a (C, C) table of finite log-probabilities (a device table
+    is then read once: hand over a `BigramLM` under capture)."""
+    if lm is not None and not isinstance(lm, BigramLM):
+        if not (torch.is_tensor(lm) or hasattr(lm, "__array__")):
+            raise ValueError(f"{what}: lm must be a BigramLM, a (C, C) table or None, got {type(lm).__name__}")
+        lm = BigramLM(lm)
+    try:
+        if num_classes is None and lm is not None:
+            num_classes = lm.num_classes
+        lw, lb = _check_fusion(lm, lm_weight, length_bonus, num_classes, what)
+    except TypeError:
+        raise ValueError(f"{what}: lm_weight and length_bonus must be numbers") from None
+    if not isinstance(fusion, bool):
+        raise ValueError(f"{what}: fusion must be a bool, got {fusion!r}")
+    if fusion and lm is None and lb == 0.0:
+        raise ValueError(f"{what}: fusion=True needs a gloss model or a length bonus: there is nothing to fuse")
+    return lm, lw, lb
+
+
+def _mwer_loss_heads(xs, grouped, input_lengths, gloss_labels, gloss_lengths, nbest, beam_size, nbest_size,
+                     posterior_scale, return_details, reference, lm, lm_weight, length_bonus, fusion):
+    """`mwer_loss` through `MWERHeadsLossOp`: the G tensors `xs` (validated by the caller) in one
+    call; `grouped=False` is a single tensor's call, whose results lose the head axis."""
+    what = "mwer_loss"
+    G = len(xs)
+    B, T, C = xs[0].shape
+    if not 1 <= C <= MAX_CLASSES:
+        raise ValueError(f"{what}: logits of {C} classes are outside [1, {MAX_CLASSES}]")
+    if G * B > 65535:
+        raise ValueError(f"{what}: {G} heads of {B} clips exceed the 65535 (head, clip) pairs of one call")
+    if not isinstance(reference, bool):
+        raise ValueError(f"{what}: reference must be a bool, got {reference!r}")
+    ps = _finite("posterior_scale", posterior_scale, what)
+    lm, lw, lb = _check_prior(lm, lm_weight, length_bonus, fusion, C, what)
+    il = _check_lengths(input_lengths, B, T)
+    labels = torch.as_tensor(gloss_labels)
+    _check_refs(labels, gloss_lengths, B, C, what)
+    if nbest is None:
+        beam, n = _check_beam(beam_size, nbest_size)
+        if T > WER_MAX_LEN:
+            raise ValueError(f"{what}: hypotheses over {T} logit frames exceed the WER kernel's {WER_MAX_LEN} tokens")
+    else:
+        if fusion:
+            raise ValueError(f"{what}: fusion=True decodes the list itself; it does not go with nbest=")
+        Gn, Bn, _, H = _check_nbest(nbest, what)
+        if nbest.tokens.dim() != (4 if grouped else 3) or Bn != B or Gn != G:
+            form = f"the {G} heads', tokens (G = {G}, B = {B}, N, H)" if grouped else \
+                f"a single head's, tokens (B = {B}, N, H)"
+            raise RuntimeError(f"{what}: the list must be {form}, got {tuple(nbest.tokens.shape)}")
+        if H > WER_MAX_LEN:
+            raise ValueError(f"{what}: hypotheses of up to {H} tokens exceed the WER kernel's {WER_MAX_LEN}")
+    check_on_device(None, xs[0])
+    dev = xs[0].device
+    table = _fusion_table(lm, dev, what)
+    in_len = _dev_i32(il, dev)
+    if nbest is None:
+        logits = xs if grouped else xs[0]
+        if fusion:
+            decode = ctc_decode_fused_nbest_heads_device if grouped else ctc_decode_fused_nbest_device
+            nbest = decode(logits, in_len, beam, lm, lw, lb, nbest=n, collapse_repeats=False)
+        else:
+            decode = ctc_decode_nbest_heads_device if grouped else ctc_decode_nbest_device
+            nbest = decode(logits, in_len, beam, n, collapse_repeats=False)
+    else:
+        check_on_device(what, nbest.tokens, nbest.lengths, nbest.count)
+    xs = [x if x.dtype == torch.float32 else x.float() for x in xs]
+    loss, *rest = MWERHeadsLossOp.apply(
+        in_len, _dev_i32(nbest.tokens, dev), _dev_i32(nbest.lengths, dev), _dev_i32(nbest.count, dev),
+        _dev_i32(labels, dev), _dev_i32(torch.as_tensor(gloss_lengths).reshape(-1), dev), ps, reference, table, lw, lb,
+        grouped, *xs)
+    if not return_details:
+        return loss
+    details = dict(zip(("loglik", "posterior", "errors", "ref_valid", "risk"), rest))
+    if not (grouped or reference):
+        del details["ref_valid"]
+    return loss, details
+
+
 def mwer_loss(gloss_logits, input_lengths, gloss_labels, gloss_lengths, nbest=None, beam_size=5, nbest_size=None,
-              posterior_scale=1.0, return_details=False):
+              posterior_scale=1.0, return_details=False, *, reference=False, lm=None, lm_weight=0.0,
+              length_bonus=0.0, fusion=False):
     """The MWER loss (0-dim, differentiable with respect to `gloss_logits`) of batch-major logits
     (B, T, C) against the references `gloss_labels` (B, R) padded / `gloss_lengths` (B); a
     reference may be empty.  `nbest=None`: the list is the `nbest_size` (default `beam_size`) best
@@ -94,9 +240,35 @@ def mwer_loss(gloss_logits, input_lengths, gloss_labels, gloss_lengths, nbest=No
     the logits' device.  With `return_details` also a dict of device tensors: `loglik` (B, N) (the
     exact CTC log-likelihoods, -inf for entries that do not exist or do not fit), `posterior`
     (B, N), `errors` (B, N) int32, `risk` (B).  T, H and R are limited by the WER kernel's 128
-    tokens.  No host sync under capture; capturable."""
+    tokens.  No host sync under capture; capturable.
+
+    Keyword-only, all off by default (the call is then exactly the above):
+    `reference=True` makes each clip's reference one more entry of its list, slot N of N + 1 (the
+    details' last axis): error count 0, its own exact likelihood, left out of the posterior where
+    the list holds the reference already or the reference does not fit in `input_lengths` frames;
+    `ref_valid` (B) int32 in the details says where it counts, and `loglik[:, N]` is the
+    reference's likelihood wherever it fits.  A list whose hypotheses are all equally wrong then
+    has a gradient, towards the transcript.
+    `lm` (a `BigramLM` on the logits' device, or a (C, C) table), `lm_weight`, `length_bonus`: the
+    posterior is the softmax of posterior_scale * (ll + lm_weight * lm(h) + length_bonus * len(h)),
+    the total `rescore_nbest_device` ranks by, for the reference slot too.
+    `fusion=True` (with `nbest=None`) takes the list from `ctc_decode_fused_nbest_device(...,
+    collapse_repeats=False)` with the same table and weights.
+    `gloss_logits` may be a sequence of G tensors of one shape, the heads of one forward, with the
+    references shared: the lists are decoded by the grouped decoders, or `nbest` is a heads-form
+    `NBest` (tokens (G, B, N, H)); one grouped call then returns `loss` (G), one mean per head,
+    and details with a leading G axis, `ref_valid` (G, B) among them.  Head g is bitwise the
+    single-tensor call on it."""
     what = "mwer_loss"
+    if isinstance(gloss_logits, (list, tuple)):
+        return _mwer_loss_heads(check_heads(gloss_logits, what), True, input_lengths, gloss_labels, gloss_lengths,
+                                nbest, beam_size, nbest_size, posterior_scale, return_details, reference, lm,
+                                lm_weight, length_bonus, fusion)
     _check_logits(gloss_logits)
+    if reference or fusion or lm is not None or lm_weight != 0.0 or length_bonus != 0.0:
+        return _mwer_loss_heads([gloss_logits], False, input_lengths, gloss_labels, gloss_lengths, nbest, beam_size,
+                                nbest_size, posterior_scale, return_details, reference, lm, lm_weight, length_bonus,
+                                fusion)
     B, T, C = gloss_logits.shape
     if not 1 <= C <= MAX_CLASSES:
         raise ValueError(f"{what}: logits of {C} classes are outside [1, {MAX_CLASSES}]")
@@ -136,9 +308,14 @@ class MWER:
     logits `head` (one of the model's five), with the list decoded per step by a beam of
     `beam_size` (1 <= beam_size <= 32) keeping `nbest` entries (default: all of the beam), the
     posterior sharpened by `posterior_scale`, and `weight` (finite, >= 0) times the loss added to
-    `total_loss` for the backward.  ValueError for anything else."""
+    `total_loss` for the backward.  `head` may be a tuple of distinct head names: their losses
+    come from one grouped call and the step adds `weight` times their sum.  `reference`, `lm`
+    (a `BigramLM` on the model's device, or a (C, C) table), `lm_weight`, `length_bonus` and
+    `fusion` are `mwer_loss`'s: the reference as one more entry of every list, the gloss model's
+    prior inside the posterior, the list from the fused search.  ValueError for anything else."""
 
-    def __init__(self, weight, beam_size=5, nbest=None, posterior_scale=1.0, head="fuse_coord_gloss_logits"):
+    def __init__(self, weight, beam_size=5, nbest=None, posterior_scale=1.0, head="fuse_coord_gloss_logits", *,
+                 reference=False, lm=None, lm_weight=0.0, length_bonus=0.0, fusion=False):
         for v in (weight, posterior_scale):
             if isinstance(v, bool) or not isinstance(v, (int, float)):
                 raise ValueError(f"MWER: weight and posterior_scale must be numbers, got {v!r}")
@@ -153,13 +330,31 @@ class MWER:
                 raise ValueError(f"MWER: {name} must be an int in [1, {MAX_BEAM}], got {v!r}")
         if nbest is not None and nbest > beam_size:
             raise ValueError(f"MWER: nbest = {nbest} exceeds beam_size = {beam_size}")
-        if head not in _LOGITS:
-            raise ValueError(f"MWER: head must be one of {_LOGITS}, got {head!r}")
+        if isinstance(head, list):
+            head = tuple(head)
+        names = head if isinstance(head, tuple) else (head,)
+        if not 1 <= len(names) <= MAX_HEADS:
+            raise ValueError(f"MWER: between 1 and {MAX_HEADS} heads, got {len(names)}")
+        for name in names:
+            if not isinstance(name, str) or name not in _LOGITS:
+                raise ValueError(f"MWER: head must be one of {_LOGITS} or a tuple of them, got {name!r}")
+        if len(set(names)) != len(names):
+            raise ValueError(f"MWER: the heads must be distinct, got {names}")
+        if not isinstance(reference, bool):
+            raise ValueError(f"MWER: reference must be a bool, got {reference!r}")
+        self.lm, self.lm_weight, self.length_bonus = _check_prior(lm, lm_weight, length_bonus, fusion, None, "MWER")
+        self.reference, self.fusion = reference, fusion
         self.beam_size, self.nbest, self.head = beam_size, beam_size if nbest is None else nbest, head
+        self.heads = names  # the head names as a tuple, whatever form `head` has
 
     def __repr__(self):
+        extra = ""  # the keyword-only arguments appear where they differ from their defaults
+        for name, default in (("reference", False), ("lm", None), ("lm_weight", 0.0), ("length_bonus", 0.0),
+                              ("fusion", False)):
+            if getattr(self, name) is not default and getattr(self, name) != default:
+                extra += f", {name}={getattr(self, name)!r}"
         return (f"MWER(weight={self.weight}, beam_size={self.beam_size}, nbest={self.nbest}, posterior_scale="
-                f"{self.posterior_scale}, head={self.head!r})")
+                f"{self.posterior_scale}, head={self.head!r}{extra})")
 
 
 def check_mwer(mwer, what):

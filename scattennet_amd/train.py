@@ -35,12 +35,19 @@ from .mwer import check_mwer, mwer_guard, mwer_loss
 def _add_mwer(outputs, src_input, mwer):
     """The MWER term of a step: `outputs["mwer_loss"]`, `outputs["mwer_risk"]` (B) and
     `outputs["mwer_report"]` = (mwer_loss, mean risk), the two numbers `read_report` adds to its
-    one copy.  Returns the loss to back-propagate."""
-    logits = outputs[mwer.head]
-    labels = heads.labels_2d(src_input, logits.shape[0], "train_step")
-    loss, details = mwer_loss(logits, outputs["input_lengths"], labels, src_input["gloss_lengths"],
-                              beam_size=mwer.beam_size, nbest_size=mwer.nbest, posterior_scale=mwer.posterior_scale,
-                              return_details=True)
+    one copy.  Returns the loss to back-propagate.  With a tuple of G heads, one grouped call:
+    `outputs["mwer_losses"]` (G) holds each head's loss, `mwer_loss` their sum and `mwer_risk` is
+    (G, B)."""
+    grouped = isinstance(mwer.head, tuple)
+    logits = [outputs[name] for name in mwer.heads]
+    labels = heads.labels_2d(src_input, logits[0].shape[0], "train_step")
+    loss, details = mwer_loss(logits if grouped else logits[0], outputs["input_lengths"], labels,
+                              src_input["gloss_lengths"], beam_size=mwer.beam_size, nbest_size=mwer.nbest,
+                              posterior_scale=mwer.posterior_scale, return_details=True, reference=mwer.reference,
+                              lm=mwer.lm, lm_weight=mwer.lm_weight, length_bonus=mwer.length_bonus,
+                              fusion=mwer.fusion)
+    if grouped:
+        outputs["mwer_losses"], loss = loss, loss.sum()
     outputs["mwer_loss"], outputs["mwer_risk"] = loss, details["risk"]
     outputs["mwer_report"] = torch.stack([loss.detach(), details["risk"].mean()])
     return outputs["total_loss"] + mwer.weight * loss
@@ -49,7 +56,8 @@ def _add_mwer(outputs, src_input, mwer):
 def train_step(model, optimizer, src_input, mwer=None):
     """One training step of MSCA_Net with FusedAdam, enqueued on the current stream without a
     host read.  Returns the forward's outputs (`finite_report` holds the losses and flags).
-    `mwer`: None, or an `MWER`: the step decodes the chosen head's logits into an n-best list,
+    `mwer`: None, or an `MWER`: the step decodes the chosen head's logits (or, for a tuple of heads,
+    all of them in one grouped call, which also adds `mwer_losses` (G)) into an n-best list,
     adds `mwer_loss`, `mwer_risk` and `mwer_report` to the outputs (the last is the pair
     (mwer_loss, mean risk) as one device tensor, which lets `read_report` keep to a single copy) and
     back-propagates `total_loss + weight * mwer_loss`; a non-finite `mwer_loss` skips the update on the device like a flagged tensor."""

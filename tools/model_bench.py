@@ -53,6 +53,9 @@ third pass takes its list from the fused search (Rescoring(..., fusion=True)), i
 --mwer (with --mixed): two BucketedTrainStep over the same stream, one with mwer=MWER(0.5, beam_size=--beam)
 (the n-best decode, the MWER loss and its backward inside every bucket's graph); whole passes in alternated
 windows, ms per step and the per-window difference, and the mean mwer_risk / mwer_loss of the stream.
+--mwer-reference / --mwer-lm / --mwer-heads 2 add a third step in the same alternation whose spec has the
+reference as a list entry / a bigram table in the posterior / both CTC heads in one grouped call, with the
+stream's statistics for that spec.
 """
 import argparse
 import json
@@ -267,7 +270,20 @@ def mixed_mwer(a, dev):
     adam = dict(lr=1e-4, betas=(0.9, 0.998), weight_decay=1e-3, max_grad_norm=1.0)
     buckets = tuple(int(b) for b in a.buckets.split(","))
     steps = {}
-    for name, spec in (("plain", None), ("mwer", S.MWER(0.5, beam_size=a.beam))):
+    variants = [("plain", None), ("mwer", S.MWER(0.5, beam_size=a.beam))]
+    if a.mwer_reference or a.mwer_lm or a.mwer_heads > 1:
+        # a third step with the extended spec: the reference as a list entry, the gloss model's
+        # prior (a random normalised table, weight 0.5), the first --mwer-heads CTC heads grouped
+        names = ("fuse_coord_gloss_logits", "alignment_gloss_logits")[:max(a.mwer_heads, 1)]
+        lm = None
+        if a.mwer_lm:
+            table = torch.log_softmax(torch.randn(a.C, a.C, generator=torch.Generator().manual_seed(a.seed + 7)) * 2, -1)
+            lm = S.BigramLM(table, dev)
+        variants.append(("mwer_ext", S.MWER(0.5, beam_size=a.beam, reference=a.mwer_reference, lm=lm,
+                                            lm_weight=0.5 if a.mwer_lm else 0.0,
+                                            head=names if a.mwer_heads > 1 else names[0])))
+    specs = dict(variants)
+    for name, spec in variants:
         model, _, w, _ = build(a, dev)
         model.check = "defer"
         opt = S.FusedAdam(model.parameters(), capture_slots=len(buckets), **adam)
@@ -281,39 +297,52 @@ def mixed_mwer(a, dev):
     for _ in range(a.windows):  # alternated windows
         for k, step in steps.items():
             ms[k].append(_pass(step.step, batches))
-    risk, loss, skipped, clips, live, rows, nonzero = [], [], 0, 0, 0, 0, 0
-    for src, _ in batches:
-        out = steps["mwer"].step(src)
-        rep = S.read_report(out)
-        risk.append(rep["mwer_risk"])
-        loss.append(rep["mwer_loss"])
-        skipped += rep["skipped"]
-        # the same list and loss once more on the step's logits, for the per-clip figures
-        z = out["fuse_coord_gloss_logits"].detach().clone().requires_grad_(True)
-        nb = S.ctc_decode_nbest_device(z, out["input_lengths"], a.beam, a.beam, collapse_repeats=False)
-        l, det = S.mwer_loss(z, out["input_lengths"], src["gloss_labels"], src["gloss_lengths"], nbest=nb,
-                             return_details=True)
-        l.backward()
-        valid = torch.isfinite(det["loglik"])
-        err = det["errors"].float()
-        hi = torch.where(valid, err, err.new_full((), -1e9)).max(1).values
-        lo = torch.where(valid, err, err.new_full((), 1e9)).min(1).values
-        clips += a.B
-        live += int((hi > lo).sum())
-        frames = torch.arange(z.shape[1], device=dev)[None, :] < out["input_lengths"][:, None]
-        rows += int(frames.sum())
-        nonzero += int(((z.grad.abs().amax(-1) > 0) & frames).sum())
-        del l, det
+    def stream_statistics(name):
+        """The figures of one MWER step over the stream, on its first head."""
+        spec = specs[name]
+        risk, loss, skipped, clips, live, rows, nonzero = [], [], 0, 0, 0, 0, 0
+        for src, _ in batches:
+            out = steps[name].step(src)
+            rep = S.read_report(out)
+            risk.append(rep["mwer_risk"])
+            loss.append(rep["mwer_loss"])
+            skipped += rep["skipped"]
+            # the same list and loss once more on the step's logits, for the per-clip figures
+            z = out[spec.heads[0]].detach().clone().requires_grad_(True)
+            nb = S.ctc_decode_nbest_device(z, out["input_lengths"], a.beam, a.beam, collapse_repeats=False)
+            l, det = S.mwer_loss(z, out["input_lengths"], src["gloss_labels"], src["gloss_lengths"], nbest=nb,
+                                 return_details=True, reference=spec.reference, lm=spec.lm, lm_weight=spec.lm_weight,
+                                 length_bonus=spec.length_bonus)
+            l.backward()
+            valid = torch.isfinite(det["loglik"])
+            if spec.reference:  # the reference slot counts where it is in the posterior
+                valid[:, -1] = det["ref_valid"] != 0
+            err = det["errors"].float()
+            hi = torch.where(valid, err, err.new_full((), -1e9)).max(1).values
+            lo = torch.where(valid, err, err.new_full((), 1e9)).min(1).values
+            clips += a.B
+            live += int((hi > lo).sum())
+            frames = torch.arange(z.shape[1], device=dev)[None, :] < out["input_lengths"][:, None]
+            rows += int(frames.sum())
+            nonzero += int(((z.grad.abs().amax(-1) > 0) & frames).sum())
+            del l, det
+        return {"mwer_risk_mean": round(statistics.mean(risk), 4), "mwer_loss_mean": round(statistics.mean(loss), 6),
+                "clips_with_non_constant_errors": round(live / clips, 4),
+                "gradient_rows_non_zero": round(nonzero / max(rows, 1), 4), "skipped_steps": skipped}
+
     diff = [x - y for x, y in zip(ms["mwer"], ms["plain"])]
-    print(json.dumps({"workload": "MSCA_Net BucketedTrainStep over a mixed-length stream with and without the MWER "
-                                  "loss, eval mode, no report read in the timed passes",
-                      "B": a.B, "max_len": a.T, "C": a.C, "S": a.S, "seed": a.seed, "beam": a.beam,
-                      "buckets": list(buckets), "batch_lengths": [T for _, T in batches],
-                      "plain_ms_per_step": _spread(ms["plain"]), "mwer_ms_per_step": _spread(ms["mwer"]),
-                      "mwer_minus_plain_ms_per_step": _spread(diff), "mwer_risk_mean": round(statistics.mean(risk), 4),
-                      "mwer_loss_mean": round(statistics.mean(loss), 6),
-                      "clips_with_non_constant_errors": round(live / clips, 4),
-                      "gradient_rows_non_zero": round(nonzero / max(rows, 1), 4), "skipped_steps": skipped}))
+    res = {"workload": "MSCA_Net BucketedTrainStep over a mixed-length stream with and without the MWER "
+                       "loss, eval mode, no report read in the timed passes",
+           "B": a.B, "max_len": a.T, "C": a.C, "S": a.S, "seed": a.seed, "beam": a.beam,
+           "buckets": list(buckets), "batch_lengths": [T for _, T in batches],
+           "plain_ms_per_step": _spread(ms["plain"]), "mwer_ms_per_step": _spread(ms["mwer"]),
+           "mwer_minus_plain_ms_per_step": _spread(diff), **stream_statistics("mwer")}
+    if "mwer_ext" in steps:
+        res["mwer_ext"] = {"spec": repr(specs["mwer_ext"]), "ms_per_step": _spread(ms["mwer_ext"]),
+                           "minus_plain_ms_per_step": _spread([x - y for x, y in zip(ms["mwer_ext"], ms["plain"])]),
+                           "minus_mwer_ms_per_step": _spread([x - y for x, y in zip(ms["mwer_ext"], ms["mwer"])]),
+                           **stream_statistics("mwer_ext")}
+    print(json.dumps(res))
 
 
 def eval_loop(S, model, beam):
@@ -519,6 +548,12 @@ def main():
                                                     "without the rescored n-best decode")
     ap.add_argument("--mwer", action="store_true", help="with --mixed: BucketedTrainStep with and without the MWER "
                                                         "loss (beam --beam), alternated windows")
+    ap.add_argument("--mwer-reference", action="store_true", help="with --mixed --mwer: a third step whose MWER "
+                    "spec has the reference as a list entry")
+    ap.add_argument("--mwer-lm", action="store_true", help="with --mixed --mwer: the third step's posterior "
+                    "includes a bigram table (weight 0.5)")
+    ap.add_argument("--mwer-heads", type=int, default=1, choices=(1, 2), help="with --mixed --mwer: the third "
+                    "step trains this many CTC heads in one grouped call")
     ap.add_argument("--beam", type=int, default=5)
     ap.add_argument("--batches", type=int, default=20)
     ap.add_argument("--buckets", default="64,128,192,256")

@@ -18,7 +18,13 @@ clip's list (so the error counts differ).  Also the statistics of the loss on th
 risk, the share of clips with non-constant error counts and the share of non-zero gradient rows.
 Needs a GPU.
 
+--reference, --lm, --heads G time the extended loss (the reference as a list entry, the bigram table
+inside the posterior, G tensors in one grouped call) beside its yardsticks instead: see `extended`.
+--dump PATH saves the plain loss's outputs and gradient, for a bit-for-bit comparison of two builds
+(SCA_LIB_PATH selects the library).
+
 Usage: python tools/mwer_bench.py [--B 8] [--T 64] [--C 1124] [--beam 5] [--nbest 5] [--steps 200]
+                                  [--reference] [--lm] [--heads G] [--dump PATH]
 """
 import argparse
 import json
@@ -47,8 +53,94 @@ def statistics_of(S, z, il, ref, ref_len, nb):
             "gradient_rows_non_zero": round(float((z.grad.abs().amax(-1) > 0).float().mean()), 4)}
 
 
+def extended(a, S, dev):
+    """--reference / --lm / --heads: the extended loss beside its yardsticks, forward + backward,
+    captured graphs in alternated windows.  Lists: the decoder's own; references: entry 1 of each
+    list with its middle token replaced by a class the list's clip does not use there (a
+    reference that is NOT in the list, so the slot is valid everywhere).
+    * `mwer`             the plain loss at N entries (the old entry points)
+    * `mwer_reference`   reference=True at N entries              (--reference)
+    * `mwer_n_plus_1`    the plain loss over a list of N + 1 entries: the slot's yardstick
+    * `mwer_lm`          the table on, everything else as the widest variant above   (--lm)
+    * `mwer_heads`       one grouped call over G tensors                             (--heads G)
+    * `mwer_calls`       G single calls on the same tensors"""
+    g = torch.Generator().manual_seed(0)
+    G, N = max(a.heads, 1), a.nbest
+    xs = [(torch.randn(a.B, a.T, a.C, generator=g) * 4).to(dev) for _ in range(G)]
+    il = torch.full((a.B,), a.T, dtype=torch.int32, device=dev)
+    nbs = [S.ctc_decode_nbest_device(x, il, a.beam, N, collapse_repeats=False) for x in xs]
+    nb6 = S.ctc_decode_nbest_device(xs[0], il, max(a.beam, N + 1), N + 1, collapse_repeats=False)
+    pick = min(1, N - 1)
+    ref_len = nbs[0].lengths[:, pick].contiguous()
+    R = max(int(ref_len.max()), 1)
+    ref = nbs[0].tokens[:, pick, :R].clone()
+    mid = (ref_len // 2).clamp(max=R - 1).long()[:, None]
+    ref.scatter_(1, mid, (ref.gather(1, mid) % (a.C - 1)) + 1)  # another class in [1, C)
+    lm = None
+    if a.lm:
+        lm = S.BigramLM(torch.log_softmax(torch.randn(a.C, a.C, generator=g) * 2, -1), dev)
+    kw = dict(reference=a.reference, lm=lm, lm_weight=0.7 if a.lm else 0.0, length_bonus=0.3 if a.lm else 0.0)
+    heads_nb = S.NBest(*(torch.stack(t) for t in zip(*nbs)))
+
+    def leaves():
+        return [x.detach().clone().requires_grad_(True) for x in xs]
+
+    def single(nb, zs=None, **kw):
+        zs = zs or leaves()[:1]
+
+        def fn():
+            zs[0].grad = None
+            S.mwer_loss(zs[0], il, ref, ref_len, nbest=nb, **kw).backward()
+        return fn
+
+    fns = {"mwer": single(nbs[0])}
+    if a.reference:
+        fns["mwer_reference"] = single(nbs[0], reference=True)
+        fns["mwer_n_plus_1"] = single(nb6)
+    if a.lm:
+        fns["mwer_lm"] = single(nbs[0], **kw)
+    if G > 1:
+        zg, zc = leaves(), leaves()
+
+        def mwer_heads():
+            for z in zg:
+                z.grad = None
+            S.mwer_loss(zg, il, ref, ref_len, nbest=heads_nb, **kw).sum().backward()
+
+        def mwer_calls():
+            for z, nb in zip(zc, nbs):
+                z.grad = None
+                S.mwer_loss(z, il, ref, ref_len, nbest=nb, **kw).backward()
+
+        fns["mwer_heads"], fns["mwer_calls"] = mwer_heads, mwer_calls
+    replays = {}
+    for name, fn in fns.items():
+        replays[name] = graphed(fn)
+        for _ in range(a.warmup):
+            replays[name]()
+    timed = alternated(replays, a.steps, a.repeats)
+    z = leaves()[0]
+    loss, det = S.mwer_loss(z, il, ref, ref_len, nbest=nbs[0], return_details=True, **kw)
+    loss.backward()
+    stats = {"loss": round(float(loss.detach()), 6), "risk_mean": round(float(det["risk"].mean()), 4),
+             "gradient_rows_non_zero": round(float((z.grad.abs().amax(-1) > 0).float().mean()), 4)}
+    if a.reference:
+        stats["ref_valid_share"] = round(float(det["ref_valid"].float().mean()), 4)
+    res = {"workload": "extended MWER loss forward + backward beside its yardsticks, graph replays", "B": a.B, "T": a.T,
+           "C": a.C, "beam": a.beam, "nbest": N, "heads": G, "reference": a.reference, "lm": a.lm, "R": R,
+           "steps": a.steps, "repeats": a.repeats, "unit": "us per call", "statistics": stats, "graph": timed}
+    if G > 1:
+        res["heads_over_calls"] = round(timed["mwer_heads"]["median"] / timed["mwer_calls"]["median"], 3)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--reference", action="store_true", help="time reference=True beside N and N + 1 entries")
+    ap.add_argument("--lm", action="store_true", help="time the bigram table inside the posterior")
+    ap.add_argument("--heads", type=int, default=1, help="time one grouped call over G tensors beside G calls")
+    ap.add_argument("--dump", default=None, help="save the plain loss's outputs and dlogits here (torch.save), to "
+                    "compare two builds bit for bit")
     ap.add_argument("--B", type=int, default=8)
     ap.add_argument("--T", type=int, default=64)
     ap.add_argument("--C", type=int, default=1124)
@@ -63,6 +155,8 @@ def main():
     import scattennet_amd as S
     from scattennet_amd.heads import CTCLossOp
     dev = torch.device("cuda")
+    if a.reference or a.lm or a.heads > 1:
+        return extended(a, S, dev)
     g = torch.Generator().manual_seed(0)
     x = (torch.randn(a.B, a.T, a.C, generator=g) * 4).to(dev)
     il = torch.full((a.B,), a.T, dtype=torch.int32, device=dev)
@@ -115,6 +209,11 @@ def main():
             replays[name]()
     timed = alternated(replays, a.steps, a.repeats)
     stats = statistics_of(S, leaf(), il, ref, ref_len, nb)
+    if a.dump:
+        z = leaf()
+        loss, det = S.mwer_loss(z, il, ref, ref_len, nbest=nb, posterior_scale=0.8, return_details=True)
+        loss.backward()
+        torch.save({"loss": loss.detach().cpu(), "dlogits": z.grad.cpu(), **{k: v.cpu() for k, v in det.items()}}, a.dump)
     res = {"workload": "MWER loss forward + backward beside the CTC loss, graph replays", "B": a.B, "T": a.T, "C": a.C,
            "beam": a.beam, "nbest": N, "steps": a.steps, "repeats": a.repeats, "unit": "us per call",
            "statistics": stats, "graph": timed}
