@@ -855,7 +855,8 @@ int sca_mwer_bwd(const float* logits, const int* in_len, const int* tokens, cons
  *     it is -nll of sca_ctc_loss_fwd for the clip.
  *   Prior: lmterm_n = lm_weight * lm(h_n) + length_bonus * len(h_n), lm(h) being
  *     sca_nbest_rescore's and the same device code: class 0 is the boundary, lm(empty) =
- *     lm[0, 0], lm = NULL means lm(h) = 0.  It applies to the reference slot too.
+ *     lm[0, 0], lm = NULL means lm(h) = 0.  It applies to the reference slot too.  The term is
+ *     computed and added only with lm != NULL or length_bonus != 0: otherwise it is +0.0f.
  *   z_n = posterior_scale * (ll_n + lmterm_n), post = softmax over V of z; ebar, d_n, risk,
  *     loss_b and w_n as above over the enlarged V; loss (G): one mean over the B clips per head.
  *     The prior is a constant of the posterior, so the gradient formula is unchanged; the

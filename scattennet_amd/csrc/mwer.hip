@@ -11,7 +11,9 @@
 // One set of kernels behind sca_mwer_fwd / bwd and sca_mwer_heads_fwd / bwd.  A "clip" of the
 // grids, the workspace and the outputs is the (head, clip) pair p = g B + b (CtcHeads, ctc.h);
 // a slot is an entry of the list or, with_ref, slot N: the clip's reference, read where it lies
-// (no copy of the list).  The old entry points are G = 1 without the reference and the prior.
+// (no copy of the list).  One host path too (MwCall): sca_mwer_fwd / bwd are its G = 1 case
+// without the reference and the prior, and a heads call without a table and a length bonus
+// skips the prior as they do.
 // No float atomics; every sum over slots, states and clips runs in a fixed order, so the
 // results are deterministic and a replayed capture is bitwise the eager call.
 #include "ctc.h"
@@ -394,23 +396,77 @@ bool mwer_dims_ok(int G, int B, int N, int T, int C, int H, int R) {
 #define MWER_HEADS_LIMITS \
   "bad arguments (1 <= G <= 8, B >= 1, G B <= 65535, T >= 1, C <= 8192, 1 <= N <= 32, 1 <= H, R <= 128, finite weights)"
 
-// The forward of every entry point, after validation: three launches, four above
-// MW_CLIPS_ONE_GROUP pairs.  ref_valid may be NULL without the reference.
-void mwer_fwd_launch(const CtcHeads& heads, const sca_decode_heads* table, int G, const int* in_len, const int* tokens,
-                     const int* out_len, const int* count, const int* ref, const int* ref_len, MwDims d,
-                     MwPrior prior, float posterior_scale, float* loglik, float* posterior, int* errors,
-                     int* ref_valid, float* risk, float* loss, float* ws, hipStream_t st) {
-  if (G == 1) {
-    sca_ctc_rowstat_launch(heads.x[0], ws, (long)d.B * d.T, d.C, st);
+// One call of any of the four entry points, forward or backward.  A single-tensor entry point is
+// G = 1 with its tensor in heads->logits[0] (and dlogits->dlogits[0]), with_ref = 0, no prior and
+// ref_valid = NULL; its backward has no references (R = 1).  A backward is initialised up to
+// dlogits and leaves the forward's fields 0 / NULL; a forward has dloss = dlogits = NULL.
+struct MwCall {
+  const char* name;  // of the entry point, for the errors
+  bool grouped;      // the _heads form: its limits, ref_valid required, the references in the backward too
+  const sca_decode_heads* heads;
+  int G;
+  const int *in_len, *tokens, *out_len, *count, *ref, *ref_len;
+  int B, N, T, C, H, R, with_ref;
+  const float* ws;     // the forward writes it
+  const float* dloss;  // backward
+  const sca_mwer_grads* dlogits;
+  MwPrior prior;  // forward
+  float posterior_scale;
+  float *loglik, *posterior;
+  int *errors, *ref_valid;
+  float *risk, *loss;
+};
+
+bool mw_call_ok(const MwCall& c, bool bwd) {
+  bool ok = c.heads && mwer_dims_ok(c.G, c.B, c.N, c.T, c.C, c.H, c.R) && c.in_len && c.tokens && c.out_len &&
+            c.count && c.ws && ((c.ref && c.ref_len) || (bwd && !c.grouped));
+  if (bwd) {
+    ok = ok && c.dloss && c.dlogits;
   } else {
-    sca_ctc_rowstat_heads_launch(table, G, ws, (long)d.B * d.T, d.C, st);
+    ok = ok && c.prior.weight - c.prior.weight == 0.0f && c.prior.bonus - c.prior.bonus == 0.0f &&
+         c.posterior_scale == c.posterior_scale && c.loglik && c.posterior && c.errors &&
+         (c.ref_valid || !c.grouped) && c.risk && c.loss;
   }
-  hipLaunchKernelGGL(mwer_entry_kernel, dim3(d.M, d.P, 3), dim3(128), 0, st, heads, in_len, tokens, out_len, count,
-                     ref, ref_len, d, prior, ws, errors);
+  for (int g = 0; ok && g < c.G; ++g) ok = c.heads->logits[g] && (!bwd || c.dlogits->dlogits[g]);
+  if (!ok) {
+    char msg[256];
+    snprintf(msg, sizeof(msg), "%s: %s", c.name, c.grouped ? MWER_HEADS_LIMITS : MWER_LIMITS);
+    sca_set_error(msg);
+  }
+  return ok;
+}
+
+// The forward of every entry point: three launches, four above MW_CLIPS_ONE_GROUP pairs.  The
+// prior's term is computed only where it can differ from 0: with a table or a length bonus.
+int mwer_fwd(const MwCall& c, void* stream) {
+  if (!mw_call_ok(c, false)) return SCA_ERR_ARG;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const MwDims d = mw_dims(c.G, c.B, c.N, c.T, c.C, c.H, c.R, c.with_ref, c.prior.lm || c.prior.bonus != 0.0f);
+  float* ws = const_cast<float*>(c.ws);
+  if (c.G == 1) {
+    sca_ctc_rowstat_launch(c.heads->logits[0], ws, (long)d.B * d.T, d.C, st);
+  } else {
+    sca_ctc_rowstat_heads_launch(c.heads, c.G, ws, (long)d.B * d.T, d.C, st);
+  }
+  hipLaunchKernelGGL(mwer_entry_kernel, dim3(d.M, d.P, 3), dim3(128), 0, st, ctc_heads_of(c.heads, c.G), c.in_len,
+                     c.tokens, c.out_len, c.count, c.ref, c.ref_len, d, c.prior, ws, c.errors);
   const int groups = d.P <= MW_CLIPS_ONE_GROUP ? 1 : (d.P + 3) / 4;
-  hipLaunchKernelGGL(mwer_clip_kernel, dim3(groups), dim3(256), 0, st, count, errors, d, posterior_scale, ws, loglik,
-                     posterior, ref_valid, risk, loss);
-  if (groups > 1) hipLaunchKernelGGL(mwer_loss_sum_kernel, dim3(G), dim3(64), 0, st, d, ws, loss);
+  hipLaunchKernelGGL(mwer_clip_kernel, dim3(groups), dim3(256), 0, st, c.count, c.errors, d, c.posterior_scale, ws,
+                     c.loglik, c.posterior, c.ref_valid, c.risk, c.loss);
+  if (groups > 1) hipLaunchKernelGGL(mwer_loss_sum_kernel, dim3(c.G), dim3(64), 0, st, d, c.ws, c.loss);
+  return sca_launch_status(c.name);
+}
+
+// The backward of every entry point: one launch.  The prior does not reach the gradient.
+int mwer_bwd(const MwCall& c, void* stream) {
+  if (!mw_call_ok(c, true)) return SCA_ERR_ARG;
+  MwGrads grads = {};
+  for (int g = 0; g < SCA_EVAL_MAX_HEADS; ++g) grads.dx[g] = c.dlogits->dlogits[g < c.G ? g : 0];
+  const MwDims d = mw_dims(c.G, c.B, c.N, c.T, c.C, c.H, c.R, c.with_ref, 0);
+  hipLaunchKernelGGL(mwer_grad_kernel, dim3(d.T, d.P), dim3(MW_GRAD_THREADS), 0, reinterpret_cast<hipStream_t>(stream),
+                     ctc_heads_of(c.heads, c.G), c.in_len, c.tokens, c.out_len, c.count, c.ref, c.ref_len, d, c.ws,
+                     c.dloss, grads);
+  return sca_launch_status(c.name);
 }
 
 }  // namespace
@@ -429,35 +485,20 @@ extern "C" int sca_mwer_fwd(const float* logits, const int* in_len, const int* t
                             const int* count, const int* ref, const int* ref_len, int B, int N, int T, int C, int H,
                             int R, float posterior_scale, float* loglik, float* posterior, int* errors, float* risk,
                             float* loss, float* ws, void* stream) {
-  if (!mwer_dims_ok(1, B, N, T, C, H, R) || !logits || !in_len || !tokens || !out_len || !count || !ref || !ref_len ||
-      !(posterior_scale == posterior_scale) || !loglik || !posterior || !errors || !risk || !loss || !ws) {
-    sca_set_error("sca_mwer_fwd: " MWER_LIMITS);
-    return SCA_ERR_ARG;
-  }
-  sca_decode_heads table = {};
-  table.logits[0] = logits;
-  mwer_fwd_launch(ctc_heads_of(&table, 1), &table, 1, in_len, tokens, out_len, count, ref, ref_len,
-                  mw_dims(1, B, N, T, C, H, R, 0, 0), MwPrior{nullptr, 0.0f, 0.0f}, posterior_scale, loglik, posterior,
-                  errors, nullptr, risk, loss, ws, reinterpret_cast<hipStream_t>(stream));
-  return sca_launch_status("sca_mwer_fwd");
+  const sca_decode_heads one = {{logits}};
+  return mwer_fwd({"sca_mwer_fwd", false, &one, 1, in_len, tokens, out_len, count, ref, ref_len, B, N, T, C, H, R, 0,
+                   ws, nullptr, nullptr, {}, posterior_scale, loglik, posterior, errors, nullptr, risk, loss},
+                  stream);
 }
 
 extern "C" int sca_mwer_bwd(const float* logits, const int* in_len, const int* tokens, const int* out_len,
                             const int* count, int B, int N, int T, int C, int H, const float* dloss, const float* ws,
                             float* dlogits, void* stream) {
-  if (!mwer_dims_ok(1, B, N, T, C, H, 1) || !logits || !in_len || !tokens || !out_len || !count || !dloss || !ws ||
-      !dlogits) {
-    sca_set_error("sca_mwer_bwd: " MWER_LIMITS);
-    return SCA_ERR_ARG;
-  }
-  sca_decode_heads table = {};
-  table.logits[0] = logits;
-  MwGrads grads = {};
-  grads.dx[0] = dlogits;
-  hipLaunchKernelGGL(mwer_grad_kernel, dim3(T, B), dim3(MW_GRAD_THREADS), 0, reinterpret_cast<hipStream_t>(stream),
-                     ctc_heads_of(&table, 1), in_len, tokens, out_len, count, nullptr, nullptr,
-                     mw_dims(1, B, N, T, C, H, 1, 0, 0), ws, dloss, grads);
-  return sca_launch_status("sca_mwer_bwd");
+  const sca_decode_heads one = {{logits}};
+  const sca_mwer_grads grads = {{dlogits}};
+  return mwer_bwd({"sca_mwer_bwd", false, &one, 1, in_len, tokens, out_len, count, nullptr, nullptr, B, N, T, C, H, 1,
+                   0, ws, dloss, &grads},
+                  stream);
 }
 
 extern "C" int sca_mwer_heads_fwd(const sca_decode_heads* heads, int G, const int* in_len, const int* tokens,
@@ -465,37 +506,17 @@ extern "C" int sca_mwer_heads_fwd(const sca_decode_heads* heads, int G, const in
                                   int N, int T, int C, int H, int R, int with_ref, const float* lm, float lm_weight,
                                   float length_bonus, float posterior_scale, float* loglik, float* posterior,
                                   int* errors, int* ref_valid, float* risk, float* loss, float* ws, void* stream) {
-  bool ok = heads && mwer_dims_ok(G, B, N, T, C, H, R) && in_len && tokens && out_len && count && ref && ref_len &&
-            lm_weight - lm_weight == 0.0f && length_bonus - length_bonus == 0.0f &&
-            posterior_scale == posterior_scale && loglik && posterior && errors && ref_valid && risk && loss && ws;
-  for (int g = 0; ok && g < G; ++g) ok = heads->logits[g] != nullptr;
-  if (!ok) {
-    sca_set_error("sca_mwer_heads_fwd: " MWER_HEADS_LIMITS);
-    return SCA_ERR_ARG;
-  }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const MwDims d = mw_dims(G, B, N, T, C, H, R, with_ref, 1);
-  mwer_fwd_launch(ctc_heads_of(heads, G), heads, G, in_len, tokens, out_len, count, ref, ref_len, d,
-                  MwPrior{lm, lm_weight, length_bonus}, posterior_scale, loglik, posterior, errors, ref_valid, risk,
-                  loss, ws, st);
-  return sca_launch_status("sca_mwer_heads_fwd");
+  return mwer_fwd({"sca_mwer_heads_fwd", true, heads, G, in_len, tokens, out_len, count, ref, ref_len, B, N, T, C, H, R,
+                   with_ref, ws, nullptr, nullptr, {lm, lm_weight, length_bonus}, posterior_scale, loglik, posterior,
+                   errors, ref_valid, risk, loss},
+                  stream);
 }
 
 extern "C" int sca_mwer_heads_bwd(const sca_decode_heads* heads, int G, const int* in_len, const int* tokens,
                                   const int* out_len, const int* count, const int* ref, const int* ref_len, int B,
                                   int N, int T, int C, int H, int R, int with_ref, const float* dloss, const float* ws,
                                   const sca_mwer_grads* dlogits, void* stream) {
-  bool ok = heads && dlogits && mwer_dims_ok(G, B, N, T, C, H, R) && in_len && tokens && out_len && count && ref &&
-            ref_len && dloss && ws;
-  for (int g = 0; ok && g < G; ++g) ok = heads->logits[g] != nullptr && dlogits->dlogits[g] != nullptr;
-  if (!ok) {
-    sca_set_error("sca_mwer_heads_bwd: " MWER_HEADS_LIMITS);
-    return SCA_ERR_ARG;
-  }
-  MwGrads grads = {};
-  for (int g = 0; g < SCA_EVAL_MAX_HEADS; ++g) grads.dx[g] = dlogits->dlogits[g < G ? g : 0];
-  const MwDims d = mw_dims(G, B, N, T, C, H, R, with_ref, 1);
-  hipLaunchKernelGGL(mwer_grad_kernel, dim3(T, d.P), dim3(MW_GRAD_THREADS), 0, reinterpret_cast<hipStream_t>(stream),
-                     ctc_heads_of(heads, G), in_len, tokens, out_len, count, ref, ref_len, d, ws, dloss, grads);
-  return sca_launch_status("sca_mwer_heads_bwd");
+  return mwer_bwd({"sca_mwer_heads_bwd", true, heads, G, in_len, tokens, out_len, count, ref, ref_len, B, N, T, C, H, R,
+                   with_ref, ws, dloss, dlogits},
+                  stream);
 }

@@ -1,15 +1,15 @@
 """Minimum word error rate (MWER) training on the device: the expected number of errors of the
 n-best hypotheses of a clip under the model's own posterior over that list — exact CTC
 likelihoods, error counts from the project's WER alignment — as a differentiable loss
-(`sca_mwer_fwd` / `sca_mwer_bwd`; the semantics are the header's, include/scatten.h).  The
-reference has none of this.
+(`sca_mwer_heads_fwd` / `sca_mwer_heads_bwd`; the semantics are the header's, include/scatten.h).
+The reference has none of this.
 
-* `MWERLossOp` — the autograd Function over fp32 logits (B, T, C) and int32 device tensors.
-* `MWERHeadsLossOp` — the same over the logits of G heads in one call (`sca_mwer_heads_fwd` /
-  `sca_mwer_heads_bwd`), optionally with each clip's reference as one more entry of its list and
-  with the bigram gloss model's prior inside the posterior.
-* `mwer_loss` — the validated entry point: decodes the detached logits into an uncollapsed
-  n-best list (`ctc_decode_nbest_device`, or the fused search) unless the caller hands one over.
+* `MWERLossOp` — the one autograd Function: fp32 logits (B, T, C) of G heads in one call and int32
+  device tensors, optionally with each clip's reference as one more entry of its list and with
+  the bigram gloss model's prior inside the posterior.  A single tensor is its G = 1 call.
+* `mwer_loss` — the validated entry point, for one tensor or a sequence of them: decodes the
+  detached logits into an uncollapsed n-best list (the plain search, or the fused one) unless
+  the caller hands one over.
 * `MWER` — the validated spec that `train_step(..., mwer=)` and `BucketedTrainStep(..., mwer=)`
   take; `mwer_guard` is the scalar they hand to `FusedAdam.step`.
 
@@ -26,49 +26,10 @@ from .decode import MAX_BEAM, WER_MAX_LEN, _check_lengths, _check_logits, check_
 from .heads import _dev_i32
 from .model import _LOGITS
 from .nbest import (MAX_CLASSES, MAX_HEADS, BigramLM, _check_beam, _check_fusion, _check_nbest, _finite,
-                    _fusion_table, ctc_decode_fused_nbest_device, ctc_decode_fused_nbest_heads_device,
-                    ctc_decode_nbest_device, ctc_decode_nbest_heads_device)
+                    _fusion_table, _nbest_decode)
 
 
 class MWERLossOp(Function):
-    """(loss, loglik, posterior, errors, risk) of `sca_mwer_fwd` on batch-major fp32 logits
-    (B, T, C); in_len (B), tokens (B, N, H), out_len (B, N), count (B), ref (B, R), ref_len (B)
-    int32 device tensors.  Only `loss` is differentiable; the workspace (row statistics, alpha,
-    beta, the gradient weights) is kept for the backward."""
-
-    @staticmethod
-    def forward(ctx, logits, in_len, tokens, out_len, count, ref, ref_len, posterior_scale):
-        x = logits.contiguous()
-        L.require_device(x)
-        B, T, C = x.shape
-        N, H = tokens.shape[1], tokens.shape[2]
-        lib = L.lib()
-        ws = x.new_empty(max(lib.sca_mwer_workspace_floats(B, N, T, H), 1))
-        loss = x.new_empty(())
-        loglik, posterior = x.new_empty(B, N), x.new_empty(B, N)
-        errors = torch.empty(B, N, dtype=torch.int32, device=x.device)
-        risk = x.new_empty(B)
-        L.check(lib.sca_mwer_fwd(L.ptr(x), L.ptr(in_len), L.ptr(tokens), L.ptr(out_len), L.ptr(count), L.ptr(ref),
-                                 L.ptr(ref_len), B, N, T, C, H, ref.shape[1], posterior_scale, L.ptr(loglik),
-                                 L.ptr(posterior), L.ptr(errors), L.ptr(risk), L.ptr(loss), L.ptr(ws),
-                                 L.stream_handle()), "sca_mwer_fwd")
-        ctx.save_for_backward(x, in_len, tokens, out_len, count, ws)
-        ctx.mark_non_differentiable(loglik, posterior, errors, risk)
-        return loss, loglik, posterior, errors, risk
-
-    @staticmethod
-    def backward(ctx, dloss, *_):
-        x, in_len, tokens, out_len, count, ws = ctx.saved_tensors
-        B, T, C = x.shape
-        dloss = dloss.contiguous() if dloss is not None else x.new_zeros(())
-        dx = torch.empty_like(x)
-        L.check(L.lib().sca_mwer_bwd(L.ptr(x), L.ptr(in_len), L.ptr(tokens), L.ptr(out_len), L.ptr(count), B,
-                                     tokens.shape[1], T, C, tokens.shape[2], L.ptr(dloss), L.ptr(ws), L.ptr(dx),
-                                     L.stream_handle()), "sca_mwer_bwd")
-        return dx, None, None, None, None, None, None, None
-
-
-class MWERHeadsLossOp(Function):
     """(loss (G), loglik, posterior, errors (G, B, M), ref_valid (G, B), risk (G, B)) of
     `sca_mwer_heads_fwd` on the G batch-major fp32 logits `*logits`, each (B, T, C); with
     `grouped=False` (one tensor) the results have no head axis and `loss` is 0-dim, so that the
@@ -91,7 +52,7 @@ class MWERHeadsLossOp(Function):
         lib, x = L.lib(), xs[0]
         ws = x.new_empty(max(lib.sca_mwer_heads_workspace_floats(G, B, N, T, H, R, int(with_ref)), 1))
         if not grouped and G != 1:
-            raise RuntimeError("MWERHeadsLossOp: grouped=False takes one logits tensor")
+            raise RuntimeError("MWERLossOp: grouped=False takes one logits tensor")
         lead = (G, B) if grouped else (B,)
         loss = x.new_empty(lead[:-1])
         loglik, posterior = x.new_empty(lead + (M,)), x.new_empty(lead + (M,))
@@ -107,6 +68,9 @@ class MWERHeadsLossOp(Function):
         ctx.save_for_backward(in_len, tokens, out_len, count, ref, ref_len, ws, *xs)
         ctx.with_ref = int(with_ref)
         ctx.mark_non_differentiable(loglik, posterior, errors, ref_valid, risk)
+        # the backward reads dloss alone: without this autograd fills one zero tensor per detail
+        # first, five small launches in every backward
+        ctx.set_materialize_grads(False)
         return loss, loglik, posterior, errors, ref_valid, risk
 
     @staticmethod
@@ -169,65 +133,6 @@ def _check_prior(lm, lm_weight, length_bonus, fusion, num_classes, what):
     return lm, lw, lb
 
 
-def _mwer_loss_heads(xs, grouped, input_lengths, gloss_labels, gloss_lengths, nbest, beam_size, nbest_size,
-                     posterior_scale, return_details, reference, lm, lm_weight, length_bonus, fusion):
-    """`mwer_loss` through `MWERHeadsLossOp`: the G tensors `xs` (validated by the caller) in one
-    call; `grouped=False` is a single tensor's call, whose results lose the head axis."""
-    what = "mwer_loss"
-    G = len(xs)
-    B, T, C = xs[0].shape
-    if not 1 <= C <= MAX_CLASSES:
-        raise ValueError(f"{what}: logits of {C} classes are outside [1, {MAX_CLASSES}]")
-    if G * B > 65535:
-        raise ValueError(f"{what}: {G} heads of {B} clips exceed the 65535 (head, clip) pairs of one call")
-    if not isinstance(reference, bool):
-        raise ValueError(f"{what}: reference must be a bool, got {reference!r}")
-    ps = _finite("posterior_scale", posterior_scale, what)
-    lm, lw, lb = _check_prior(lm, lm_weight, length_bonus, fusion, C, what)
-    il = _check_lengths(input_lengths, B, T)
-    labels = torch.as_tensor(gloss_labels)
-    _check_refs(labels, gloss_lengths, B, C, what)
-    if nbest is None:
-        beam, n = _check_beam(beam_size, nbest_size)
-        if T > WER_MAX_LEN:
-            raise ValueError(f"{what}: hypotheses over {T} logit frames exceed the WER kernel's {WER_MAX_LEN} tokens")
-    else:
-        if fusion:
-            raise ValueError(f"{what}: fusion=True decodes the list itself; it does not go with nbest=")
-        Gn, Bn, _, H = _check_nbest(nbest, what)
-        if nbest.tokens.dim() != (4 if grouped else 3) or Bn != B or Gn != G:
-            form = f"the {G} heads', tokens (G = {G}, B = {B}, N, H)" if grouped else \
-                f"a single head's, tokens (B = {B}, N, H)"
-            raise RuntimeError(f"{what}: the list must be {form}, got {tuple(nbest.tokens.shape)}")
-        if H > WER_MAX_LEN:
-            raise ValueError(f"{what}: hypotheses of up to {H} tokens exceed the WER kernel's {WER_MAX_LEN}")
-    check_on_device(None, xs[0])
-    dev = xs[0].device
-    table = _fusion_table(lm, dev, what)
-    in_len = _dev_i32(il, dev)
-    if nbest is None:
-        logits = xs if grouped else xs[0]
-        if fusion:
-            decode = ctc_decode_fused_nbest_heads_device if grouped else ctc_decode_fused_nbest_device
-            nbest = decode(logits, in_len, beam, lm, lw, lb, nbest=n, collapse_repeats=False)
-        else:
-            decode = ctc_decode_nbest_heads_device if grouped else ctc_decode_nbest_device
-            nbest = decode(logits, in_len, beam, n, collapse_repeats=False)
-    else:
-        check_on_device(what, nbest.tokens, nbest.lengths, nbest.count)
-    xs = [x if x.dtype == torch.float32 else x.float() for x in xs]
-    loss, *rest = MWERHeadsLossOp.apply(
-        in_len, _dev_i32(nbest.tokens, dev), _dev_i32(nbest.lengths, dev), _dev_i32(nbest.count, dev),
-        _dev_i32(labels, dev), _dev_i32(torch.as_tensor(gloss_lengths).reshape(-1), dev), ps, reference, table, lw, lb,
-        grouped, *xs)
-    if not return_details:
-        return loss
-    details = dict(zip(("loglik", "posterior", "errors", "ref_valid", "risk"), rest))
-    if not (grouped or reference):
-        del details["ref_valid"]
-    return loss, details
-
-
 def mwer_loss(gloss_logits, input_lengths, gloss_labels, gloss_lengths, nbest=None, beam_size=5, nbest_size=None,
               posterior_scale=1.0, return_details=False, *, reference=False, lm=None, lm_weight=0.0,
               length_bonus=0.0, fusion=False):
@@ -260,19 +165,22 @@ def mwer_loss(gloss_logits, input_lengths, gloss_labels, gloss_lengths, nbest=No
     and details with a leading G axis, `ref_valid` (G, B) among them.  Head g is bitwise the
     single-tensor call on it."""
     what = "mwer_loss"
-    if isinstance(gloss_logits, (list, tuple)):
-        return _mwer_loss_heads(check_heads(gloss_logits, what), True, input_lengths, gloss_labels, gloss_lengths,
-                                nbest, beam_size, nbest_size, posterior_scale, return_details, reference, lm,
-                                lm_weight, length_bonus, fusion)
-    _check_logits(gloss_logits)
-    if reference or fusion or lm is not None or lm_weight != 0.0 or length_bonus != 0.0:
-        return _mwer_loss_heads([gloss_logits], False, input_lengths, gloss_labels, gloss_lengths, nbest, beam_size,
-                                nbest_size, posterior_scale, return_details, reference, lm, lm_weight, length_bonus,
-                                fusion)
-    B, T, C = gloss_logits.shape
+    grouped = isinstance(gloss_logits, (list, tuple))
+    if grouped:
+        xs = check_heads(gloss_logits, what)
+    else:
+        _check_logits(gloss_logits)
+        xs = [gloss_logits]
+    G = len(xs)
+    B, T, C = xs[0].shape
     if not 1 <= C <= MAX_CLASSES:
         raise ValueError(f"{what}: logits of {C} classes are outside [1, {MAX_CLASSES}]")
+    if G * B > 65535:
+        raise ValueError(f"{what}: {G} heads of {B} clips exceed the 65535 (head, clip) pairs of one call")
+    if not isinstance(reference, bool):
+        raise ValueError(f"{what}: reference must be a bool, got {reference!r}")
     ps = _finite("posterior_scale", posterior_scale, what)
+    lm, lw, lb = _check_prior(lm, lm_weight, length_bonus, fusion, C, what)
     il = _check_lengths(input_lengths, B, T)
     labels = torch.as_tensor(gloss_labels)
     _check_refs(labels, gloss_lengths, B, C, what)
@@ -281,26 +189,34 @@ def mwer_loss(gloss_logits, input_lengths, gloss_labels, gloss_lengths, nbest=No
         if T > WER_MAX_LEN:
             raise ValueError(f"{what}: hypotheses over {T} logit frames exceed the WER kernel's {WER_MAX_LEN} tokens")
     else:
-        G, Bn, _, H = _check_nbest(nbest, what)
-        if nbest.tokens.dim() != 3 or Bn != B:
-            raise RuntimeError(f"{what}: the list must be a single head's, tokens (B = {B}, N, H), got "
-                               f"{tuple(nbest.tokens.shape)}")
+        if fusion:
+            raise ValueError(f"{what}: fusion=True decodes the list itself; it does not go with nbest=")
+        Gn, Bn, _, H = _check_nbest(nbest, what)
+        if nbest.tokens.dim() != (4 if grouped else 3) or Bn != B or Gn != G:
+            form = f"the {G} heads', tokens (G = {G}, B = {B}, N, H)" if grouped else \
+                f"a single head's, tokens (B = {B}, N, H)"
+            raise RuntimeError(f"{what}: the list must be {form}, got {tuple(nbest.tokens.shape)}")
         if H > WER_MAX_LEN:
             raise ValueError(f"{what}: hypotheses of up to {H} tokens exceed the WER kernel's {WER_MAX_LEN}")
-    check_on_device(None, gloss_logits)
-    dev = gloss_logits.device
+    check_on_device(None, xs[0])
+    dev = xs[0].device
+    table = _fusion_table(lm, dev, what)
     in_len = _dev_i32(il, dev)
     if nbest is None:
-        nbest = ctc_decode_nbest_device(gloss_logits, in_len, beam, n, collapse_repeats=False)
+        nbest = _nbest_decode(xs, grouped, in_len, beam, n, False, (lm, lw, lb) if fusion else None, what)
     else:
         check_on_device(what, nbest.tokens, nbest.lengths, nbest.count)
-    x = gloss_logits if gloss_logits.dtype == torch.float32 else gloss_logits.float()
-    loss, loglik, posterior, errors, risk = MWERLossOp.apply(
-        x, in_len, _dev_i32(nbest.tokens, dev), _dev_i32(nbest.lengths, dev), _dev_i32(nbest.count, dev),
-        _dev_i32(labels, dev), _dev_i32(torch.as_tensor(gloss_lengths).reshape(-1), dev), ps)
-    if return_details:
-        return loss, {"loglik": loglik, "posterior": posterior, "errors": errors, "risk": risk}
-    return loss
+    xs = [x if x.dtype == torch.float32 else x.float() for x in xs]
+    loss, *rest = MWERLossOp.apply(
+        in_len, _dev_i32(nbest.tokens, dev), _dev_i32(nbest.lengths, dev), _dev_i32(nbest.count, dev),
+        _dev_i32(labels, dev), _dev_i32(torch.as_tensor(gloss_lengths).reshape(-1), dev), ps, reference, table, lw, lb,
+        grouped, *xs)
+    if not return_details:
+        return loss
+    details = dict(zip(("loglik", "posterior", "errors", "ref_valid", "risk"), rest))
+    if not (grouped or reference):
+        del details["ref_valid"]
+    return loss, details
 
 
 class MWER:

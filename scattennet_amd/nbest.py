@@ -53,6 +53,24 @@ def _check_beam(beam_size, nbest):
     return beam, n
 
 
+def _nbest_decode(xs, grouped, input_lengths, beam_size, nbest, collapse_repeats, fusion=None, what=None):
+    """The n-best decode behind the four wrappers below, `rescored_decode` and `mwer_loss`: `xs`
+    is the validated list of logits tensors (one, with `grouped=False`, for the single-tensor
+    form of the result); `fusion`: None for the plain search, or (lm, lm_weight, length_bonus)
+    for the fused one, validated here under the name `what`."""
+    beam, n = _check_beam(beam_size, nbest)
+    B, T, C = xs[0].shape
+    il = _check_lengths(input_lengths, B, T)
+    lm, lw, lb = None, 0.0, 0.0
+    if fusion is not None:
+        lm = fusion[0]
+        lw, lb = _check_fusion(*fusion, C, what)
+    check_on_device(None, xs[0])
+    table = _fusion_table(lm, xs[0].device, what)
+    return NBest(*_decoder("nbest" if fusion is None else "fused", _dev_i32(il, xs[0].device), beam, n,
+                           bool(collapse_repeats), lw, lb, grouped, *xs, table=table))
+
+
 def ctc_decode_nbest_device(gloss_logits, input_lengths, beam_size, nbest=None, collapse_repeats=True):
     """The `nbest` (default: `beam_size`) best labellings of `ctc_decode_device`'s search over
     batch-major logits (B, T, C), as an `NBest` of device tensors: tokens (B, N, T) int32 padded
@@ -61,12 +79,7 @@ def ctc_decode_nbest_device(gloss_logits, input_lengths, beam_size, nbest=None, 
     `ctc_decode_device(..., collapse_repeats=False)`; with it, entries that collapse to one
     labelling are merged (logaddexp) and the list re-sorted.  No host sync; capturable."""
     _check_logits(gloss_logits)
-    B, T, _ = gloss_logits.shape
-    beam, n = _check_beam(beam_size, nbest)
-    il = _check_lengths(input_lengths, B, T)
-    check_on_device(None, gloss_logits)
-    return NBest(*_decoder("nbest", _dev_i32(il, gloss_logits.device), beam, n, bool(collapse_repeats), 0.0, 0.0,
-                           False, gloss_logits))
+    return _nbest_decode([gloss_logits], False, input_lengths, beam_size, nbest, collapse_repeats)
 
 
 def ctc_decode_nbest_heads_device(logits_list, input_lengths, beam_size, nbest=None, collapse_repeats=True):
@@ -74,11 +87,7 @@ def ctc_decode_nbest_heads_device(logits_list, input_lengths, beam_size, nbest=N
     of tokens (G, B, N, T), lengths (G, B, N), scores (G, B, N), count (G, B); row g is bitwise
     the single-head call's for `logits_list[g]`."""
     xs = check_heads(logits_list, "ctc_decode_nbest_heads")
-    beam, n = _check_beam(beam_size, nbest)
-    B, T, _ = xs[0].shape
-    il = _check_lengths(input_lengths, B, T)
-    check_on_device(None, xs[0])
-    return NBest(*_decoder("nbest", _dev_i32(il, xs[0].device), beam, n, bool(collapse_repeats), 0.0, 0.0, True, *xs))
+    return _nbest_decode(xs, True, input_lengths, beam_size, nbest, collapse_repeats)
 
 
 def nbest_lists(tokens, lengths, values, count, extra=None, order=None):
@@ -143,32 +152,18 @@ def ctc_decode_fused_nbest_device(gloss_logits, input_lengths, beam_size, lm, lm
     format: `scores` are acoustic log-probabilities, so `rescore_nbest_device` with the same
     `lm`, `lm_weight` and `length_bonus` gives the totals the search ranked by.  With weight 0
     and bonus 0 the result is bitwise `ctc_decode_nbest_device`'s.  No host sync; capturable."""
-    what = "ctc_decode_fused_nbest"
     _check_logits(gloss_logits)
-    B, T, C = gloss_logits.shape
-    beam, n = _check_beam(beam_size, nbest)
-    il = _check_lengths(input_lengths, B, T)
-    lw, lb = _check_fusion(lm, lm_weight, length_bonus, C, what)
-    check_on_device(None, gloss_logits)
-    table = _fusion_table(lm, gloss_logits.device, what)
-    return NBest(*_decoder("fused", _dev_i32(il, gloss_logits.device), beam, n, bool(collapse_repeats), lw, lb, False,
-                           gloss_logits, table=table))
+    return _nbest_decode([gloss_logits], False, input_lengths, beam_size, nbest, collapse_repeats,
+                         (lm, lm_weight, length_bonus), "ctc_decode_fused_nbest")
 
 
 def ctc_decode_fused_nbest_heads_device(logits_list, input_lengths, beam_size, lm, lm_weight=0.0, length_bonus=0.0,
                                         nbest=None, collapse_repeats=True):
     """`ctc_decode_fused_nbest_device` over the G heads of one forward in one grouped call, shaped
     like `ctc_decode_nbest_heads_device`'s result; row g is bitwise the single-head call's."""
-    what = "ctc_decode_fused_nbest_heads"
     xs = check_heads(logits_list, "ctc_decode_nbest_heads")
-    beam, n = _check_beam(beam_size, nbest)
-    B, T, C = xs[0].shape
-    il = _check_lengths(input_lengths, B, T)
-    lw, lb = _check_fusion(lm, lm_weight, length_bonus, C, what)
-    check_on_device(None, xs[0])
-    table = _fusion_table(lm, xs[0].device, what)
-    return NBest(*_decoder("fused", _dev_i32(il, xs[0].device), beam, n, bool(collapse_repeats), lw, lb, True, *xs,
-                           table=table))
+    return _nbest_decode(xs, True, input_lengths, beam_size, nbest, collapse_repeats, (lm, lm_weight, length_bonus),
+                         "ctc_decode_fused_nbest_heads")
 
 
 def ctc_decode_fused_nbest(gloss_logits, beam_size, input_lengths, lm, lm_weight=0.0, length_bonus=0.0, nbest=None,
@@ -406,11 +401,9 @@ def rescored_decode(logits_list, input_lengths, beam_size, rescoring, what="resc
     No host read."""
     xs = check_heads(logits_list, "ctc_decode_nbest_heads")
     check_rescoring(rescoring, beam_size, what, xs[0].shape[2], xs[0].shape[1])
-    if rescoring.fusion:
-        nb = ctc_decode_fused_nbest_heads_device(xs, input_lengths, beam_size, rescoring.lm, rescoring.lm_weight,
-                                                 rescoring.length_bonus, rescoring.nbest)
-    else:
-        nb = ctc_decode_nbest_heads_device(xs, input_lengths, beam_size, rescoring.nbest)
+    fusion = (rescoring.lm, rescoring.lm_weight, rescoring.length_bonus) if rescoring.fusion else None
+    nb = _nbest_decode(xs, True, input_lengths, beam_size, rescoring.nbest, True, fusion,
+                       "ctc_decode_fused_nbest_heads")
     total, posterior, order = rescore_nbest_device(nb, rescoring.lm, rescoring.lm_weight, rescoring.length_bonus,
                                                    rescoring.posterior_scale)
     out = {"nbest_tokens": nb.tokens, "nbest_lengths": nb.lengths, "nbest_totals": total,

@@ -1,84 +1,41 @@
-"""GPU parity of the MWER loss (sca_mwer_fwd / sca_mwer_bwd, scattennet_amd/mwer.py) against
-the float64 restatement of tests/mwer_ref.py, under the project's bound of 1e-3 (golden_util.
-rel_err): the kernels on the four n-best cases and on a hand-built case, the decode-and-loss
-entry point, capture, and the training steps on tests/golden/model_small.  Every test prints
-the figures it asserts."""
-import copy
-
+"""GPU parity of the MWER loss (scattennet_amd/mwer.py: one op over sca_mwer_heads_fwd /
+sca_mwer_heads_bwd) against the float64 restatement of tests/mwer_ref.py, under the project's
+bound of 1e-3 (golden_util.rel_err); integers are compared as integers.  The kernels on the four
+n-best cases in all four modes (plain, and with the reference slot and the prior, whose other
+tests are tests/test_gpu_mwer_ext.py's; the helpers of both are tests/mwer_gpu.py) and on a
+hand-built case, the single-tensor C entry points sca_mwer_fwd / sca_mwer_bwd against the one
+path, the decode-and-loss entry point, capture, and the training steps on
+tests/golden/model_small.  Every test prints the figures it asserts."""
 import numpy as np
 import pytest
 import torch
 
 from tests import mwer_ref as M
 from tests import nbest_ref as NR
-from tests.golden_util import close, load, rel_err
+from tests.golden_util import close, rel_err
+from tests.mwer_gpu import fx  # noqa: F401  (the fixture, by name)
+from tests.mwer_gpu import (IDS, MODES, SHAPES, TOL, _assert_parity, _bits, _build, _case, _case_run, _dev, _grads, _nbest,
+                            _run, _same, _trainer)
 
 pytestmark = pytest.mark.gpu
 
-TOL = 1e-3  # the project's relative bound
-SHAPES = list(NR.CASES)
-IDS = ["B%d_T%d_C%d_W%d_N%d" % s for s in SHAPES]
-
-
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return torch.device("cuda:0")
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _nbest(lists, N, H, dev, fill=0):
-    import scattennet_amd as S
-    tokens, out_len, count = M.pack_lists(lists, N, H, fill)
-    return S.NBest(torch.from_numpy(tokens).to(dev), torch.from_numpy(out_len).to(dev),
-                   torch.zeros(out_len.shape, device=dev), torch.from_numpy(count).to(dev))
-
-
-def _run(logits, in_len, lists, refs, N, H, dev, ps, fill=0):
-    """The op on host inputs: (loss, details, dlogits) as host tensors."""
-    import scattennet_amd as S
-    x = torch.from_numpy(np.asarray(logits, np.float32)).to(dev).requires_grad_(True)
-    ref, ref_len = M.pack_refs(refs)
-    loss, det = S.mwer_loss(x, torch.tensor(in_len), torch.from_numpy(ref), torch.from_numpy(ref_len),
-                            nbest=_nbest(lists, N, H, dev, fill), posterior_scale=ps, return_details=True)
-    loss.backward()
-    torch.cuda.synchronize()
-    return loss.detach().cpu(), {k: v.cpu() for k, v in det.items()}, x.grad.cpu()
-
-
-def _assert_parity(where, loss, det, dx, want):
-    """Every output against the restatement; returns the measured figures."""
-    ll, wl = det["loglik"].double().numpy(), want["loglik"]
-    assert np.array_equal(np.isneginf(ll), np.isneginf(wl)), (where, ll, wl)
-    fin = np.isfinite(wl)
-    figs = {"loglik": rel_err(torch.from_numpy(ll[fin]), torch.from_numpy(wl[fin])),
-            "posterior": rel_err(det["posterior"], torch.from_numpy(want["posterior"])),
-            "risk": rel_err(det["risk"], torch.from_numpy(want["risk"])),
-            "loss": rel_err(loss, torch.tensor(want["loss"])),
-            "dlogits": rel_err(dx, torch.from_numpy(want["dlogits"]))}
-    print(where, {k: f"{v:.3g}" for k, v in figs.items()})
-    assert np.array_equal(det["errors"].numpy().astype(np.int64), want["errors"]), where
-    for k, v in figs.items():
-        assert v < TOL, (where, k, v)
-    return figs
-
 
 # ------------------------------------------------------------------ 1: the kernels
+@pytest.mark.parametrize("mode", list(MODES))
 @pytest.mark.parametrize("shape", SHAPES, ids=IDS)
-def test_kernels_against_the_restatement(shape):
-    dev = _dev()
+def test_kernels_against_the_restatement(shape, mode):
     B, T, C, W, N = shape
-    logits, in_len, lists, refs = M.case_inputs(shape)
-    want = M.case_ref(shape)
-    for b in range(B):  # the conditions tests/test_mwer.py asserts on these inputs
-        if in_len[b] >= 1:
-            errs = want["errors"][b, :len(lists[b])]
-            assert errs.min() != errs.max() and np.abs(want["dlogits"][b]).max() >= 1e-3
-    loss, det, dx = _run(logits, in_len, lists, refs, N, T, dev, M.POSTERIOR_SCALE)
-    _assert_parity(IDS[SHAPES.index(shape)], loss, det, dx, want)
+    with_ref, table = MODES[mode]
+    (_, in_len, lists, _), want, _ = _case(shape, mode)
+    if mode == "plain":
+        for b in range(B):  # the conditions tests/test_mwer.py asserts on these inputs
+            if in_len[b] >= 1:
+                errs = want["errors"][b, :len(lists[b])]
+                assert errs.min() != errs.max() and np.abs(want["dlogits"][b]).max() >= 1e-3
+    loss, det, dx = _case_run(shape, mode)
+    assert det["loglik"].shape == (B, N + with_ref) and ("ref_valid" in det) == with_ref and loss.dim() == 0
+    _assert_parity(f"{IDS[SHAPES.index(shape)]} {mode}", loss, det, dx, want)
+    assert np.abs(want["dlogits"]).max() >= 1e-3  # not a vacuous case
     for b in range(B):
         assert not dx[b, in_len[b]:].any(), b  # rows past in_len are written as zeros
 
@@ -114,9 +71,9 @@ def test_hand_built_case():
     assert float(det["errors"][1, 3]) == 0 and np.isneginf(float(det["loglik"][1, 3]))
 
 
-def test_many_clips_take_the_grid_form_of_the_per_clip_kernel():
-    """B = 70 > 64: four clips per workgroup and the separate fixed-order sum over the clips."""
-    dev = _dev()
+# ------------------------------------------------------------------ 3: the grid form
+def _many_clips():
+    """B = 70, T = 5, C = 4, N = 3, lengths ragged from 0, lists of 1 to 3 entries."""
     rng = np.random.default_rng(11)
     B, T, C, N = 70, 5, 4, 3
     x = rng.normal(0.0, 2.0, (B, T, C)).astype(np.float32)
@@ -124,13 +81,71 @@ def test_many_clips_take_the_grid_form_of_the_per_clip_kernel():
     pool = [[1], [2, 3], [], [1, 1], [3, 2, 1], [2]]
     lists = [[pool[(b + k) % len(pool)] for k in range(1 + b % N)] for b in range(B)]
     refs = [pool[(b + 1) % len(pool)] for b in range(B)]
-    want = M.mwer(x, in_len, lists, refs, 1.0, n_max=N)
+    return x, in_len, lists, refs
+
+
+def test_many_clips_take_the_grid_form_of_the_per_clip_kernel():
+    """B = 70 > 64: four clips per workgroup and the separate fixed-order sum over the clips."""
+    dev = _dev()
+    x, in_len, lists, refs = _many_clips()
+    want = M.mwer(x, in_len, lists, refs, 1.0, n_max=3)
     assert np.abs(want["dlogits"]).max() >= 1e-3 and abs(want["loss"]) > 1e-3
-    loss, det, dx = _run(x, in_len, lists, refs, N, T, dev, 1.0, fill=-3)
+    loss, det, dx = _run(x, in_len, lists, refs, 3, 5, dev, 1.0, fill=-3)
     _assert_parity("B70", loss, det, dx, want)
 
 
-# ------------------------------------------------------------------ 3: end to end
+# ------------------------------------------------------------------ 4: the old entry points
+def _case_of(shape, fill):
+    logits, in_len, lists, refs = M.case_inputs(shape)
+    return logits, in_len, lists, refs, shape[4], shape[1], M.POSTERIOR_SCALE, fill
+
+
+# (logits, in_len, lists, refs, N, H, posterior_scale, fill): the smallest inputs that reach every
+# branch of the launcher behind sca_mwer_fwd / sca_mwer_bwd
+SINGLE_TENSOR_CASES = {
+    "fill_behind_count_and_lengths": lambda: _case_of((4, 12, 6, 8, 3), -5),
+    "ragged_lengths": lambda: _case_of((5, 16, 4, 8, 8), 0),
+    "N32_all_lanes_of_the_clip_kernel": lambda: _case_of((3, 20, 33, 32, 32), 0),
+    "hand_built_clamp_gate_unfit_entry_empty_reference": lambda: _hand_case() + (4, 10, 1.0, -7),
+    "B70_grid_form_and_loss_sum_kernel": lambda: _many_clips() + (3, 5, 1.0, -3),
+}
+
+
+@pytest.mark.parametrize("case", list(SINGLE_TENSOR_CASES))
+def test_single_tensor_entry_points_are_the_one_path(case):
+    """sca_mwer_workspace_floats / sca_mwer_fwd / sca_mwer_bwd, which no Python of the package
+    calls, through the library on device tensors: the loss, every detail and dlogits are bitwise
+    what `mwer_loss` (sca_mwer_heads_fwd / sca_mwer_heads_bwd at G = 1) gives."""
+    import scattennet_amd as S
+    from scattennet_amd import _lib as L
+    dev = _dev()
+    logits, in_len, lists, refs, N, H, ps, fill = SINGLE_TENSOR_CASES[case]()
+    B, T, C = logits.shape
+    nb = _nbest(lists, N, H, dev, fill)
+    il = torch.tensor(in_len, dtype=torch.int32, device=dev)
+    ref, ref_len = (torch.from_numpy(a).to(dev) for a in M.pack_refs(refs))
+    x = torch.from_numpy(logits).to(dev).requires_grad_(True)
+    loss, det = S.mwer_loss(x, il, ref, ref_len, nbest=nb, posterior_scale=ps, return_details=True)
+    loss.backward()
+    assert loss.dim() == 0 and set(det) == {"loglik", "posterior", "errors", "risk"}
+    lib, xd = L.lib(), x.detach()
+    ws = xd.new_empty(max(lib.sca_mwer_workspace_floats(B, N, T, H), 1))
+    old_loss, dloss, dx = xd.new_empty(()), xd.new_ones(()), torch.empty_like(xd)
+    old = {"loglik": xd.new_empty(B, N), "posterior": xd.new_empty(B, N),
+           "errors": torch.empty(B, N, dtype=torch.int32, device=dev), "risk": xd.new_empty(B)}
+    L.check(lib.sca_mwer_fwd(L.ptr(xd), L.ptr(il), L.ptr(nb.tokens), L.ptr(nb.lengths), L.ptr(nb.count), L.ptr(ref),
+                             L.ptr(ref_len), B, N, T, C, H, ref.shape[1], ps, L.ptr(old["loglik"]),
+                             L.ptr(old["posterior"]), L.ptr(old["errors"]), L.ptr(old["risk"]), L.ptr(old_loss),
+                             L.ptr(ws), L.stream_handle()), "sca_mwer_fwd")
+    L.check(lib.sca_mwer_bwd(L.ptr(xd), L.ptr(il), L.ptr(nb.tokens), L.ptr(nb.lengths), L.ptr(nb.count), B, N, T, C, H,
+                             L.ptr(dloss), L.ptr(ws), L.ptr(dx), L.stream_handle()), "sca_mwer_bwd")
+    torch.cuda.synchronize()
+    _same((old_loss, old, dx), (loss.detach(), det, x.grad), case)
+    print(case, "loss", float(old_loss), "max |dlogits|", float(dx.abs().max()))
+    assert dx.abs().max() > 0
+
+
+# ------------------------------------------------------------------ 5: end to end
 @pytest.mark.parametrize("shape", SHAPES, ids=IDS)
 def test_decode_and_loss_against_the_restatement(shape):
     import scattennet_amd as S
@@ -148,7 +163,7 @@ def test_decode_and_loss_against_the_restatement(shape):
                    x.grad.cpu(), want)
 
 
-# ------------------------------------------------------------------ 4: capture
+# ------------------------------------------------------------------ 6: capture
 def test_captured_forward_and_backward_replay_bitwise():
     import scattennet_amd as S
     dev = _dev()
@@ -187,33 +202,9 @@ def test_captured_forward_and_backward_replay_bitwise():
         assert got[5].abs().max() > 0
 
 
-# ------------------------------------------------------------------ 5: the steps
+# ------------------------------------------------------------------ 7: the steps
 HEAD = "fuse_coord_gloss_logits"
 BEAM, NBEST, WEIGHT = NR.MODEL_BEAM, 3, 0.5
-ADAM = dict(lr=0.0, betas=(0.9, 0.998), weight_decay=0.0)  # lr 0: every step sees the same parameters
-
-
-@pytest.fixture(scope="module")
-def fx():
-    return load("model_small", "manifest_model.json")
-
-
-def _build(fx, dev):
-    """The dropout-free configuration of the existing step tests: the fixture model in eval mode."""
-    import scattennet_amd as S
-    m = S.MSCA_Net(copy.deepcopy(fx["meta"]["cfg"]), list(range(fx["meta"]["vocab"])), device="cuda")
-    m.load_state_dict({k: v for k, v in fx["param"].items()}, strict=True)
-    return m.to(dev).eval()
-
-
-def _trainer(fx, dev):
-    import scattennet_amd as S
-    model = _build(fx, dev)
-    return model, S.FusedAdam(model.parameters(), **ADAM)
-
-
-def _grads(model):
-    return {k: (None if p.grad is None else p.grad.detach().cpu().clone()) for k, p in model.named_parameters()}
 
 
 def _spec():

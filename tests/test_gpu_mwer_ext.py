@@ -1,118 +1,25 @@
-"""GPU parity of the extended MWER loss (sca_mwer_heads_fwd / sca_mwer_heads_bwd: the reference
-as one more entry of the list, the gloss model's prior inside the posterior, several heads per
-call) against the float64 restatement of tests/mwer_ext_ref.py, under the project's bound of 1e-3
-(golden_util.rel_err); integers are compared as integers.  The kernels on the four n-best cases
-and on a hand-built case, the reference slot's likelihood against the CTC loss, the bitwise
-conditions of the header, the grid form of the per-clip kernel, and the training steps on
-tests/golden/model_small.  Every test prints the figures it asserts."""
-import copy
-import functools
-
+"""GPU parity of the extended MWER loss (the reference as one more entry of the list, the gloss
+model's prior inside the posterior, several heads per call) against the float64 restatement of
+tests/mwer_ref.py, under the project's bound of 1e-3 (golden_util.rel_err); integers are compared
+as integers.  The helpers are tests/mwer_gpu.py's and the kernels on the four n-best cases in
+every mode tests/test_gpu_mwer.py's; here are the reference slot's likelihood against the CTC
+loss, a hand-built case, the bitwise conditions of the header, the grid form of the per-clip
+kernel, and the training steps on tests/golden/model_small.  Every test prints the figures it asserts."""
 import numpy as np
 import pytest
 import torch
 
-from tests import mwer_ext_ref as X
 from tests import mwer_ref as M
 from tests import nbest_ref as NR
-from tests.golden_util import close, load, rel_err
+from tests.golden_util import close, rel_err
+from tests.mwer_gpu import fx  # noqa: F401  (the fixture, by name)
+from tests.mwer_gpu import (IDS, SHAPES, TOL, _assert_parity, _bits, _build, _case_run, _dev, _grads, _lm, _run,
+                            _same, _trainer)
 
 pytestmark = pytest.mark.gpu
 
-TOL = 1e-3  # the project's relative bound
-SHAPES = list(NR.CASES)
-IDS = ["B%d_T%d_C%d_W%d_N%d" % s for s in SHAPES]
-MODES = {"reference+table": (True, True), "reference": (True, False), "table": (False, True)}
 
-
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return torch.device("cuda:0")
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _nbest(lists, N, H, dev, fill=0):
-    """An NBest from host lists: one head's (lists[b]) or, for a list of G of them, the heads' form."""
-    import scattennet_amd as S
-    if isinstance(lists, tuple):
-        tokens, out_len, count = (np.stack(a) for a in zip(*(M.pack_lists(l, N, H, fill) for l in lists)))
-    else:
-        tokens, out_len, count = M.pack_lists(lists, N, H, fill)
-    return S.NBest(torch.from_numpy(tokens).to(dev), torch.from_numpy(out_len).to(dev),
-                   torch.zeros(out_len.shape, device=dev), torch.from_numpy(count).to(dev))
-
-
-def _lm(table, dev):
-    import scattennet_amd as S
-    return None if table is None else S.BigramLM(torch.from_numpy(np.asarray(table)), dev)
-
-
-def _run(logits, in_len, lists, refs, N, H, dev, ps, fill=0, lm=None, **kw):
-    """The op on host inputs: (loss, details, dlogits) as host tensors.  `logits` / `lists`: one
-    head's, or tuples of G of them (dlogits is then a list)."""
-    import scattennet_amd as S
-    grouped = isinstance(logits, tuple)
-    xs = [torch.from_numpy(np.asarray(x, np.float32)).to(dev).requires_grad_(True) for x in (logits if grouped else (logits,))]
-    ref, ref_len = M.pack_refs(refs)
-    loss, det = S.mwer_loss(xs if grouped else xs[0], torch.tensor(in_len), torch.from_numpy(ref),
-                            torch.from_numpy(ref_len), nbest=_nbest(lists, N, H, dev, fill), posterior_scale=ps,
-                            return_details=True, lm=_lm(lm, dev), **kw)
-    loss.sum().backward()
-    torch.cuda.synchronize()
-    grads = [x.grad.cpu() for x in xs]
-    return loss.detach().cpu(), {k: v.cpu() for k, v in det.items()}, grads if grouped else grads[0]
-
-
-def _assert_parity(where, loss, det, dx, want):
-    """Every output against the restatement; returns the measured figures."""
-    ll, wl = det["loglik"].double().numpy(), want["loglik"]
-    assert np.array_equal(np.isneginf(ll), np.isneginf(wl)), (where, ll, wl)
-    fin = np.isfinite(wl)
-    figs = {"loglik": rel_err(torch.from_numpy(ll[fin]), torch.from_numpy(wl[fin])),
-            "posterior": rel_err(det["posterior"], torch.from_numpy(want["posterior"])),
-            "risk": rel_err(det["risk"], torch.from_numpy(want["risk"])),
-            "loss": rel_err(loss, torch.tensor(want["loss"])),
-            "dlogits": rel_err(dx, torch.from_numpy(want["dlogits"]))}
-    print(where, {k: f"{v:.3g}" for k, v in figs.items()}, "loss", want["loss"])
-    assert np.array_equal(det["errors"].numpy().astype(np.int64), want["errors"]), where
-    if "ref_valid" in det:
-        assert np.array_equal(det["ref_valid"].numpy().astype(np.int64), want["ref_valid"]), where
-    for k, v in figs.items():
-        assert v < TOL, (where, k, v)
-    return figs
-
-
-# ------------------------------------------------------------------ 1: the kernels
-@functools.lru_cache(maxsize=None)
-def _case_run(shape, mode):
-    """One GPU run of a case in a mode, shared by the tests that read it."""
-    dev = _dev()
-    B, T, C, W, N = shape
-    with_ref, table = MODES[mode]
-    logits, in_len, lists, refs = X.case_inputs(shape)
-    kw = X.prior_kwargs(shape, table)
-    return _run(logits, in_len, lists, refs, N, T, dev, M.POSTERIOR_SCALE, reference=with_ref, **kw)
-
-
-@pytest.mark.parametrize("mode", list(MODES))
-@pytest.mark.parametrize("shape", SHAPES, ids=IDS)
-def test_kernels_against_the_restatement(shape, mode):
-    B, T, C, W, N = shape
-    with_ref, table = MODES[mode]
-    _, in_len, _, _ = X.case_inputs(shape)
-    want = X.case_ref(shape, with_ref, table)
-    loss, det, dx = _case_run(shape, mode)
-    assert det["loglik"].shape == (B, N + with_ref) and ("ref_valid" in det) == with_ref
-    _assert_parity(f"{IDS[SHAPES.index(shape)]} {mode}", loss, det, dx, want)
-    assert np.abs(want["dlogits"]).max() >= 1e-3  # not a vacuous case
-    for b in range(B):
-        assert not dx[b, in_len[b]:].any(), b  # rows past in_len are written as zeros
-
-
+# ------------------------------------------------------------------ 1: the reference slot
 @pytest.mark.parametrize("shape", SHAPES, ids=IDS)
 def test_reference_slot_likelihood_is_the_ctc_loss(shape):
     """loglik[.., N] = -nll of CTCLossOp on the same logits and references, for the clips where
@@ -120,7 +27,7 @@ def test_reference_slot_likelihood_is_the_ctc_loss(shape):
     from scattennet_amd.heads import CTCLossOp
     dev = _dev()
     B, T, C, W, N = shape
-    logits, in_len, _, refs = X.case_inputs(shape)
+    logits, in_len, _, refs = M.case_inputs_ext(shape)
     _, det, _ = _case_run(shape, "reference")
     ref, ref_len = (torch.from_numpy(a).to(dev) for a in M.pack_refs(refs))
     _, nll = CTCLossOp.apply(torch.from_numpy(logits).to(dev), ref, torch.tensor(in_len, dtype=torch.int32, device=dev),
@@ -154,8 +61,8 @@ def test_hand_built_case():
     dev = _dev()
     x, in_len, lists, refs = _hand_case()
     lm = NR.random_lm(6, seed=3)
-    for name, kw in (("acoustic", {}), ("table", dict(lm=lm, lm_weight=X.LM_WEIGHT, length_bonus=X.LENGTH_BONUS))):
-        want = X.mwer(x, in_len, lists, refs, 1.0, n_max=4, with_ref=True, **kw)
+    for name, kw in (("acoustic", {}), ("table", dict(lm=lm, lm_weight=M.LM_WEIGHT, length_bonus=M.LENGTH_BONUS))):
+        want = M.mwer(x, in_len, lists, refs, 1.0, n_max=4, with_ref=True, **kw)
         assert want["ref_valid"].tolist() == [1, 0, 0, 1, 0, 0, 1, 1]
         assert np.isneginf(want["loglik"][[1, 5], 4]).all() and np.isfinite(want["loglik"][[0, 2, 3, 4, 6, 7], 4]).all()
         assert set(want["errors"][7, :3]) == {2} and np.abs(want["dlogits"][7]).max() >= 1e-3
@@ -171,22 +78,13 @@ def test_hand_built_case():
 
 
 # ------------------------------------------------------------------ 3: the bitwise conditions
-def _same(a, b, where):
-    (la, da, ga), (lb, db, gb) = a, b
-    assert torch.equal(_bits(la), _bits(lb)), where
-    assert set(da) == set(db)
-    for k in da:
-        assert da[k].dtype == db[k].dtype and torch.equal(_bits(da[k]), _bits(db[k])), (where, k)
-    assert torch.equal(_bits(ga), _bits(gb)), where
-
-
 def test_weight_zero_and_bonus_zero_with_a_table_is_the_call_without_one():
     dev = _dev()
     shape = (5, 16, 4, 8, 8)
-    logits, in_len, lists, refs = X.case_inputs(shape)
+    logits, in_len, lists, refs = M.case_inputs_ext(shape)
     base = _case_run(shape, "reference")
     zero = _run(logits, in_len, lists, refs, shape[4], shape[1], dev, M.POSTERIOR_SCALE, reference=True,
-                lm=X.random_lm(shape[2]), lm_weight=0.0, length_bonus=0.0)
+                lm=M.random_lm(shape[2]), lm_weight=0.0, length_bonus=0.0)
     _same(zero, base, "weight 0")
     assert base[2].abs().max() > 0
 
@@ -197,10 +95,10 @@ def test_head_of_a_grouped_call_is_the_single_head_call():
     dev = _dev()
     shape = (5, 16, 4, 8, 8)
     B, T, C, W, N = shape
-    _, in_len, lists, refs = X.case_inputs(shape)
+    _, in_len, lists, refs = M.case_inputs_ext(shape)
     xs = tuple(np.random.default_rng(s).normal(0.0, 4.0, (B, T, C)).astype(np.float32) for s in (0, 1, 2))
     heads_lists = (lists, lists[1:] + lists[:1], [l[::-1] for l in lists])  # entries that do not fit are fine
-    kw = dict(reference=True, lm=X.random_lm(C), lm_weight=X.LM_WEIGHT, length_bonus=X.LENGTH_BONUS)
+    kw = dict(reference=True, lm=M.random_lm(C), lm_weight=M.LM_WEIGHT, length_bonus=M.LENGTH_BONUS)
     loss, det, dxs = _run(xs, in_len, heads_lists, refs, N, T, dev, M.POSTERIOR_SCALE, **kw)
     assert loss.shape == (3,) and det["loglik"].shape == (3, B, N + 1) and det["ref_valid"].shape == (3, B)
     for g in range(3):
@@ -210,51 +108,23 @@ def test_head_of_a_grouped_call_is_the_single_head_call():
     assert not torch.equal(dxs[0], dxs[1])
 
 
-def test_new_path_without_reference_and_table_is_the_old_op():
-    import scattennet_amd as S
-    dev = _dev()
-    shape = (4, 12, 6, 8, 3)
-    B, T, C, W, N = shape
-    logits, in_len, lists, refs = M.case_inputs(shape)
-    nb = _nbest(lists, N, T, dev, fill=-5)
-    il = torch.tensor(in_len, dtype=torch.int32, device=dev)
-    ref, ref_len = (torch.from_numpy(a).to(dev) for a in M.pack_refs(refs))
-    outs = []
-    for new in (False, True):
-        x = torch.from_numpy(logits).to(dev).requires_grad_(True)
-        if new:
-            loss, ll, post, err, rv, risk = S.MWERHeadsLossOp.apply(il, nb.tokens, nb.lengths, nb.count, ref, ref_len,
-                                                                    M.POSTERIOR_SCALE, False, None, 0.0, 0.0, False,
-                                                                    x)
-            assert not rv.any() and loss.dim() == 0
-        else:
-            loss, ll, post, err, risk = S.MWERLossOp.apply(x, il, nb.tokens, nb.lengths, nb.count, ref, ref_len,
-                                                           M.POSTERIOR_SCALE)
-        loss.backward()
-        torch.cuda.synchronize()
-        outs.append((loss.detach().cpu(), {"loglik": ll.cpu(), "posterior": post.cpu(), "errors": err.cpu(),
-                                           "risk": risk.cpu()}, x.grad.cpu()))
-    _same(outs[1], outs[0], "new path")
-    assert outs[0][2].abs().max() > 0
-
-
 def test_captured_forward_and_backward_replay_bitwise():
     import scattennet_amd as S
     dev = _dev()
     shape = (5, 16, 4, 8, 8)
     B, T, C, W, N = shape
-    logits, in_len, _, refs = X.case_inputs(shape)
+    logits, in_len, _, refs = M.case_inputs_ext(shape)
     xs = [torch.from_numpy(logits).to(dev).requires_grad_(True), torch.from_numpy(logits[::-1].copy()).to(dev).requires_grad_(True)]
     il = torch.tensor(in_len, dtype=torch.int32, device=dev)
     ref, ref_len = (torch.from_numpy(a).to(dev) for a in M.pack_refs(refs))
-    lm = _lm(X.random_lm(C), dev)
+    lm = _lm(M.random_lm(C), dev)
 
     def chain():
         for x in xs:
             x.grad = None
         loss, det = S.mwer_loss(xs, il, ref, ref_len, beam_size=W, nbest_size=N, posterior_scale=M.POSTERIOR_SCALE,
-                                return_details=True, reference=True, lm=lm, lm_weight=X.LM_WEIGHT,
-                                length_bonus=X.LENGTH_BONUS, fusion=True)
+                                return_details=True, reference=True, lm=lm, lm_weight=M.LM_WEIGHT,
+                                length_bonus=M.LENGTH_BONUS, fusion=True)
         loss.sum().backward()
         return [loss.detach(), det["loglik"], det["posterior"], det["errors"], det["ref_valid"], det["risk"],
                 xs[0].grad, xs[1].grad]
@@ -296,7 +166,7 @@ def test_many_pairs_take_the_grid_form_of_the_per_clip_kernel():
     refs = [pool[(b + 1) % len(pool)] for b in range(B)]
     loss, det, dxs = _run(xs, in_len, lists, refs, N, T, dev, 1.0, fill=-3, reference=True)
     for g in range(G):
-        want = X.mwer(xs[g], in_len, lists[g], refs, 1.0, n_max=N, with_ref=True)
+        want = M.mwer(xs[g], in_len, lists[g], refs, 1.0, n_max=N, with_ref=True)
         assert np.abs(want["dlogits"]).max() >= 1e-3 and abs(want["loss"]) > 1e-3
         assert 0 < want["ref_valid"].sum() < B
         _assert_parity(f"G2xB35 head {g}", loss[g], {k: v[g] for k, v in det.items()}, dxs[g], want)
@@ -305,30 +175,6 @@ def test_many_pairs_take_the_grid_form_of_the_per_clip_kernel():
 # ------------------------------------------------------------------ 5: the steps
 HEADS = ("alignment_gloss_logits", "fuse_coord_gloss_logits")
 BEAM, NBEST, WEIGHT, LM_W = NR.MODEL_BEAM, 3, 0.5, 0.5
-ADAM = dict(lr=0.0, betas=(0.9, 0.998), weight_decay=0.0)  # lr 0: every step sees the same parameters
-
-
-@pytest.fixture(scope="module")
-def fx():
-    return load("model_small", "manifest_model.json")
-
-
-def _build(fx, dev):
-    """The dropout-free configuration of the existing step tests: the fixture model in eval mode."""
-    import scattennet_amd as S
-    m = S.MSCA_Net(copy.deepcopy(fx["meta"]["cfg"]), list(range(fx["meta"]["vocab"])), device="cuda")
-    m.load_state_dict({k: v for k, v in fx["param"].items()}, strict=True)
-    return m.to(dev).eval()
-
-
-def _trainer(fx, dev):
-    import scattennet_amd as S
-    model = _build(fx, dev)
-    return model, S.FusedAdam(model.parameters(), **ADAM)
-
-
-def _grads(model):
-    return {k: (None if p.grad is None else p.grad.detach().cpu().clone()) for k, p in model.named_parameters()}
 
 
 def _table(fx):
@@ -353,7 +199,7 @@ def _restated(out, src, table):
             entries, gaps = NR.nbest(logits[b], lens[b], BEAM, NBEST, collapse_repeats=False)
             assert min(gaps["frame"], gaps["final"]) >= 1e-4, gaps  # no tie in the search (tests/test_nbest.py)
             lists.append([h for h, _ in entries])
-        res.append(X.mwer(logits, lens, lists, refs, 1.0, n_max=NBEST, with_ref=True, lm=table, lm_weight=LM_W))
+        res.append(M.mwer(logits, lens, lists, refs, 1.0, n_max=NBEST, with_ref=True, lm=table, lm_weight=LM_W))
     return res
 
 

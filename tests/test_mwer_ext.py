@@ -1,6 +1,6 @@
 """CPU checks of the extended MWER loss (the reference as one more entry of the list, the gloss
 model's prior inside the posterior, several heads per call): the float64 restatement
-(tests/mwer_ext_ref.py) against its own closed form, the slot rules, the conditions the GPU
+(tests/mwer_ref.py) against its own closed form, the slot rules, the conditions the GPU
 cases' inputs must meet, host-only API validation, and the header's entry points.  No GPU."""
 import itertools
 import os
@@ -11,7 +11,6 @@ import pytest
 import torch
 
 from tests import decode_ref as D
-from tests import mwer_ext_ref as X
 from tests import mwer_ref as M
 from tests import nbest_ref as NR
 
@@ -27,9 +26,9 @@ def _logits(T, C, seed=1):
 @pytest.mark.parametrize("table", [False, True], ids=["acoustic", "table"])
 @pytest.mark.parametrize("shape", SHAPES, ids=IDS)
 def test_closed_form_gradient_equals_autograd_on_the_augmented_lists(shape, table):
-    logits, in_len, lists, refs = X.case_inputs(shape)
-    res = X.case_ref(shape, True, table)
-    got = X.analytic_grad(logits, in_len, lists, refs, M.POSTERIOR_SCALE, with_ref=True, **X.prior_kwargs(shape, table))
+    logits, in_len, lists, refs = M.case_inputs_ext(shape)
+    res = M.case_ref_ext(shape, True, table)
+    got = M.analytic_grad(logits, in_len, lists, refs, M.POSTERIOR_SCALE, with_ref=True, **M.prior_kwargs(shape, table))
     assert np.abs(got - res["dlogits"]).max() < 1e-9
     assert np.isfinite(res["loss"]) and np.abs(res["dlogits"]).max() >= 1e-3
 
@@ -40,10 +39,10 @@ def test_the_gpu_inputs_cover_the_slot_rules():
     seen = {"duplicate": 0, "unfit": 0, "slots33": 0, "full_length": 0}
     for shape in SHAPES:
         B, T, C, W, N = shape
-        logits, in_len, lists, refs = X.case_inputs(shape)
-        res = X.case_ref(shape, True, False)
+        logits, in_len, lists, refs = M.case_inputs_ext(shape)
+        res = M.case_ref_ext(shape, True, False)
         assert res["ref_valid"].sum() >= 1, shape
-        assert abs(res["loss"] - X.case_ref(shape, False, False)["loss"]) > 1e-6, shape
+        assert abs(res["loss"] - M.case_ref_ext(shape, False, False)["loss"]) > 1e-6, shape
         for b in range(B):
             assert all(1 <= c < C for c in refs[b])
             fits = M.fits(refs[b], in_len[b])
@@ -66,7 +65,7 @@ def test_error_count_zero_means_equal_sequences():
     """The duplicate rule rests on it: under wer_single's costs err == 0 iff the sequences are equal."""
     pairs = 0
     for shape in SHAPES:
-        _, _, lists, refs = X.case_inputs(shape)
+        _, _, lists, refs = M.case_inputs_ext(shape)
         pool = [list(r) for r in refs] + [list(r) for r in M.case_inputs(shape)[3]]
         for b, entries in enumerate(lists):
             for r in pool:
@@ -83,42 +82,42 @@ def test_slot_rules():
     x = _logits(5, 4, seed=3)[None]
     kw = dict(with_ref=True)
     # a duplicate: the slot is out of V, its likelihood is still reported, the result is the plain list's
-    res, plain = X.mwer(x, [4], [[[1], [2, 3]]], [[2, 3]], **kw), M.mwer(x, [4], [[[1], [2, 3]]], [[2, 3]])
+    res, plain = M.mwer(x, [4], [[[1], [2, 3]]], [[2, 3]], **kw), M.mwer(x, [4], [[[1], [2, 3]]], [[2, 3]])
     assert res["ref_valid"][0] == 0 and res["posterior"][0, 2] == 0.0
     assert res["loglik"][0, 2] == res["loglik"][0, 1] and np.isfinite(res["loglik"][0, 2])
     assert res["loss"] == plain["loss"] and np.array_equal(res["dlogits"], plain["dlogits"])
     # an unfit reference ([1, 1] needs 3 frames)
-    res = X.mwer(x, [2], [[[1], [2]]], [[1, 1]], **kw)
+    res = M.mwer(x, [2], [[[1], [2]]], [[1, 1]], **kw)
     assert res["ref_valid"][0] == 0 and res["loglik"][0, 2] == -np.inf and res["posterior"][0, 2] == 0.0
     # an empty reference: valid iff the empty entry is absent
-    assert X.mwer(x, [3], [[[1], [2]]], [[]], **kw)["ref_valid"][0] == 1
-    assert X.mwer(x, [3], [[[1], []]], [[]], **kw)["ref_valid"][0] == 0
-    assert X.mwer(x, [0], [[[]]], [[]], **kw)["ref_valid"][0] == 0 and X.mwer(x, [0], [[[1]]], [[]], **kw)["ref_valid"][0] == 1
+    assert M.mwer(x, [3], [[[1], [2]]], [[]], **kw)["ref_valid"][0] == 1
+    assert M.mwer(x, [3], [[[1], []]], [[]], **kw)["ref_valid"][0] == 0
+    assert M.mwer(x, [0], [[[]]], [[]], **kw)["ref_valid"][0] == 0 and M.mwer(x, [0], [[[1]]], [[]], **kw)["ref_valid"][0] == 1
     # count = 0 with a fitting reference: a lone valid slot, posterior 1, no loss and no gradient
-    res = X.mwer(x, [5], [[]], [[1, 2]], n_max=2, **kw)
+    res = M.mwer(x, [5], [[]], [[1, 2]], n_max=2, **kw)
     assert res["ref_valid"][0] == 1 and res["posterior"][0].tolist() == [0.0, 0.0, 1.0]
     assert res["loss"] == 0.0 and res["risk"][0] == 0.0 and not res["dlogits"].any()
-    assert not X.analytic_grad(x, [5], [[]], [[1, 2]], **kw).any()
+    assert not M.analytic_grad(x, [5], [[]], [[1, 2]], **kw).any()
     # equal error counts have no gradient without the slot and one with it
     lists, refs = [[[1], [2], [3]]], [[1, 2, 3]]
     assert not M.mwer(x, [5], lists, refs)["dlogits"].any()
-    res = X.mwer(x, [5], lists, refs, **kw)
+    res = M.mwer(x, [5], lists, refs, **kw)
     assert set(res["errors"][0, :3]) == {2} and np.abs(res["dlogits"]).max() > 1e-3 and res["loss"] != 0
-    assert np.abs(X.analytic_grad(x, [5], lists, refs, **kw) - res["dlogits"]).max() < 1e-12
+    assert np.abs(M.analytic_grad(x, [5], lists, refs, **kw) - res["dlogits"]).max() < 1e-12
 
 
 def test_prior_is_the_rescorers_total_and_weight_zero_changes_nothing():
     x = _logits(6, 5, seed=4)[None]
     lists, refs = [[[1, 2], [3], [], [4, 4]]], [[1, 3]]
     lm = NR.random_lm(5, seed=2)
-    base = X.mwer(x, [6], lists, refs, 0.8, with_ref=True)
-    zero = X.mwer(x, [6], lists, refs, 0.8, with_ref=True, lm=lm, lm_weight=0.0, length_bonus=0.0)
+    base = M.mwer(x, [6], lists, refs, 0.8, with_ref=True)
+    zero = M.mwer(x, [6], lists, refs, 0.8, with_ref=True, lm=lm, lm_weight=0.0, length_bonus=0.0)
     assert zero["loss"] == base["loss"] and np.array_equal(zero["posterior"], base["posterior"])
-    res = X.mwer(x, [6], lists, refs, 0.8, with_ref=True, lm=lm, lm_weight=0.7, length_bonus=0.3)
+    res = M.mwer(x, [6], lists, refs, 0.8, with_ref=True, lm=lm, lm_weight=0.7, length_bonus=0.3)
     slots = lists[0] + refs
     total, post, _ = NR.rescore([(h, ll) for h, ll in zip(slots, res["loglik"][0])], lm, 0.7, 0.3, 0.8)
     assert np.abs(post - res["posterior"][0]).max() < 1e-12 and abs(res["loss"] - base["loss"]) > 1e-4
-    assert X.prior([], lm, 0.7, 0.3) == pytest.approx(0.7 * lm[0, 0])
+    assert M.prior([], lm, 0.7, 0.3) == pytest.approx(0.7 * lm[0, 0])
 
 
 def test_mwer_spec_validation_and_repr():

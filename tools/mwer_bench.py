@@ -2,7 +2,8 @@
 yaml (B = 8, T/4 = 64, C = 1124), beam 5 and N = 5, with the lists the decoder gives, beside what
 the CTC loss of the same build costs on the same logits:
 
-* `mwer`            MWERLossOp forward + backward over the decoder's N-best list
+* `mwer`            MWERLossOp forward + backward over the decoder's N-best list (one tensor,
+                    everything off: `sca_mwer_heads_fwd` / `_bwd` at G = 1 without the prior)
 * `ctc_1target`     CTCLossOp forward + backward, one target per clip (entry 0 of the list)
 * `ctc_replicated`  CTCLossOp forward + backward on logits.repeat_interleave(N, 0) with the N
                     hypotheses as labels: what the existing kernels charge for the N likelihoods
@@ -58,7 +59,7 @@ def extended(a, S, dev):
     captured graphs in alternated windows.  Lists: the decoder's own; references: entry 1 of each
     list with its middle token replaced by a class the list's clip does not use there (a
     reference that is NOT in the list, so the slot is valid everywhere).
-    * `mwer`             the plain loss at N entries (the old entry points)
+    * `mwer`             the plain loss at N entries (one tensor, everything off)
     * `mwer_reference`   reference=True at N entries              (--reference)
     * `mwer_n_plus_1`    the plain loss over a list of N + 1 entries: the slot's yardstick
     * `mwer_lm`          the table on, everything else as the widest variant above   (--lm)
