@@ -56,6 +56,8 @@
  *   sca_eval_log_alignments  and confidences of given label sequences, and their log in a pass
  *   sca_ensemble_log_probs (no counterpart) the weighted mean of the heads' posteriors as
  *                          log-probabilities, decoded as one more head
+ *   sca_ensemble_log_probs_bwd  (no counterpart) its vector-Jacobian product, which makes the
+ *                          ensemble a tensor the training losses can be taken on
  *   sca_ctc_beam_decode*_nbest  (no counterpart; the interface of the decoder's top_paths) the N
  *   sca_nbest_rescore/mbr/gather  best labellings of the beam search, their rescoring with a
  *                          bigram gloss model, the posterior over the list and MBR selection
@@ -962,6 +964,43 @@ typedef struct {
 } sca_ensemble_weights;
 int sca_ensemble_log_probs(const sca_decode_heads* heads, int G, const sca_ensemble_weights* weights, int mode,
                            int B, int T, int C, float* out, void* stream);
+
+/* The vector-Jacobian product of sca_ensemble_log_probs: dlogits[g] (B, T, C) fp32 =
+ * (d out / d x_g)^T dout for the members of one forward, in one launch.  heads, G, weights (again
+ * normalised here in double, exactly as the forward does), mode, B, T, C: the forward's; out:
+ * the forward's output; dout (B, T, C): the incoming gradient, contiguous.  The weights are host
+ * constants without a gradient.  dlogits: up to G device pointers by value (entries [G, 8) are
+ * ignored).  A null entry means "this member takes no gradient": nothing of it is computed or
+ * written; with every entry null nothing is launched.  Every element of a non-null entry is
+ * written.
+ *
+ * Per row, p_g = softmax(x_g), lp_g = log p_g, q = exp(out):
+ *   mode 0:  r_g[c] = exp(lp_g[c] + log W_g - out[c])   (member g's responsibility for class c;
+ *            <= 1 by construction, so nothing overflows at the heads' clamp)
+ *            dx_g[k] = r_g[k] dout[k] - p_g[k] sum_c r_g[c] dout[c]
+ *   mode 1:  du[c] = dout[c] - q[c] sum_c' dout[c']
+ *            dx_g[k] = W_g du[k]
+ *            This is the form implemented: the chain through log_softmax(x_g) adds
+ *            - W_g p_g[k] sum_c du[c], and that sum is identically 0 because sum q = 1.  The
+ *            members are not read in this mode.
+ * A row with dout = 0 gets gradients that compare == 0 in both modes.  In mode 0 the members'
+ * row statistics (max, log-sum-exp) are recomputed as the forward computes them; nothing is
+ * saved between the two calls but `out`.
+ *
+ * The forward's shape: one wave per row, four rows per workgroup; 16-byte loads and stores where
+ * every row involved (the members, out, dout and every non-null gradient) starts on a 16-byte
+ * boundary and C % 4 == 0, scalar ones otherwise.  No atomics, no LDS, no barrier, a fixed order
+ * of every sum: a row's gradients depend on nothing but the row, and a replayed capture is
+ * bitwise the eager call.  Nothing allocates, copies or synchronises (capturable).
+ * SCA_ERR_ARG before any GPU call: the forward's checks on heads, G, weights, mode and sizes; a
+ * null out, dout or dlogits; out == dout; a non-null gradient tensor that is out, dout, a member
+ * or another gradient tensor.                                                              */
+typedef struct {
+  float* dlogits[SCA_EVAL_MAX_HEADS]; /* entries [G, 8) are ignored; NULL: no gradient for this member */
+} sca_ensemble_grads;
+int sca_ensemble_log_probs_bwd(const sca_decode_heads* heads, int G, const sca_ensemble_weights* weights,
+                               int mode, int B, int T, int C, const float* out, const float* dout,
+                               const sca_ensemble_grads* dlogits, void* stream);
 
 /* SeqKD over R rows of C logits (student, teacher): columns [start, C) only (use_blank=False
  * -> start 1), temperature temp:

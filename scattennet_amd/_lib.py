@@ -156,6 +156,10 @@ class EnsembleWeights(ctypes.Structure):
     _fields_ = [("w", c_float * EVAL_MAX_HEADS)]
 
 
+class EnsembleGrads(ctypes.Structure):
+    _fields_ = [("dlogits", c_void_p * EVAL_MAX_HEADS)]
+
+
 class EvalState(ctypes.Structure):
     _fields_ = [("cursor", c_int), ("steps", c_int), ("overflow", c_int), ("first_flagged", c_int),
                 ("totals", (c_int * 4) * EVAL_MAX_HEADS), ("flags", ctypes.c_uint * REPORT_MAX_FLAGS),
@@ -248,6 +252,7 @@ EXPORTS = {
     "sca_ctc_align_heads": ([c_void_p, c_int, c_void_p, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 6, c_int),
     "sca_eval_log_alignments": ([c_void_p] * 3 + [c_int] * 3 + [c_void_p] * 4 + [c_int, c_int, c_void_p], c_int),
     "sca_ensemble_log_probs": ([c_void_p, c_int, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p], c_int),
+    "sca_ensemble_log_probs_bwd": ([c_void_p, c_int, c_void_p] + [c_int] * 4 + [c_void_p] * 4, c_int),
     "sca_optim_blocks": ([c_int, c_int], c_int),
     "sca_optim_grad_sqnorm": ([c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
     "sca_optim_adam_step": ([c_void_p, c_void_p, c_int, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p],

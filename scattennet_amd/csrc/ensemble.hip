@@ -12,6 +12,10 @@
 // on a 16-byte boundary and C is a multiple of 4; any other row takes the scalar path.
 // No atomics, no LDS; every sum runs in a fixed order and a row's result depends on nothing
 // but the row, so a replayed capture is bitwise the eager call.
+//
+// sca_ensemble_log_probs_bwd is the vector-Jacobian product of the same map, one launch for all
+// members with the same shape and guarantees; the members' row statistics are recomputed, not
+// saved.
 #include "ctc.h"
 
 namespace {
@@ -55,6 +59,28 @@ __device__ __forceinline__ void stv(float* p, const Pack<V>& r) {
   }
 }
 
+// The row statistics of one member's row, by one wave: m = max, ls = log sum exp(x - m).  One
+// body under the forward and the backward, so they agree bitwise.
+template <int V>
+__device__ __forceinline__ void member_stat(const float* __restrict__ xr, int C, int lane, float& m, float& ls) {
+  float mx = NEG_INF;
+  for (int c = lane * V; c < C; c += 64 * V) {
+    const Pack<V> x = ldv<V>(xr + c);
+#pragma unroll
+    for (int i = 0; i < V; ++i) mx = fmaxf(mx, x.v[i]);
+  }
+  mx = wave_max(mx);
+  float s = 0.0f;
+  for (int c = lane * V; c < C; c += 64 * V) {
+    const Pack<V> x = ldv<V>(xr + c);
+#pragma unroll
+    for (int i = 0; i < V; ++i) s += __expf(x.v[i] - mx);
+  }
+  s = wave_sum(s);
+  m = mx;
+  ls = __logf(s);
+}
+
 // One row by one wave; lane l owns the elements [V (l + 64 k), V (l + 64 k) + V) in every pass.
 // V = 4 only when C % 4 == 0, so a pack never crosses the end of the row.
 template <int V>
@@ -66,25 +92,7 @@ __device__ __forceinline__ void ensemble_row(const EnsHeads& h, int G, int mode,
   for (int g = 0; g < G_MAX; ++g) {
     m[g] = 0.0f;
     ls[g] = 0.0f;
-    if (g < G) {
-      const float* xr = h.x.x[g] + off;
-      float mx = NEG_INF;
-      for (int c = lane * V; c < C; c += 64 * V) {
-        const Pack<V> x = ldv<V>(xr + c);
-#pragma unroll
-        for (int i = 0; i < V; ++i) mx = fmaxf(mx, x.v[i]);
-      }
-      mx = wave_max(mx);
-      float s = 0.0f;
-      for (int c = lane * V; c < C; c += 64 * V) {
-        const Pack<V> x = ldv<V>(xr + c);
-#pragma unroll
-        for (int i = 0; i < V; ++i) s += __expf(x.v[i] - mx);
-      }
-      s = wave_sum(s);
-      m[g] = mx;
-      ls[g] = __logf(s);
-    }
+    if (g < G) member_stat<V>(h.x.x[g] + off, C, lane, m[g], ls[g]);
   }
 
   if (mode == 0) {
@@ -174,7 +182,165 @@ __global__ __launch_bounds__(256) void ensemble_log_probs_kernel(EnsHeads h, int
     ensemble_row<1>(h, G, mode, off, outr, C, lane);
 }
 
+// ---- backward: dx_g = (d out / d x_g)^T dout for every member that takes a gradient ----------
+// The gradient tensors, by value beside the members.  A null entry: the member takes no
+// gradient; nothing of it is computed or written.
+struct EnsGrads {
+  float* dx[G_MAX];
+};
+
+// One row by one wave, the lanes' elements as in ensemble_row.  q = exp(out), p_g = softmax(x_g).
+//   mode 0: r_g[c] = exp(a_g[c] - out[c]), a_g = lp_g + log W_g as the forward computes it (the
+//     responsibility of member g for class c, <= 1 up to rounding: nothing overflows);
+//     dx_g[k] = r_g[k] dout[k] - p_g[k] sum_c r_g[c] dout[c].  The members' row statistics are
+//     recomputed as the forward does (a row is a few KB: the re-reads come from L2 / L1).
+//   mode 1: du[c] = dout[c] - q[c] sum_c' dout[c'] and dx_g = W_g du: the term
+//     - W_g p_g[k] sum_c du[c] of the chain through log_softmax(x_g) is dropped, the sum being
+//     identically 0 (sum q = 1).  The members are not read at all.
+template <int V>
+__device__ __forceinline__ void ensemble_bwd_row(const EnsHeads& h, const EnsGrads& d, int G, int mode, long off,
+                                                 const float* __restrict__ outr, const float* __restrict__ doutr, int C,
+                                                 int lane) {
+  if (mode == 1) {
+    float D = 0.0f;
+    for (int c = lane * V; c < C; c += 64 * V) {
+      const Pack<V> dy = ldv<V>(doutr + c);
+#pragma unroll
+      for (int i = 0; i < V; ++i) D += dy.v[i];
+    }
+    D = wave_sum(D);
+    for (int c = lane * V; c < C; c += 64 * V) {
+      const Pack<V> o = ldv<V>(outr + c), dy = ldv<V>(doutr + c);
+      Pack<V> du;
+#pragma unroll
+      for (int i = 0; i < V; ++i) du.v[i] = dy.v[i] - __expf(o.v[i]) * D;
+#pragma unroll
+      for (int g = 0; g < G_MAX; ++g) {
+        if (g < G && d.dx[g]) {
+          Pack<V> r;
+#pragma unroll
+          for (int i = 0; i < V; ++i) r.v[i] = h.w[g] * du.v[i];
+          stv<V>(d.dx[g] + off + c, r);
+        }
+      }
+    }
+    return;
+  }
+
+  // mode 0.  s[g] = sum_c r_g[c] dout[c], one pass over the classes for all the members
+  float m[G_MAX], ls[G_MAX], s[G_MAX];
+#pragma unroll
+  for (int g = 0; g < G_MAX; ++g) {
+    m[g] = 0.0f;
+    ls[g] = 0.0f;
+    s[g] = 0.0f;
+    if (g < G && d.dx[g]) member_stat<V>(h.x.x[g] + off, C, lane, m[g], ls[g]);
+  }
+  for (int c = lane * V; c < C; c += 64 * V) {
+    const Pack<V> o = ldv<V>(outr + c), dy = ldv<V>(doutr + c);
+#pragma unroll
+    for (int g = 0; g < G_MAX; ++g) {
+      if (g < G && d.dx[g]) {
+        const Pack<V> x = ldv<V>(h.x.x[g] + off + c);
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+          const float a = ctc_lp_raw(x.v[i], m[g], ls[g]) + h.lw[g];
+          s[g] += __expf(a - o.v[i]) * dy.v[i];
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int g = 0; g < G_MAX; ++g)
+    if (g < G && d.dx[g]) s[g] = wave_sum(s[g]);
+  for (int c = lane * V; c < C; c += 64 * V) {
+    const Pack<V> o = ldv<V>(outr + c), dy = ldv<V>(doutr + c);
+#pragma unroll
+    for (int g = 0; g < G_MAX; ++g) {
+      if (g < G && d.dx[g]) {
+        const Pack<V> x = ldv<V>(h.x.x[g] + off + c);
+        Pack<V> r;
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+          const float lp = ctc_lp_raw(x.v[i], m[g], ls[g]);
+          r.v[i] = __expf((lp + h.lw[g]) - o.v[i]) * dy.v[i] - __expf(lp) * s[g];
+        }
+        stv<V>(d.dx[g] + off + c, r);
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void ensemble_log_probs_bwd_kernel(EnsHeads h, EnsGrads d, int G, int mode,
+                                                                     const float* out, const float* dout, long rows,
+                                                                     int C) {
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= rows) return;  // no barrier below: a wave without a row leaves
+  const long off = row * C;
+  // 16-byte packs only where every row involved starts on a 16-byte boundary: the members, out,
+  // dout and every gradient row that is written
+  uintptr_t bits = reinterpret_cast<uintptr_t>(out + off) | reinterpret_cast<uintptr_t>(dout + off) | (uintptr_t)(C & 3);
+#pragma unroll
+  for (int g = 0; g < G_MAX; ++g) {
+    if (g < G) {
+      bits |= reinterpret_cast<uintptr_t>(h.x.x[g] + off);
+      if (d.dx[g]) bits |= reinterpret_cast<uintptr_t>(d.dx[g] + off);
+    }
+  }
+  if ((bits & 15) == 0)
+    ensemble_bwd_row<4>(h, d, G, mode, off, out + off, dout + off, C, lane);
+  else
+    ensemble_bwd_row<1>(h, d, G, mode, off, out + off, dout + off, C, lane);
+}
+
+// G normalised weights and their logarithms, in double, for the forward and the backward alike
+EnsHeads ens_heads_of(const sca_decode_heads* heads, int G, const sca_ensemble_weights* weights, double sum) {
+  EnsHeads h;
+  h.x = ctc_heads_of(heads, G);
+  for (int g = 0; g < G_MAX; ++g) {
+    const double w = (double)weights->w[g < G ? g : 0] / sum;
+    h.w[g] = (float)w;
+    h.lw[g] = (float)log(w);
+  }
+  return h;
+}
+
 }  // namespace
+
+extern "C" int sca_ensemble_log_probs_bwd(const sca_decode_heads* heads, int G, const sca_ensemble_weights* weights,
+                                          int mode, int B, int T, int C, const float* out, const float* dout,
+                                          const sca_ensemble_grads* dlogits, void* stream) {
+  const long rows = (long)B * T;
+  bool ok = heads && weights && out && dout && dlogits && out != dout && G >= 1 && G <= SCA_EVAL_MAX_HEADS &&
+            (mode == 0 || mode == 1) && B >= 1 && T >= 1 && C >= 1 && (rows + 3) / 4 <= 0x7fffffffL;
+  double sum = 0.0;
+  bool any = false;
+  for (int g = 0; ok && g < G; ++g) {
+    const float w = weights->w[g];
+    ok = heads->logits[g] != nullptr && w > 0.0f && w <= 3.0e38f;  // NaN fails w > 0
+    sum += w;
+    const float* dx = dlogits->dlogits[g];
+    if (!dx) continue;
+    any = true;
+    ok = ok && dx != out && dx != dout;
+    for (int k = 0; ok && k < G; ++k)
+      ok = dx != heads->logits[k] && (k == g || dx != dlogits->dlogits[k]);
+  }
+  if (!ok) {
+    sca_set_error("sca_ensemble_log_probs_bwd: bad arguments (1 <= G <= 8 non-null tensors, G finite positive "
+                  "weights, mode 0 or 1, B, T, C >= 1, out and dout non-null and distinct, every non-null gradient "
+                  "tensor distinct from out, dout, the members and the other gradient tensors)");
+    return SCA_ERR_ARG;
+  }
+  if (!any) return SCA_OK;  // no member takes a gradient: nothing to launch
+  const EnsHeads h = ens_heads_of(heads, G, weights, sum);
+  EnsGrads d;
+  for (int g = 0; g < G_MAX; ++g) d.dx[g] = g < G ? dlogits->dlogits[g] : nullptr;
+  hipLaunchKernelGGL(ensemble_log_probs_bwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), h, d, G, mode, out, dout, rows, C);
+  return sca_launch_status("sca_ensemble_log_probs_bwd");
+}
 
 extern "C" int sca_ensemble_log_probs(const sca_decode_heads* heads, int G, const sca_ensemble_weights* weights,
                                       int mode, int B, int T, int C, float* out, void* stream) {
@@ -192,13 +358,7 @@ extern "C" int sca_ensemble_log_probs(const sca_decode_heads* heads, int G, cons
                   "positive weights, mode 0 or 1, B, T, C >= 1)");
     return SCA_ERR_ARG;
   }
-  EnsHeads h;
-  h.x = ctc_heads_of(heads, G);
-  for (int g = 0; g < G_MAX; ++g) {
-    const double w = (double)weights->w[g < G ? g : 0] / sum;
-    h.w[g] = (float)w;
-    h.lw[g] = (float)log(w);
-  }
+  const EnsHeads h = ens_heads_of(heads, G, weights, sum);
   hipLaunchKernelGGL(ensemble_log_probs_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), h, G, mode, out, rows, C);
   return sca_launch_status("sca_ensemble_log_probs");

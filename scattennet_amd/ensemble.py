@@ -2,10 +2,12 @@
 include/scatten.h): the normalised log-probabilities of the weighted mean of G heads'
 posteriors, the tensor the multi-stream recognisers decode next to the single heads.
 
-* `ensemble_log_probs(logits_list, weights=None, mode="prob")` — one launch over the G logit
-  tensors of one forward; device tensors in and out, no host read, usable under
-  `torch.cuda.graph` capture.  `"prob"`: the arithmetic mean of the posteriors; `"logprob"`:
-  the log-linear (geometric) mean, renormalised.  Its output is a logit tensor like any other:
+* `ensemble_log_probs(logits_list, weights=None, mode="prob", *, differentiable=False)` — one
+  launch over the G logit tensors of one forward; device tensors in and out, no host read, usable
+  under `torch.cuda.graph` capture.  `differentiable=True` attaches the result to the members
+  (`EnsembleLogProbsOp`, `sca_ensemble_log_probs_bwd`), which makes the ensemble a tensor that
+  `mwer_loss`, `MWER(head=EnsembleSpec(...))` and the CTC loss train on.  `"prob"`: the
+  arithmetic mean of the posteriors; `"logprob"`: the log-linear (geometric) mean, renormalised.  Its output is a logit tensor like any other:
   `ctc_decode_device`, `ctc_decode_heads_device` and `ctc_align_heads_device` take it as it is.
 * `EnsembleSpec(members, weights=None, mode="prob")` — which of the model's five logit tensors
   an ensemble averages; `check_ensembles` validates a `{output_key: EnsembleSpec}` dict against
@@ -19,6 +21,7 @@ import math
 
 import torch
 from torch import nn
+from torch.autograd import Function
 
 from . import _lib as L
 from .decode import check_heads, check_on_device
@@ -52,41 +55,86 @@ def _check_weights(weights, G, what):
     return ws
 
 
+def _launch_forward(xs, weights, mode):
+    """`sca_ensemble_log_probs` on contiguous fp32 device tensors: the new (B, T, C) output."""
+    L.require_device(*xs)
+    G = len(xs)
+    B, T, C = xs[0].shape
+    out = torch.empty_like(xs[0])
+    hx, wx = L.decode_heads(xs), L.EnsembleWeights()
+    for g in range(G):
+        wx.w[g] = weights[g]
+    L.check(L.lib().sca_ensemble_log_probs(ctypes.byref(hx), G, ctypes.byref(wx), mode, B, T, C, L.ptr(out),
+                                           L.stream_handle()), "sca_ensemble_log_probs")
+    return out
+
+
+class EnsembleLogProbsOp(Function):
+    """`sca_ensemble_log_probs` with its vector-Jacobian product (`sca_ensemble_log_probs_bwd`):
+    `weights` (G normalised Python floats), `mode` (0 / 1) and the G fp32 device logits `*logits`,
+    each (B, T, C).  The output is bitwise the detached call's.  The backward is one launch for
+    all members; a member that needs no gradient is a null entry of the pointer table, so its
+    gradient is neither computed nor written.  The weights are host constants."""
+
+    @staticmethod
+    def forward(ctx, weights, mode, *logits):
+        xs = [x.contiguous() for x in logits]
+        out = _launch_forward(xs, weights, mode)
+        ctx.save_for_backward(out, *xs)
+        ctx.weights, ctx.mode = weights, mode
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        out, *xs = ctx.saved_tensors
+        G = len(xs)
+        B, T, C = out.shape
+        dout = dout.contiguous()
+        L.require_device(dout)
+        dxs = [torch.empty_like(x) if ctx.needs_input_grad[2 + g] else None for g, x in enumerate(xs)]
+        hx, wx, gx = L.decode_heads(xs), L.EnsembleWeights(), L.EnsembleGrads()
+        for g in range(G):
+            wx.w[g] = ctx.weights[g]
+            gx.dlogits[g] = None if dxs[g] is None else dxs[g].data_ptr()
+        L.check(L.lib().sca_ensemble_log_probs_bwd(ctypes.byref(hx), G, ctypes.byref(wx), ctx.mode, B, T, C,
+                                                   L.ptr(out), L.ptr(dout), ctypes.byref(gx), L.stream_handle()),
+                "sca_ensemble_log_probs_bwd")
+        return (None, None) + tuple(dxs)
+
+
 class _Ensembler(nn.Module):
-    """Parameter-free module, so that fp16 / bf16 logits take the fp32 view of fp32_compute."""
+    """Parameter-free module, so that fp16 / bf16 logits take the fp32 view of fp32_compute (and,
+    on the differentiable path, receive their gradients in their own dtype through its casts)."""
 
     @fp32_compute()
-    def forward(self, weights, mode, *logits):
-        xs = [x.detach().contiguous() for x in logits]
-        L.require_device(*xs)
-        G = len(xs)
-        B, T, C = xs[0].shape
-        out = torch.empty_like(xs[0])
-        hx, wx = L.decode_heads(xs), L.EnsembleWeights()
-        for g in range(G):
-            wx.w[g] = weights[g]
-        L.check(L.lib().sca_ensemble_log_probs(ctypes.byref(hx), G, ctypes.byref(wx), mode, B, T, C, L.ptr(out),
-                                               L.stream_handle()), "sca_ensemble_log_probs")
-        return out
+    def forward(self, weights, mode, differentiable, *logits):
+        if differentiable:
+            return EnsembleLogProbsOp.apply(weights, mode, *logits)
+        return _launch_forward([x.detach().contiguous() for x in logits], weights, mode)
 
 
 _ensembler = _Ensembler()
 
 
-def ensemble_log_probs(logits_list, weights=None, mode="prob"):
+def ensemble_log_probs(logits_list, weights=None, mode="prob", *, differentiable=False):
     """The ensemble of G heads' posteriors as normalised log-probabilities, in one launch
     (`sca_ensemble_log_probs`).  `logits_list`: 1..8 tensors of one shape (B, T, C); `weights`:
     None (equal) or G finite positive numbers, normalised by their sum; `mode`: "prob", the
     arithmetic mean of the posteriors (log sum_g w_g softmax(x_g)), or "logprob", the log-linear
     mean renormalised (log_softmax(sum_g w_g log_softmax(x_g))).  With G = 1 both are the rows'
-    log_softmax.  Returns a detached (B, T, C) device tensor.  No host sync; capturable."""
+    log_softmax.  Returns a detached (B, T, C) device tensor; with `differentiable=True` the same
+    bits attached to the members (`EnsembleLogProbsOp`: one more launch in the backward, for all
+    the members that require a gradient; fp16 / bf16 members receive theirs in their own dtype).
+    The weights take no gradient.  No host sync; capturable, the backward too."""
+    if not isinstance(differentiable, bool):
+        raise ValueError(f"ensemble_log_probs: differentiable must be a bool, got {differentiable!r}")
     xs = check_heads(logits_list, "ensemble_log_probs")
     if xs[0].numel() == 0:
         raise ValueError(f"ensemble_log_probs: empty logits {tuple(xs[0].shape)}")
     ws = _check_weights(weights, len(xs), "ensemble_log_probs")
     m = _check_mode(mode, "ensemble_log_probs")
     check_on_device(None, xs[0])
-    return _ensembler(ws, m, *xs)
+    return _ensembler(ws, m, differentiable, *xs)
 
 
 class EnsembleSpec:
@@ -111,8 +159,9 @@ class EnsembleSpec:
     def __repr__(self):
         return f"EnsembleSpec(members={self.members!r}, weights={self.weights!r}, mode={self.mode!r})"
 
-    def compute(self, outputs):
-        return ensemble_log_probs([outputs[k] for k in self.members], self.weights, self.mode)
+    def compute(self, outputs, differentiable=False):
+        return ensemble_log_probs([outputs[k] for k in self.members], self.weights, self.mode,
+                                  differentiable=differentiable)
 
 
 def check_ensembles(heads, ensembles, what):

@@ -22,6 +22,7 @@ import torch
 from torch.autograd import Function
 
 from . import _lib as L
+from .ensemble import EnsembleSpec
 from .decode import MAX_BEAM, WER_MAX_LEN, _check_lengths, _check_logits, check_heads, check_on_device
 from .heads import _dev_i32
 from .model import _LOGITS
@@ -225,7 +226,10 @@ class MWER:
     `beam_size` (1 <= beam_size <= 32) keeping `nbest` entries (default: all of the beam), the
     posterior sharpened by `posterior_scale`, and `weight` (finite, >= 0) times the loss added to
     `total_loss` for the backward.  `head` may be a tuple of distinct head names: their losses
-    come from one grouped call and the step adds `weight` times their sum.  `reference`, `lm`
+    come from one grouped call and the step adds `weight` times their sum.  `head`, or an entry of
+    the tuple (at most 8 entries), may also be an `EnsembleSpec` (distinct objects): the step
+    computes that ensemble of its own logits with `differentiable=True` and takes the loss on it
+    like on any head, so the gradient reaches every member.  `reference`, `lm`
     (a `BigramLM` on the model's device, or a (C, C) table), `lm_weight`, `length_bonus` and
     `fusion` are `mwer_loss`'s: the reference as one more entry of every list, the gloss model's
     prior inside the posterior, the list from the fused search.  ValueError for anything else."""
@@ -252,16 +256,20 @@ class MWER:
         if not 1 <= len(names) <= MAX_HEADS:
             raise ValueError(f"MWER: between 1 and {MAX_HEADS} heads, got {len(names)}")
         for name in names:
+            if isinstance(name, EnsembleSpec):
+                continue
             if not isinstance(name, str) or name not in _LOGITS:
-                raise ValueError(f"MWER: head must be one of {_LOGITS} or a tuple of them, got {name!r}")
-        if len(set(names)) != len(names):
-            raise ValueError(f"MWER: the heads must be distinct, got {names}")
+                raise ValueError(f"MWER: head must be one of {_LOGITS}, an EnsembleSpec or a tuple of them, got {name!r}")
+        keys = [n for n in names if isinstance(n, str)]
+        specs = [id(n) for n in names if not isinstance(n, str)]
+        if len(set(keys)) != len(keys) or len(set(specs)) != len(specs):
+            raise ValueError(f"MWER: the heads must be distinct (keys by name, specs as objects), got {names}")
         if not isinstance(reference, bool):
             raise ValueError(f"MWER: reference must be a bool, got {reference!r}")
         self.lm, self.lm_weight, self.length_bonus = _check_prior(lm, lm_weight, length_bonus, fusion, None, "MWER")
         self.reference, self.fusion = reference, fusion
         self.beam_size, self.nbest, self.head = beam_size, beam_size if nbest is None else nbest, head
-        self.heads = names  # the head names as a tuple, whatever form `head` has
+        self.heads = names  # the heads (logit keys or EnsembleSpecs) as a tuple, whatever form `head` has
 
     def __repr__(self):
         extra = ""  # the keyword-only arguments appear where they differ from their defaults

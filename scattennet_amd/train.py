@@ -39,7 +39,8 @@ def _add_mwer(outputs, src_input, mwer):
     `outputs["mwer_losses"]` (G) holds each head's loss, `mwer_loss` their sum and `mwer_risk` is
     (G, B)."""
     grouped = isinstance(mwer.head, tuple)
-    logits = [outputs[name] for name in mwer.heads]
+    # an EnsembleSpec among the heads: the ensemble of this step's logits, attached to its members
+    logits = [outputs[h] if isinstance(h, str) else h.compute(outputs, differentiable=True) for h in mwer.heads]
     labels = heads.labels_2d(src_input, logits[0].shape[0], "train_step")
     loss, details = mwer_loss(logits if grouped else logits[0], outputs["input_lengths"], labels,
                               src_input["gloss_lengths"], beam_size=mwer.beam_size, nbest_size=mwer.nbest,

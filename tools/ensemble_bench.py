@@ -12,8 +12,15 @@ and one write of (B, T, C) fp32) and the rate that gives.  The outputs of the tw
 compared (maximum absolute difference) before anything is timed.  Synthetic logits N(0, 3^2).
 Needs a GPU.
 
+--backward times forward + backward instead: `ensemble_log_probs(..., differentiable=True)` and one
+launch of `sca_ensemble_log_probs_bwd` for all members, against autograd through the same torch
+composition, under one fixed incoming gradient N(0, 1); every variant owns its leaves.  The members'
+gradients of the two forms are compared (maximum absolute difference) before anything is timed, on
+leaves of their own.  The bytes are the forward's plus the backward's: "prob" reads the G members,
+out and dout and writes G gradients, "logprob" reads out and dout and writes G gradients.
+
 Usage: python tools/ensemble_bench.py [--B 8] [--T 64] [--C 1124] [--members 2 5] [--calls 100]
-                                      [--replays 5] [--windows 7]
+                                      [--replays 5] [--windows 7] [--backward]
 """
 import argparse
 import json
@@ -46,6 +53,8 @@ def main():
     ap.add_argument("--calls", type=int, default=100)
     ap.add_argument("--replays", type=int, default=5)
     ap.add_argument("--windows", type=int, default=7)
+    ap.add_argument("--backward", action="store_true", help="time forward + backward of the differentiable call "
+                                                             "against autograd through the torch composition")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("ensemble_bench: needs a GPU; nothing is measured without one")
@@ -53,14 +62,39 @@ def main():
     from scattennet_amd.ensemble import MODES
     dev = torch.device("cuda")
     gen = torch.Generator().manual_seed(0)
-    out = {"workload": "ensemble_log_probs against the torch composition it replaces; captured graphs, device events",
+    what = "ensemble_log_probs forward + backward against autograd through" if a.backward else "ensemble_log_probs against"
+    out = {"workload": what + " the torch composition it replaces; captured graphs, device events",
            "B": a.B, "T": a.T, "C": a.C, "calls_per_graph": a.calls, "replays_per_window": a.replays,
            "windows": a.windows, "unit": "us per call", "cases": []}
     for G in a.members:
         xs = [(torch.randn(a.B, a.T, a.C, generator=gen) * 3).to(dev) for _ in range(G)]
         weights = [1.0 / G] * G
         graphs, diff = {}, {}
-        for mode in MODES:
+        dout = torch.randn(a.B, a.T, a.C, generator=gen).to(dev)
+
+        def leaves():
+            return [x.detach().clone().requires_grad_(True) for x in xs]
+
+        def fwd_bwd(form, mode, zs):
+            def fn():
+                for z in zs:
+                    z.grad = None
+                y = S.ensemble_log_probs(zs, None, mode, differentiable=True) if form == "fused" else \
+                    torch_composition(zs, weights, mode)
+                y.backward(dout)
+                return [z.grad for z in zs]
+            return fn
+
+        for mode in MODES if a.backward else ():
+            side = torch.cuda.Stream()  # the comparison, on leaves of its own and off the default stream
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                gf, gt = fwd_bwd("fused", mode, leaves())(), fwd_bwd("torch", mode, leaves())()
+                diff[mode] = max(float((p - q).abs().max()) for p, q in zip(gf, gt))
+            torch.cuda.current_stream().wait_stream(side)
+            graphs[f"fused_{mode}"] = graph_of(fwd_bwd("fused", mode, leaves()), a.calls)
+            graphs[f"torch_{mode}"] = graph_of(fwd_bwd("torch", mode, leaves()), a.calls)
+        for mode in () if a.backward else MODES:
             fused = lambda mode=mode: S.ensemble_log_probs(xs, None, mode)  # noqa: E731
             composed = lambda mode=mode: torch_composition(xs, weights, mode)  # noqa: E731
             diff[mode] = float((fused() - composed()).abs().max())
@@ -69,14 +103,18 @@ def main():
         for gr, _ in graphs.values():
             gr.replay()
         torch.cuda.synchronize()
-        nbytes = (G + 1) * a.B * a.T * a.C * 4
-        case = {"G": G, "bytes_moved_at_least": nbytes, "max_abs_diff_fused_vs_torch": diff}
+        row = a.B * a.T * a.C * 4
+        nbytes = {mode: (G + 1) * row for mode in MODES}
+        if a.backward:
+            nbytes = {"prob": (G + 1 + 2 * G + 2) * row, "logprob": (G + 1 + G + 2) * row}
+        case = {"G": G, "bytes_moved_at_least": nbytes if a.backward else (G + 1) * row,
+                "max_abs_diff_fused_vs_torch": diff}
         case.update(alternated(graphs, a.calls, a.replays, a.windows))
         for mode in MODES:
             f, t = case[f"fused_{mode}"], case[f"torch_{mode}"]
             case[f"torch_over_fused_{mode}"] = round(t["median"] / f["median"], 2)
             case[f"fused_below_torch_range_{mode}"] = f["median"] < t["min"]
-            case[f"fused_GBps_{mode}"] = round(nbytes / (f["median"] * 1e-6) / 1e9, 1)
+            case[f"fused_GBps_{mode}"] = round(nbytes[mode] / (f["median"] * 1e-6) / 1e9, 1)
         out["cases"].append(case)
     print(json.dumps(out))
 

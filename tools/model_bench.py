@@ -55,7 +55,10 @@ third pass takes its list from the fused search (Rescoring(..., fusion=True)), i
 windows, ms per step and the per-window difference, and the mean mwer_risk / mwer_loss of the stream.
 --mwer-reference / --mwer-lm / --mwer-heads 2 add a third step in the same alternation whose spec has the
 reference as a list entry / a bigram table in the posterior / both CTC heads in one grouped call, with the
-stream's statistics for that spec.
+stream's statistics for that spec.  --ensemble (with --mixed --mwer) puts the five-member ensemble
+(MWER(head=EnsembleSpec(...)), its forward and backward inside every bucket's graph) in place of that step's
+first head: the figure to compare is the third step's minus the `mwer` step's, which trains the fuse head.
+--ensemble-members left,right,body names other members than all five.
 """
 import argparse
 import json
@@ -271,10 +274,15 @@ def mixed_mwer(a, dev):
     buckets = tuple(int(b) for b in a.buckets.split(","))
     steps = {}
     variants = [("plain", None), ("mwer", S.MWER(0.5, beam_size=a.beam))]
-    if a.mwer_reference or a.mwer_lm or a.mwer_heads > 1:
+    if a.mwer_reference or a.mwer_lm or a.mwer_heads > 1 or a.ensemble:
         # a third step with the extended spec: the reference as a list entry, the gloss model's
-        # prior (a random normalised table, weight 0.5), the first --mwer-heads CTC heads grouped
+        # prior (a random normalised table, weight 0.5), the first --mwer-heads CTC heads grouped;
+        # --ensemble: the five-member ensemble in place of the first head (its backward in the graph)
         names = ("fuse_coord_gloss_logits", "alignment_gloss_logits")[:max(a.mwer_heads, 1)]
+        if a.ensemble:
+            from scattennet_amd.model import _LOGITS
+            members = tuple(a.ensemble_members.split(",")) if a.ensemble_members else _LOGITS
+            names = (S.EnsembleSpec(members),) + names[1:]
         lm = None
         if a.mwer_lm:
             table = torch.log_softmax(torch.randn(a.C, a.C, generator=torch.Generator().manual_seed(a.seed + 7)) * 2, -1)
@@ -308,7 +316,8 @@ def mixed_mwer(a, dev):
             loss.append(rep["mwer_loss"])
             skipped += rep["skipped"]
             # the same list and loss once more on the step's logits, for the per-clip figures
-            z = out[spec.heads[0]].detach().clone().requires_grad_(True)
+            head = spec.heads[0]  # a logit key, or the EnsembleSpec of --ensemble
+            z = (out[head] if isinstance(head, str) else head.compute(out)).detach().clone().requires_grad_(True)
             nb = S.ctc_decode_nbest_device(z, out["input_lengths"], a.beam, a.beam, collapse_repeats=False)
             l, det = S.mwer_loss(z, out["input_lengths"], src["gloss_labels"], src["gloss_lengths"], nbest=nb,
                                  return_details=True, reference=spec.reference, lm=spec.lm, lm_weight=spec.lm_weight,
@@ -541,7 +550,10 @@ def main():
     ap.add_argument("--align", action="store_true", help="with --mixed --eval: the bucketed pass with and without "
                                                          "the forced alignment of every hypothesis")
     ap.add_argument("--ensemble", action="store_true", help="with --mixed --eval: the bucketed pass with and without "
-                                                            "one five-member ensemble beside the two default heads")
+                                                            "one five-member ensemble beside the two default heads; "
+                                                            "with --mixed --mwer: a third step that trains on it")
+    ap.add_argument("--ensemble-members", default=None, help="with --mixed --mwer --ensemble: the members, logit keys "
+                                                             "separated by commas (default: all five)")
     ap.add_argument("--fusion", action="store_true", help="with --mixed --eval --rescore: a third pass whose list "
                                                           "comes from the fused search (Rescoring(fusion=True))")
     ap.add_argument("--rescore", default=None, help="with --mixed --eval: N[:score|mbr], the bucketed pass with and "

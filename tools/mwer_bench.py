@@ -21,11 +21,13 @@ Needs a GPU.
 
 --reference, --lm, --heads G time the extended loss (the reference as a list entry, the bigram table
 inside the posterior, G tensors in one grouped call) beside its yardsticks instead: see `extended`.
+--ensemble G times the loss on the differentiable ensemble of G member tensors beside the loss on the
+torch composition of the same members (autograd through log_softmax / stack / logsumexp): see `on_ensemble`.
 --dump PATH saves the plain loss's outputs and gradient, for a bit-for-bit comparison of two builds
 (SCA_LIB_PATH selects the library).
 
 Usage: python tools/mwer_bench.py [--B 8] [--T 64] [--C 1124] [--beam 5] [--nbest 5] [--steps 200]
-                                  [--reference] [--lm] [--heads G] [--dump PATH]
+                                  [--reference] [--lm] [--heads G] [--ensemble G] [--dump PATH]
 """
 import argparse
 import json
@@ -135,8 +137,79 @@ def extended(a, S, dev):
     print(json.dumps(res))
 
 
+def on_ensemble(a, S, dev):
+    """--ensemble G: MWER forward + backward on the ensemble of G members, in both modes, one list per
+    mode (the decoder's, on the detached ensemble) and the references of `extended`; captured graphs in
+    alternated windows, every variant on leaves of its own.
+    * `op_<mode>`      ensemble_log_probs(members, differentiable=True) -> mwer_loss -> backward: the
+                       ensemble's forward and its one backward launch around the loss
+    * `torch_<mode>`   the torch composition of the same members -> mwer_loss -> backward
+    * `loss_<mode>`    mwer_loss -> backward on the ensemble as a leaf: the loss alone"""
+    from tools.ensemble_bench import torch_composition
+    g = torch.Generator().manual_seed(0)
+    G, N = a.ensemble, a.nbest
+    xs = [(torch.randn(a.B, a.T, a.C, generator=g) * 4).to(dev) for _ in range(G)]
+    weights = [1.0 / G] * G
+    il = torch.full((a.B,), a.T, dtype=torch.int32, device=dev)
+    kw = dict(reference=a.reference)
+    fns, diff, stats = {}, {}, {}
+
+    def leaves():
+        return [x.detach().clone().requires_grad_(True) for x in xs]
+
+    for mode in ("prob", "logprob"):
+        ens = S.ensemble_log_probs(xs, None, mode)
+        nb = S.ctc_decode_nbest_device(ens, il, a.beam, N, collapse_repeats=False)
+        pick = min(1, N - 1)
+        ref_len = nb.lengths[:, pick].contiguous()
+        R = max(int(ref_len.max()), 1)
+        ref = nb.tokens[:, pick, :R].clone()
+        mid = (ref_len // 2).clamp(max=R - 1).long()[:, None]
+        ref.scatter_(1, mid, (ref.gather(1, mid) % (a.C - 1)) + 1)  # another class in [1, C)
+
+        def chain(form, zs, mode=mode, nb=nb, ref=ref, ref_len=ref_len):
+            def fn():
+                for z in zs:
+                    z.grad = None
+                y = zs[0] if form == "loss" else S.ensemble_log_probs(zs, None, mode, differentiable=True) \
+                    if form == "op" else torch_composition(zs, weights, mode)
+                loss = S.mwer_loss(y, il, ref, ref_len, nbest=nb, **kw)
+                loss.backward()
+                return loss.detach(), [z.grad for z in zs]
+            return fn
+
+        side = torch.cuda.Stream()  # the comparison and the statistics, off the default stream
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            (lo, go), (lt, gt) = chain("op", leaves())(), chain("torch", leaves())()
+            diff[mode] = {"loss": float((lo - lt).abs()), "gradients": max(float((p - q).abs().max()) for p, q in zip(go, gt))}
+            stats[mode] = {"loss": round(float(lo), 6),
+                           "gradient_rows_non_zero": round(float((go[0].abs().amax(-1) > 0).float().mean()), 4)}
+        torch.cuda.current_stream().wait_stream(side)
+        fns[f"op_{mode}"] = chain("op", leaves())
+        fns[f"torch_{mode}"] = chain("torch", leaves())
+        fns[f"loss_{mode}"] = chain("loss", [ens.clone().requires_grad_(True)])
+    replays = {}
+    for name, fn in fns.items():
+        replays[name] = graphed(fn)
+        for _ in range(a.warmup):
+            replays[name]()
+    timed = alternated(replays, a.steps, a.repeats)
+    res = {"workload": "MWER loss forward + backward on the differentiable ensemble beside the torch composition "
+                       "of the same members, graph replays", "B": a.B, "T": a.T, "C": a.C, "beam": a.beam, "nbest": N,
+           "members": G, "reference": a.reference, "steps": a.steps, "repeats": a.repeats, "unit": "us per call",
+           "statistics": stats, "max_abs_diff_op_vs_torch": diff, "graph": timed}
+    for mode in ("prob", "logprob"):
+        res[f"torch_over_op_{mode}"] = round(timed[f"torch_{mode}"]["median"] / timed[f"op_{mode}"]["median"], 3)
+        res[f"op_minus_loss_{mode}"] = round(timed[f"op_{mode}"]["median"] - timed[f"loss_{mode}"]["median"], 2)
+        res[f"torch_minus_loss_{mode}"] = round(timed[f"torch_{mode}"]["median"] - timed[f"loss_{mode}"]["median"], 2)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--ensemble", type=int, default=0, help="time the loss on the differentiable ensemble of G "
+                    "members beside the loss on their torch composition (with --reference: the slot on)")
     ap.add_argument("--reference", action="store_true", help="time reference=True beside N and N + 1 entries")
     ap.add_argument("--lm", action="store_true", help="time the bigram table inside the posterior")
     ap.add_argument("--heads", type=int, default=1, help="time one grouped call over G tensors beside G calls")
@@ -156,6 +229,8 @@ def main():
     import scattennet_amd as S
     from scattennet_amd.heads import CTCLossOp
     dev = torch.device("cuda")
+    if a.ensemble:
+        return on_ensemble(a, S, dev)
     if a.reference or a.lm or a.heads > 1:
         return extended(a, S, dev)
     g = torch.Generator().manual_seed(0)
