@@ -118,6 +118,7 @@ CASES = {
     (4, 12, 6, 8, 3): (0, [12, 0, 1, 7]),
     (3, 20, 33, 32, 32): (0, [20, 1, 13]),
     (2, 64, 1124, 5, 5): (0, [64, 37]),
+    (2, 128, 12, 8, 8): (0, [128, 97]),  # nbest_ref's long case: entries of more than 64 tokens
 }
 
 

@@ -155,6 +155,9 @@ CASES = {
     (4, 12, 6, 8, 3): (0, [12, 0, 1, 7]),          # N < W
     (3, 20, 33, 32, 32): (0, [20, 1, 13]),         # the widest beam and list
     (2, 64, 1124, 5, 5): (0, [64, 37]),            # the evaluation shape
+    # T = 128, the limit of sca_nbest_mbr: entries of 102-104 and 78-79 tokens, so the rescoring
+    # wave sums more than 64 gathers and MWER's lattices have L = 205-209 and 157-159
+    (2, 128, 12, 8, 8): (0, [128, 97]),
 }
 
 

@@ -34,6 +34,7 @@ BEAM_CASES = {
     # fewer labels than W + 1; pruned prefixes come back here while a child of theirs is still active
     (5, 16, 4, 8): (0, [16, 0, 1, 9, 16]),
     (1, 4, 8192, 32): (0, [4]),                             # the class limit
+    (2, 128, 12, 8): (0, [128, 97]),                        # outputs of more than 64 tokens (nbest_ref's logits)
 }
 EXHAUSTIVE_CASE = ((4, 4, 3, 32), 0)
 
@@ -336,7 +337,8 @@ def _torch_greedy(x, lens):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("B,T,C,lens", [(8, 64, 1124, [64, 0, 1, 37, 64, 50, 13, 64]), (3, 37, 70, [37, 20, 1])])
+@pytest.mark.parametrize("B,T,C,lens", [(8, 64, 1124, [64, 0, 1, 37, 64, 50, 13, 64]), (3, 37, 70, [37, 20, 1]),
+                                        (2, 128, 12, [128, 97])])
 def test_hip_greedy_decode_matches_torch(B, T, C, lens):
     import scattennet_amd as S
     # a small spread, so that blanks and repeats do occur among the arg-maxima
