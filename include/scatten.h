@@ -58,6 +58,8 @@
  *                          log-probabilities, decoded as one more head
  *   sca_ensemble_log_probs_bwd  (no counterpart) its vector-Jacobian product, which makes the
  *                          ensemble a tensor the training losses can be taken on
+ *   sca_ensemble_log_probs_dw, _dw_bwd  (no counterpart) the same pair with learned weights, the
+ *                          softmax of scores on the device, and the gradient of those scores
  *   sca_ctc_beam_decode*_nbest  (no counterpart; the interface of the decoder's top_paths) the N
  *   sca_nbest_rescore/mbr/gather  best labellings of the beam search, their rescoring with a
  *                          bigram gloss model, the posterior over the list and MBR selection
@@ -1001,6 +1003,47 @@ typedef struct {
 int sca_ensemble_log_probs_bwd(const sca_decode_heads* heads, int G, const sca_ensemble_weights* weights,
                                int mode, int B, int T, int C, const float* out, const float* dout,
                                const sca_ensemble_grads* dlogits, void* stream);
+
+/* The same ensemble with learned weights: weight_logits (G) fp32 on the device are G unconstrained
+ * scores theta, and W = softmax(theta) takes the place of the host weights above (positive and
+ * normalised by construction; theta = 0 gives equal weights).  The kernel reads theta from memory,
+ * so nothing about the weights is frozen in a captured graph: a replay after an optimizer step or
+ * a load_state_dict on theta computes with the new weights.  Every wave computes
+ * log W_g = (theta_g - max theta) - log sum_g exp(theta_g - max theta) and W_g = exp(log W_g) once
+ * (G wave-uniform loads), the same function in the forward and the backward; the row arithmetic,
+ * the launch shape and the guarantees are those of sca_ensemble_log_probs.  Specified for finite
+ * theta.  SCA_ERR_ARG before any GPU call: the checks of sca_ensemble_log_probs on heads, G, mode
+ * and sizes; a null weight_logits or out; weight_logits that is out or a member.
+ *
+ * sca_ensemble_log_probs_dw_bwd: the members' gradients are exactly those of
+ * sca_ensemble_log_probs_bwd with W from theta (a null entry of dlogits is skipped), and
+ * dweight_logits (G) fp32, or NULL for "theta takes no gradient", is d theta summed over all
+ * B T rows.  Per row, with r_g, du and q as above and D = sum_c dout[c]:
+ *   mode 0:  d theta_g += s_g - W_g D,  s_g = sum_c r_g[c] dout[c]
+ *            (the s_g of the members' gradient, here formed for every member, also one whose
+ *            dlogits entry is null)
+ *   mode 1:  d theta_g += W_g sum_c du[c] (lp_g[c] - out[c])
+ *            (out in the place of u is exact because sum_c du = 0; with dweight_logits the
+ *            members and their row statistics are read in this mode too, without it still not)
+ * sum_g d theta_g = 0 up to rounding; a row with dout = 0 contributes exactly 0; with G = 1 the
+ * entry writes dweight_logits[0] = 0 (a 4-byte memset) and computes nothing for it.
+ *
+ * The sum over the rows takes two launches.  The row kernel (one wave per row as above, no LDS, no
+ * barrier) stores its row's G partials into ws (B T, G) with plain stores; then one workgroup
+ * sums them in a fixed order: thread t adds the rows t, t + 256, ... ascending, and an LDS tree
+ * adds the 256 threads.  No float atomics and no counter: d theta depends on the partials alone,
+ * and a replayed capture is bitwise the eager call.  ws: sca_ensemble_log_probs_dw_workspace_bytes
+ * (G, B, T) bytes (0 for G = 1 or sizes out of range), needed only with dweight_logits and
+ * G >= 2.  With dweight_logits NULL and every dlogits entry null nothing is launched.
+ * SCA_ERR_ARG before any GPU call: the forward's checks; a null out, dout or dlogits; out ==
+ * dout; weight_logits that is out or dout; a null ws where it is needed; a non-null gradient
+ * tensor, dweight_logits or ws that is out, dout, weight_logits, a member or another of them.  */
+int sca_ensemble_log_probs_dw(const sca_decode_heads* heads, int G, const float* weight_logits, int mode, int B,
+                              int T, int C, float* out, void* stream);
+long sca_ensemble_log_probs_dw_workspace_bytes(int G, int B, int T);
+int sca_ensemble_log_probs_dw_bwd(const sca_decode_heads* heads, int G, const float* weight_logits, int mode,
+                                  int B, int T, int C, const float* out, const float* dout,
+                                  const sca_ensemble_grads* dlogits, float* dweight_logits, void* ws, void* stream);
 
 /* SeqKD over R rows of C logits (student, teacher): columns [start, C) only (use_blank=False
  * -> start 1), temperature temp:

@@ -23,7 +23,8 @@ from .optim import FusedAdam, WarmupCosineAnnealingScheduler, build_optimizer, c
 from .model import MSCA_Net, finite_flags, first_error  # noqa: F401
 from .train import read_report, train_step  # noqa: F401
 from .bucketed import BucketedStep, BucketedTrainStep, pad_batch  # noqa: F401
-from .ensemble import EnsembleLogProbsOp, EnsembleSpec, ensemble_log_probs  # noqa: F401
+from .ensemble import EnsembleLogProbsOp, EnsembleSpec, LearnedEnsemble, LearnedEnsembleLogProbsOp  # noqa: F401
+from .ensemble import ensemble_log_probs  # noqa: F401
 from .mwer import MWER, MWERLossOp, mwer_guard, mwer_loss  # noqa: F401
 from .nbest import (BigramLM, NBest, Rescoring, ctc_decode_fused_nbest, ctc_decode_fused_nbest_device,  # noqa: F401
                     ctc_decode_fused_nbest_heads_device, ctc_decode_nbest, ctc_decode_nbest_device,

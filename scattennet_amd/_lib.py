@@ -253,6 +253,9 @@ EXPORTS = {
     "sca_eval_log_alignments": ([c_void_p] * 3 + [c_int] * 3 + [c_void_p] * 4 + [c_int, c_int, c_void_p], c_int),
     "sca_ensemble_log_probs": ([c_void_p, c_int, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p], c_int),
     "sca_ensemble_log_probs_bwd": ([c_void_p, c_int, c_void_p] + [c_int] * 4 + [c_void_p] * 4, c_int),
+    "sca_ensemble_log_probs_dw": ([c_void_p, c_int, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p], c_int),
+    "sca_ensemble_log_probs_dw_workspace_bytes": ([c_int] * 3, c_long),
+    "sca_ensemble_log_probs_dw_bwd": ([c_void_p, c_int, c_void_p] + [c_int] * 4 + [c_void_p] * 6, c_int),
     "sca_optim_blocks": ([c_int, c_int], c_int),
     "sca_optim_grad_sqnorm": ([c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
     "sca_optim_adam_step": ([c_void_p, c_void_p, c_int, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p],

@@ -20,7 +20,7 @@ from . import heads
 from .encoder import n_pool_of
 from .model import _LOGITS
 from .mwer import check_mwer
-from .train import train_step
+from .train import step_parameters, train_step
 
 
 def pad_batch(src_input, frames, labels=None):
@@ -286,7 +286,7 @@ class BucketedTrainStep(BucketedStep):
     def _before_capture(self):
         # No autograd graph of an earlier step is alive (every step handed out detached outputs
         # only) and the group table is current; the gradients of the last step are dropped so
-        # that the graph's own live in its pool.
-        for p in self.model.parameters():
+        # that the graph's own live in its pool (a LearnedEnsemble head's among them).
+        for p in step_parameters(self.model, self.mwer):
             p.grad = None
         self._before_replay()  # the captured step reads the same hyper-parameter table

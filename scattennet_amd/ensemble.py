@@ -14,6 +14,12 @@ posteriors, the tensor the multi-stream recognisers decode next to the single he
   the decoded heads (`EvalState`, `BucketedEvalStep`, `recognize_step`), and `add_ensembles`
   computes them into a head-output dict.
 
+* `LearnedEnsemble(members, mode="prob", init=None)` — the same with learned weights: an
+  `nn.Module` whose one parameter `weight_logits` (G,) stays on the device; the weights are its
+  softmax, computed inside the kernels (`sca_ensemble_log_probs_dw`, `_dw_bwd`), and
+  `ensemble_log_probs(..., weight_logits=...)` is the call underneath.  Accepted wherever an
+  `EnsembleSpec` is; `freeze()` gives the `EnsembleSpec` with the weights of the moment.
+
 The reference has no ensemble; the semantics are the header's.
 """
 import ctypes
@@ -102,12 +108,67 @@ class EnsembleLogProbsOp(Function):
         return (None, None) + tuple(dxs)
 
 
+def _launch_forward_dw(xs, theta, mode):
+    """`sca_ensemble_log_probs_dw` on contiguous fp32 device tensors: the new (B, T, C) output."""
+    L.require_device(theta, *xs)
+    B, T, C = xs[0].shape
+    out = torch.empty_like(xs[0])
+    hx = L.decode_heads(xs)
+    L.check(L.lib().sca_ensemble_log_probs_dw(ctypes.byref(hx), len(xs), L.ptr(theta), mode, B, T, C, L.ptr(out),
+                                              L.stream_handle()), "sca_ensemble_log_probs_dw")
+    return out
+
+
+class LearnedEnsembleLogProbsOp(Function):
+    """`sca_ensemble_log_probs_dw` with its vector-Jacobian product (`sca_ensemble_log_probs_dw_bwd`):
+    `mode` (0 / 1), the (G,) fp32 device scores `theta` (the weights are softmax(theta), computed in
+    the kernel from the tensor's current contents) and the G fp32 device logits `*logits`.  The
+    output is bitwise the detached call's.  The backward gives the members' gradients as
+    `EnsembleLogProbsOp` does (a member that needs none is a null entry) and, when `theta` requires
+    one, d theta (G): per-row partials in a workspace, summed by a second launch in a fixed order."""
+
+    @staticmethod
+    def forward(ctx, mode, theta, *logits):
+        xs = [x.contiguous() for x in logits]
+        theta = theta.contiguous()
+        out = _launch_forward_dw(xs, theta, mode)
+        ctx.save_for_backward(out, theta, *xs)
+        ctx.mode = mode
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        out, theta, *xs = ctx.saved_tensors
+        G = len(xs)
+        B, T, C = out.shape
+        dout = dout.contiguous()
+        L.require_device(dout)
+        dxs = [torch.empty_like(x) if ctx.needs_input_grad[2 + g] else None for g, x in enumerate(xs)]
+        dtheta = ws = None
+        if ctx.needs_input_grad[1]:
+            dtheta = torch.empty_like(theta)
+            ws = L.workspace(L.lib().sca_ensemble_log_probs_dw_workspace_bytes(G, B, T), out.device)
+        hx, gx = L.decode_heads(xs), L.EnsembleGrads()
+        for g in range(G):
+            gx.dlogits[g] = None if dxs[g] is None else dxs[g].data_ptr()
+        L.check(L.lib().sca_ensemble_log_probs_dw_bwd(ctypes.byref(hx), G, L.ptr(theta), ctx.mode, B, T, C, L.ptr(out),
+                                                      L.ptr(dout), ctypes.byref(gx), L.ptr(dtheta), L.ptr(ws),
+                                                      L.stream_handle()), "sca_ensemble_log_probs_dw_bwd")
+        return (None, dtheta) + tuple(dxs)
+
+
 class _Ensembler(nn.Module):
     """Parameter-free module, so that fp16 / bf16 logits take the fp32 view of fp32_compute (and,
-    on the differentiable path, receive their gradients in their own dtype through its casts)."""
+    on the differentiable path, receive their gradients in their own dtype through its casts).
+    `weight_logits` (None: host `weights`) comes after the members, so the members' dtype decides
+    the module's; `ensemble_log_probs` hands it over as fp32 already."""
 
     @fp32_compute()
-    def forward(self, weights, mode, differentiable, *logits):
+    def forward(self, weights, mode, differentiable, *logits, weight_logits=None):
+        if weight_logits is not None:
+            if differentiable:
+                return LearnedEnsembleLogProbsOp.apply(mode, weight_logits, *logits)
+            return _launch_forward_dw([x.detach().contiguous() for x in logits], weight_logits.detach().contiguous(), mode)
         if differentiable:
             return EnsembleLogProbsOp.apply(weights, mode, *logits)
         return _launch_forward([x.detach().contiguous() for x in logits], weights, mode)
@@ -116,7 +177,22 @@ class _Ensembler(nn.Module):
 _ensembler = _Ensembler()
 
 
-def ensemble_log_probs(logits_list, weights=None, mode="prob", *, differentiable=False):
+def _check_weight_logits(theta, xs, what):
+    """The learned weights' scores: a floating (G,) tensor on the members' device.  ValueError
+    otherwise, before any launch."""
+    if not torch.is_tensor(theta):
+        raise ValueError(f"{what}: weight_logits must be a ({len(xs)},) tensor, got {type(theta).__name__}")
+    if theta.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise ValueError(f"{what}: weight_logits must be fp32, fp16 or bf16, got {theta.dtype}")
+    if tuple(theta.shape) != (len(xs),):
+        raise ValueError(f"{what}: weight_logits must have shape ({len(xs)},), one score per member, got "
+                         f"{tuple(theta.shape)}")
+    if theta.device != xs[0].device:
+        raise ValueError(f"{what}: weight_logits must be on the members' device {xs[0].device}, got {theta.device}")
+    return theta
+
+
+def ensemble_log_probs(logits_list, weights=None, mode="prob", *, weight_logits=None, differentiable=False):
     """The ensemble of G heads' posteriors as normalised log-probabilities, in one launch
     (`sca_ensemble_log_probs`).  `logits_list`: 1..8 tensors of one shape (B, T, C); `weights`:
     None (equal) or G finite positive numbers, normalised by their sum; `mode`: "prob", the
@@ -125,12 +201,28 @@ def ensemble_log_probs(logits_list, weights=None, mode="prob", *, differentiable
     log_softmax.  Returns a detached (B, T, C) device tensor; with `differentiable=True` the same
     bits attached to the members (`EnsembleLogProbsOp`: one more launch in the backward, for all
     the members that require a gradient; fp16 / bf16 members receive theirs in their own dtype).
-    The weights take no gradient.  No host sync; capturable, the backward too."""
+    The host `weights` take no gradient.  No host sync; capturable, the backward too.
+
+    `weight_logits` (instead of `weights`; giving both is a ValueError): a (G,) floating tensor of
+    unconstrained scores on the members' device; the weights are softmax(weight_logits), computed
+    inside the kernel from the tensor's contents at launch (`sca_ensemble_log_probs_dw`), so a
+    captured graph follows every in-place change of it.  With `differentiable=True` it receives
+    its gradient when it requires one (`LearnedEnsembleLogProbsOp`: the per-row partials and a
+    second launch that sums them in a fixed order; an fp16 / bf16 tensor receives it in its own
+    dtype)."""
     if not isinstance(differentiable, bool):
         raise ValueError(f"ensemble_log_probs: differentiable must be a bool, got {differentiable!r}")
     xs = check_heads(logits_list, "ensemble_log_probs")
     if xs[0].numel() == 0:
         raise ValueError(f"ensemble_log_probs: empty logits {tuple(xs[0].shape)}")
+    if weight_logits is not None:
+        if weights is not None:
+            raise ValueError("ensemble_log_probs: give weights (host constants) or weight_logits (learned, on the "
+                             "device), not both")
+        theta = _check_weight_logits(weight_logits, xs, "ensemble_log_probs")
+        m = _check_mode(mode, "ensemble_log_probs")
+        check_on_device(None, xs[0])
+        return _ensembler(None, m, differentiable, *xs, weight_logits=theta.float())
     ws = _check_weights(weights, len(xs), "ensemble_log_probs")
     m = _check_mode(mode, "ensemble_log_probs")
     check_on_device(None, xs[0])
@@ -164,9 +256,56 @@ class EnsembleSpec:
                                   differentiable=differentiable)
 
 
+class LearnedEnsemble(nn.Module):
+    """An ensemble of the model's heads whose weights are learned: one parameter `weight_logits`
+    (G,) fp32, the weights being softmax(weight_logits) (`ensemble_log_probs(weight_logits=...)`).
+    `members` and `mode` as `EnsembleSpec` takes and validates them; `init`: None (zeros: equal
+    weights) or G finite positive numbers, the parameter starting at the log of their normalised
+    values.  It stands wherever an `EnsembleSpec` does: in the `ensembles` of `EvalState`,
+    `BucketedEvalStep`, `recognize_step` and `BucketedRecognizer`, and as a head of `MWER`, where
+    the steps also clear its gradient.  The kernels read the parameter from device memory, so a
+    captured step follows an optimizer update or `load_state_dict` without recapture.  The module
+    lives outside `MSCA_Net` (whose checkpoints load unchanged); its parameter reaches the
+    optimizer as `FusedAdam(list(model.parameters()) + list(ens.parameters()), ...)`, and it moves
+    to the model's device like any module (`.to(device)`)."""
+
+    def __init__(self, members, mode="prob", init=None):
+        super().__init__()
+        spec = EnsembleSpec(members, None, mode)
+        self.members, self.mode = spec.members, spec.mode
+        if init is None:
+            theta = torch.zeros(len(self.members))
+        else:
+            ws = _check_weights(init, len(self.members), "LearnedEnsemble")
+            theta = torch.tensor([math.log(w) for w in ws], dtype=torch.float32)
+        self.weight_logits = nn.Parameter(theta)
+
+    def __repr__(self):  # no host read of the parameter
+        return f"LearnedEnsemble(members={self.members!r}, mode={self.mode!r})"
+
+    def compute(self, outputs, differentiable=False):
+        return ensemble_log_probs([outputs[k] for k in self.members], None, self.mode,
+                                  weight_logits=self.weight_logits, differentiable=differentiable)
+
+    def weights(self):
+        """softmax(weight_logits) as a tuple of Python floats: one explicit host read."""
+        theta = self.weight_logits.detach().cpu().double()
+        return tuple(torch.softmax(theta, 0).tolist())
+
+    def freeze(self):
+        """The plain `EnsembleSpec` with the current weights as host constants (one host read),
+        for deployment on the host-weight path."""
+        return EnsembleSpec(self.members, self.weights(), self.mode)
+
+
+def learned_ensembles(heads):
+    """The `LearnedEnsemble`s among an `MWER`'s heads (or any sequence of keys and specs)."""
+    return [h for h in heads if isinstance(h, LearnedEnsemble)]
+
+
 def check_ensembles(heads, ensembles, what):
-    """The `{output_key: EnsembleSpec}` dict of an evaluation or recognition step, validated on
-    the host against the decoded `heads`: every key contains "gloss_logits" (the reference's
+    """The `{output_key: EnsembleSpec}` dict of an evaluation or recognition step (a value may also
+    be a `LearnedEnsemble`), validated on the host against the decoded `heads`: every key contains "gloss_logits" (the reference's
     evaluate_fn loop would pick it up), is none of the five logit keys, and heads plus ensembles
     are at most 8 decoded tensors.  Returns the dict (empty for None), in insertion order."""
     if ensembles is None:
@@ -178,8 +317,9 @@ def check_ensembles(heads, ensembles, what):
             raise ValueError(f"{what}: an ensemble's output key must contain 'gloss_logits', got {key!r}")
         if key in _LOGITS:
             raise ValueError(f"{what}: the ensemble key {key!r} is one of the model's own logit keys {_LOGITS}")
-        if not isinstance(spec, EnsembleSpec):
-            raise ValueError(f"{what}: ensembles[{key!r}] must be an EnsembleSpec, got {type(spec).__name__}")
+        if not isinstance(spec, (EnsembleSpec, LearnedEnsemble)):
+            raise ValueError(f"{what}: ensembles[{key!r}] must be an EnsembleSpec or a LearnedEnsemble, got "
+                             f"{type(spec).__name__}")
     if len(heads) + len(ensembles) > MAX_HEADS:
         raise ValueError(f"{what}: {len(heads)} heads and {len(ensembles)} ensembles are more than the {MAX_HEADS} "
                          "tensors one grouped decode takes")

@@ -22,7 +22,7 @@ import torch
 from torch.autograd import Function
 
 from . import _lib as L
-from .ensemble import EnsembleSpec
+from .ensemble import EnsembleSpec, LearnedEnsemble
 from .decode import MAX_BEAM, WER_MAX_LEN, _check_lengths, _check_logits, check_heads, check_on_device
 from .heads import _dev_i32
 from .model import _LOGITS
@@ -229,7 +229,9 @@ class MWER:
     come from one grouped call and the step adds `weight` times their sum.  `head`, or an entry of
     the tuple (at most 8 entries), may also be an `EnsembleSpec` (distinct objects): the step
     computes that ensemble of its own logits with `differentiable=True` and takes the loss on it
-    like on any head, so the gradient reaches every member.  `reference`, `lm`
+    like on any head, so the gradient reaches every member; a `LearnedEnsemble` stands where an
+    `EnsembleSpec` does, and its `weight_logits` takes a gradient too (the steps clear it with the
+    model's).  `reference`, `lm`
     (a `BigramLM` on the model's device, or a (C, C) table), `lm_weight`, `length_bonus` and
     `fusion` are `mwer_loss`'s: the reference as one more entry of every list, the gloss model's
     prior inside the posterior, the list from the fused search.  ValueError for anything else."""
@@ -256,7 +258,7 @@ class MWER:
         if not 1 <= len(names) <= MAX_HEADS:
             raise ValueError(f"MWER: between 1 and {MAX_HEADS} heads, got {len(names)}")
         for name in names:
-            if isinstance(name, EnsembleSpec):
+            if isinstance(name, (EnsembleSpec, LearnedEnsemble)):
                 continue
             if not isinstance(name, str) or name not in _LOGITS:
                 raise ValueError(f"MWER: head must be one of {_LOGITS}, an EnsembleSpec or a tuple of them, got {name!r}")

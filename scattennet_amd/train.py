@@ -27,6 +27,7 @@ import math
 import torch
 
 from . import heads, ops
+from .ensemble import learned_ensembles
 from .model import _students_of, deferred_check, first_error, flag_names, guard_of
 from .model import read_report as model_read_report
 from .mwer import check_mwer, mwer_guard, mwer_loss
@@ -54,6 +55,16 @@ def _add_mwer(outputs, src_input, mwer):
     return outputs["total_loss"] + mwer.weight * loss
 
 
+def step_parameters(model, mwer):
+    """The parameters whose gradients a step clears: the model's and, with an `MWER` that has
+    `LearnedEnsemble`s among its heads, theirs (modules outside the model), so that a weight
+    gradient does not accumulate across steps."""
+    yield from model.parameters()
+    if mwer is not None:
+        for ens in learned_ensembles(mwer.heads):
+            yield from ens.parameters()
+
+
 def train_step(model, optimizer, src_input, mwer=None):
     """One training step of MSCA_Net with FusedAdam, enqueued on the current stream without a
     host read.  Returns the forward's outputs (`finite_report` holds the losses and flags).
@@ -61,9 +72,11 @@ def train_step(model, optimizer, src_input, mwer=None):
     all of them in one grouped call, which also adds `mwer_losses` (G)) into an n-best list,
     adds `mwer_loss`, `mwer_risk` and `mwer_report` to the outputs (the last is the pair
     (mwer_loss, mean risk) as one device tensor, which lets `read_report` keep to a single copy) and
-    back-propagates `total_loss + weight * mwer_loss`; a non-finite `mwer_loss` skips the update on the device like a flagged tensor."""
+    back-propagates `total_loss + weight * mwer_loss`; a non-finite `mwer_loss` skips the update on the device like a flagged tensor.
+    A `LearnedEnsemble` among the heads has its `weight_logits.grad` cleared with the model's and
+    filled by the backward; the optimizer updates it when it was given the parameter."""
     check_mwer(mwer, "train_step")
-    for p in model.parameters():
+    for p in step_parameters(model, mwer):
         p.grad = None
     ops.advance_dropout()
     with deferred_check(model):

@@ -58,7 +58,9 @@ reference as a list entry / a bigram table in the posterior / both CTC heads in 
 stream's statistics for that spec.  --ensemble (with --mixed --mwer) puts the five-member ensemble
 (MWER(head=EnsembleSpec(...)), its forward and backward inside every bucket's graph) in place of that step's
 first head: the figure to compare is the third step's minus the `mwer` step's, which trains the fuse head.
---ensemble-members left,right,body names other members than all five.
+--ensemble-members left,right,body names other members than all five.  --learned adds a fourth step
+with the same members in a LearnedEnsemble (weights on the device, d theta in the graph, the parameter in
+the optimizer), timed in the same alternated windows.
 """
 import argparse
 import json
@@ -290,11 +292,19 @@ def mixed_mwer(a, dev):
         variants.append(("mwer_ext", S.MWER(0.5, beam_size=a.beam, reference=a.mwer_reference, lm=lm,
                                             lm_weight=0.5 if a.mwer_lm else 0.0,
                                             head=names if a.mwer_heads > 1 else names[0])))
+        if a.ensemble and a.learned:
+            # --learned: a fourth step, the same spec with the ensemble's weights learned (a
+            # LearnedEnsemble on the device, its parameter in the optimizer, d theta in the graph)
+            learned = (S.LearnedEnsemble(members).to(dev),) + names[1:]
+            variants.append(("mwer_learned", S.MWER(0.5, beam_size=a.beam, reference=a.mwer_reference, lm=lm,
+                                                    lm_weight=0.5 if a.mwer_lm else 0.0,
+                                                    head=learned if a.mwer_heads > 1 else learned[0])))
     specs = dict(variants)
     for name, spec in variants:
         model, _, w, _ = build(a, dev)
         model.check = "defer"
-        opt = S.FusedAdam(model.parameters(), capture_slots=len(buckets), **adam)
+        extra = [p for h in (spec.heads if spec else ()) if isinstance(h, S.LearnedEnsemble) for p in h.parameters()]
+        opt = S.FusedAdam(list(model.parameters()) + extra, capture_slots=len(buckets), **adam)
         steps[name] = S.BucketedTrainStep(model, opt, a.B, buckets, a.S, mwer=spec)
     n_pool = (len(w["residual_blocks"]) + 1) // 2
     batches = mixed_batches(a, w, dev, n_pool)
@@ -351,6 +361,12 @@ def mixed_mwer(a, dev):
                            "minus_plain_ms_per_step": _spread([x - y for x, y in zip(ms["mwer_ext"], ms["plain"])]),
                            "minus_mwer_ms_per_step": _spread([x - y for x, y in zip(ms["mwer_ext"], ms["mwer"])]),
                            **stream_statistics("mwer_ext")}
+    if "mwer_learned" in steps:
+        ens = specs["mwer_learned"].heads[0]
+        res["mwer_learned"] = {"spec": repr(specs["mwer_learned"]), "ms_per_step": _spread(ms["mwer_learned"]),
+                               "minus_mwer_ext_ms_per_step": _spread([x - y for x, y in zip(ms["mwer_learned"],
+                                                                                            ms["mwer_ext"])]),
+                               **stream_statistics("mwer_learned"), "weights_after": [round(v, 6) for v in ens.weights()]}
     print(json.dumps(res))
 
 
@@ -554,6 +570,8 @@ def main():
                                                             "with --mixed --mwer: a third step that trains on it")
     ap.add_argument("--ensemble-members", default=None, help="with --mixed --mwer --ensemble: the members, logit keys "
                                                              "separated by commas (default: all five)")
+    ap.add_argument("--learned", action="store_true", help="with --mixed --mwer --ensemble: a fourth step whose "
+                                                           "ensemble weights are learned (LearnedEnsemble)")
     ap.add_argument("--fusion", action="store_true", help="with --mixed --eval --rescore: a third pass whose list "
                                                           "comes from the fused search (Rescoring(fusion=True))")
     ap.add_argument("--rescore", default=None, help="with --mixed --eval: N[:score|mbr], the bucketed pass with and "
