@@ -60,6 +60,9 @@
  *                          ensemble a tensor the training losses can be taken on
  *   sca_ensemble_log_probs_dw, _dw_bwd  (no counterpart) the same pair with learned weights, the
  *                          softmax of scores on the device, and the gradient of those scores
+ *   sca_distill_heads_fwd/bwd  the SeqKD terms of model/__init__.py:203-214 for all students in one
+ *                          call, with (no counterpart) the ensemble of G heads as the teacher,
+ *                          formed on the fly
  *   sca_ctc_beam_decode*_nbest  (no counterpart; the interface of the decoder's top_paths) the N
  *   sca_nbest_rescore/mbr/gather  best labellings of the beam search, their rescoring with a
  *                          bigram gloss model, the posterior over the list and MBR selection
@@ -1067,6 +1070,56 @@ int sca_seqkd_valid_fwd(const float* student, const float* teacher, int R, int C
 int sca_seqkd_valid_bwd(const float* student, const float* teacher, int R, int C, int start, float temp,
                         const float* dloss, const float* ws, float* dstudent, float* dteacher, int T,
                         const int* valid_frames, int shift, void* stream);
+
+/* Ensemble distillation (no counterpart): SeqKD of S students, 1 <= S <=
+ * SCA_DISTILL_MAX_STUDENTS, against the ensemble of G members, 1 <= G <= SCA_EVAL_MAX_HEADS, in
+ * one call.  The teacher is formed on the fly and never stored.  By definition
+ *   losses[s] = sca_seqkd_fwd(students[s], e, R = B T, C, start, temp, weight[s], lo, hi)
+ *   e         = sca_ensemble_log_probs(members, G, W, mode)
+ * where per row only softmax(e[start:] / temp) matters: in mode 1 the outer normalisation of
+ * u = sum_g W_g lp_g is not computed, and with G = 1 the member's logits are read as the teacher's
+ * (its log-sum-exp cancels too) with the row arithmetic of sca_seqkd_*, so that the call is then
+ * BITWISE sca_seqkd_fwd / _bwd (with valid_frames: the _valid pair) once per student.
+ * Weights: exactly one of `weights` (host, normalised in double as sca_ensemble_log_probs does)
+ * and `weight_logits` ((G) fp32 on the device, W = softmax of it, read by every wave as
+ * sca_ensemble_log_probs_dw does, so a captured graph follows an update).  A student may be one
+ * of the members.  valid_frames: NULL, or the device scalar of the *_valid entries with `shift`:
+ * rows with t >= nv = clamp(*valid_frames >> shift, 1, T) contribute exact zeros, the divisor is
+ * B nv and the backward writes exact zeros into those rows.
+ * The teacher is detached: the backward writes, for every non-NULL dstudents->dlogits[s],
+ *   dstudent_s = dlosses[s] gate_s weight[s] temp / rows (softmax(s / temp) - q)  in columns >=
+ * start and zeros below, gate_s being the clamp gate the forward left in ws; a NULL entry is
+ * skipped (nothing of it is computed or written) and with every entry NULL nothing is launched.
+ * Neither the members nor weight_logits take a gradient.
+ * One wave64 per (row, student); 16-byte loads where every row involved starts on a 16-byte
+ * boundary and C % 4 == 0 (G >= 2), scalar loads otherwise; no atomics, every sum in a fixed
+ * order, a row's result depends on the row alone; nothing allocates, copies or synchronises, so
+ * the calls are capturable and a replay is bitwise the eager call.  fwd: two launches (the rows,
+ * then one finalize for all S); bwd: one.  ws: sca_distill_heads_workspace_floats(S, G, B, T)
+ * floats (0 for arguments out of range), written by fwd and read by bwd: per student the row
+ * losses, the row statistics and the gate, and for G >= 2 the members' row statistics.
+ * SCA_ERR_ARG before any GPU call: the ensemble entries' checks on members, G, the weights and
+ * mode; S out of range; a NULL student, losses, dlosses, dstudents or ws; temp <= 0; start outside
+ * [0, C); with valid_frames, shift outside [0, 30]; both or neither weight source; losses, ws (fwd)
+ * or a non-NULL dstudent (bwd) that is a member, a student, weight_logits, valid_frames, dlosses,
+ * ws or another output.                                                                    */
+#define SCA_DISTILL_MAX_STUDENTS 8
+typedef struct {
+  const float* logits[SCA_DISTILL_MAX_STUDENTS]; /* entries [S, 8) are ignored */
+  float weight[SCA_DISTILL_MAX_STUDENTS];
+} sca_distill_students;
+typedef struct {
+  float* dlogits[SCA_DISTILL_MAX_STUDENTS]; /* entries [S, 8) are ignored; NULL: no gradient for this student */
+} sca_distill_grads;
+long sca_distill_heads_workspace_floats(int S, int G, int B, int T);
+int sca_distill_heads_fwd(const sca_decode_heads* members, int G, const sca_ensemble_weights* weights,
+                          const float* weight_logits, int mode, const sca_distill_students* students, int S, int B,
+                          int T, int C, int start, float temp, float lo, float hi, const int* valid_frames, int shift,
+                          float* losses, float* ws, void* stream);
+int sca_distill_heads_bwd(const sca_decode_heads* members, int G, const sca_ensemble_weights* weights,
+                          const float* weight_logits, int mode, const sca_distill_students* students, int S, int B,
+                          int T, int C, int start, float temp, const int* valid_frames, int shift,
+                          const float* dlosses, const float* ws, const sca_distill_grads* dstudents, void* stream);
 
 /* torch.clamp(x, lo, hi) over n elements (dy == NULL; a NaN stays a NaN), or its backward
  * dx = dy * [lo <= x <= hi] */

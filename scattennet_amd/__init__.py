@@ -25,6 +25,7 @@ from .train import read_report, train_step  # noqa: F401
 from .bucketed import BucketedStep, BucketedTrainStep, pad_batch  # noqa: F401
 from .ensemble import EnsembleLogProbsOp, EnsembleSpec, LearnedEnsemble, LearnedEnsembleLogProbsOp  # noqa: F401
 from .ensemble import ensemble_log_probs  # noqa: F401
+from .distill import Distill, EnsembleDistillOp, check_distill, ensemble_distillation_loss  # noqa: F401
 from .mwer import MWER, MWERLossOp, mwer_guard, mwer_loss  # noqa: F401
 from .nbest import (BigramLM, NBest, Rescoring, ctc_decode_fused_nbest, ctc_decode_fused_nbest_device,  # noqa: F401
                     ctc_decode_fused_nbest_heads_device, ctc_decode_nbest, ctc_decode_nbest_device,

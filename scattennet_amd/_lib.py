@@ -160,6 +160,17 @@ class EnsembleGrads(ctypes.Structure):
     _fields_ = [("dlogits", c_void_p * EVAL_MAX_HEADS)]
 
 
+DISTILL_MAX_STUDENTS = 8
+
+
+class DistillStudents(ctypes.Structure):
+    _fields_ = [("logits", c_void_p * DISTILL_MAX_STUDENTS), ("weight", c_float * DISTILL_MAX_STUDENTS)]
+
+
+class DistillGrads(ctypes.Structure):
+    _fields_ = [("dlogits", c_void_p * DISTILL_MAX_STUDENTS)]
+
+
 class EvalState(ctypes.Structure):
     _fields_ = [("cursor", c_int), ("steps", c_int), ("overflow", c_int), ("first_flagged", c_int),
                 ("totals", (c_int * 4) * EVAL_MAX_HEADS), ("flags", ctypes.c_uint * REPORT_MAX_FLAGS),
@@ -256,6 +267,11 @@ EXPORTS = {
     "sca_ensemble_log_probs_dw": ([c_void_p, c_int, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p], c_int),
     "sca_ensemble_log_probs_dw_workspace_bytes": ([c_int] * 3, c_long),
     "sca_ensemble_log_probs_dw_bwd": ([c_void_p, c_int, c_void_p] + [c_int] * 4 + [c_void_p] * 6, c_int),
+    "sca_distill_heads_workspace_floats": ([c_int] * 4, c_long),
+    "sca_distill_heads_fwd": ([c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p] + [c_int] * 5 + [c_float] * 3 +
+                              [c_void_p, c_int] + [c_void_p] * 3, c_int),
+    "sca_distill_heads_bwd": ([c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p] + [c_int] * 5 + [c_float] +
+                              [c_void_p, c_int] + [c_void_p] * 4, c_int),
     "sca_optim_blocks": ([c_int, c_int], c_int),
     "sca_optim_grad_sqnorm": ([c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
     "sca_optim_adam_step": ([c_void_p, c_void_p, c_int, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p],

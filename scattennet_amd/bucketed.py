@@ -19,6 +19,7 @@ import torch
 from . import heads
 from .encoder import n_pool_of
 from .model import _LOGITS
+from .distill import check_distill
 from .mwer import check_mwer
 from .train import step_parameters, train_step
 
@@ -250,16 +251,20 @@ class BucketedTrainStep(BucketedStep):
     handed to `train_step`; the added frames lie past `input_lengths`, so the MWER loss and its
     gradients are those of the unpadded batch; that holds for every form of the spec (several
     heads, the reference as an entry, the gloss model's prior, the fused search): the padded
-    labels lie past `gloss_lengths` as the frames lie past `input_lengths`.
+    labels lie past `gloss_lengths` as the frames lie past `input_lengths`.  `distill`: None or a
+    `Distill`, handed to `train_step`, which passes the bucket's `valid_frames` to the grouped
+    call: the added frames contribute exact zeros, so the term and its gradients are the
+    unpadded batch's.
 
     Memory: every bucket keeps its own graph memory pool — all activations, gradients and
     workspaces of one step at (batch_size, bucket) stay reserved for the graph's lifetime, so
     the cost is about the sum over buckets of an eager step's peak at that length (parameters
     and optimizer state are shared, not duplicated)."""
 
-    def __init__(self, model, optimizer, batch_size, frame_buckets, label_bucket, mwer=None):
+    def __init__(self, model, optimizer, batch_size, frame_buckets, label_bucket, mwer=None, distill=None):
         super().__init__(model, batch_size, frame_buckets, label_bucket)
         self.mwer = check_mwer(mwer, "BucketedTrainStep")
+        self.distill = check_distill(distill, "BucketedTrainStep")
         n, slots = len(self.frame_buckets), getattr(optimizer, "capture_slots", 0)
         if slots < n:
             raise ValueError(f"BucketedTrainStep: {n} buckets need an optimizer with capture_slots >= {n} (one "
@@ -270,9 +275,10 @@ class BucketedTrainStep(BucketedStep):
         return next(self.model.parameters()).device
 
     def _run(self, src):
+        kw = {} if self.distill is None else {"distill": self.distill}
         if self.mwer is None:
-            return train_step(self.model, self.optimizer, src)
-        return train_step(self.model, self.optimizer, src, mwer=self.mwer)
+            return train_step(self.model, self.optimizer, src, **kw)
+        return train_step(self.model, self.optimizer, src, mwer=self.mwer, **kw)
 
     def _keep(self, outputs):
         """Detached: the step's backward has run, and an autograd graph a caller keeps alive must

@@ -27,6 +27,7 @@ import math
 import torch
 
 from . import heads, ops
+from .distill import check_distill
 from .ensemble import learned_ensembles
 from .model import _students_of, deferred_check, first_error, flag_names, guard_of
 from .model import read_report as model_read_report
@@ -55,6 +56,23 @@ def _add_mwer(outputs, src_input, mwer):
     return outputs["total_loss"] + mwer.weight * loss
 
 
+def _add_distill(model, outputs, src_input, distill, loss):
+    """The ensemble-distillation term of a step: `outputs["ensemble_kd_losses"]` (S), one loss per
+    student of `distill` from one grouped call, `outputs["ensemble_kd_loss"]`, their sum, and
+    `outputs["ensemble_kd_report"]`, the sum as a (1,) device tensor for `read_report`'s one copy.
+    A batch padded to a length bucket (`valid_frames`) takes part with its valid frames only.
+    Returns `loss` plus the term.  (No key ends in `_distill_loss`: the report layout of the
+    model's own terms follows from that suffix.)"""
+    valid = None
+    if src_input.get("valid_frames") is not None:
+        valid = (src_input["valid_frames"].to(outputs[distill.students[0]].device), model.n_pool())
+    losses = distill.losses(outputs, valid=valid)
+    total = losses.sum()
+    outputs["ensemble_kd_losses"], outputs["ensemble_kd_loss"] = losses, total
+    outputs["ensemble_kd_report"] = total.detach().float().reshape(1)
+    return loss + total
+
+
 def step_parameters(model, mwer):
     """The parameters whose gradients a step clears: the model's and, with an `MWER` that has
     `LearnedEnsemble`s among its heads, theirs (modules outside the model), so that a weight
@@ -65,7 +83,7 @@ def step_parameters(model, mwer):
             yield from ens.parameters()
 
 
-def train_step(model, optimizer, src_input, mwer=None):
+def train_step(model, optimizer, src_input, mwer=None, distill=None):
     """One training step of MSCA_Net with FusedAdam, enqueued on the current stream without a
     host read.  Returns the forward's outputs (`finite_report` holds the losses and flags).
     `mwer`: None, or an `MWER`: the step decodes the chosen head's logits (or, for a tuple of heads,
@@ -74,8 +92,15 @@ def train_step(model, optimizer, src_input, mwer=None):
     (mwer_loss, mean risk) as one device tensor, which lets `read_report` keep to a single copy) and
     back-propagates `total_loss + weight * mwer_loss`; a non-finite `mwer_loss` skips the update on the device like a flagged tensor.
     A `LearnedEnsemble` among the heads has its `weight_logits.grad` cleared with the model's and
-    filled by the backward; the optimizer updates it when it was given the parameter."""
+    filled by the backward; the optimizer updates it when it was given the parameter.
+    `distill`: None, or a `Distill`: its students learn from its teacher (a head, or an ensemble of
+    this step's heads formed inside the kernels) in one grouped call; the step adds
+    `ensemble_kd_losses` (S), `ensemble_kd_loss` (their sum) and `ensemble_kd_report`, back-propagates
+    the sum with the rest, and skips the update on the device when it is not finite.  The teacher
+    is detached.  It comes on top of the model's own `*_distill_loss` terms; with
+    cfg["self_distillation"] = False it stands instead of them."""
     check_mwer(mwer, "train_step")
+    check_distill(distill, "train_step")
     for p in step_parameters(model, mwer):
         p.grad = None
     ops.advance_dropout()
@@ -85,6 +110,9 @@ def train_step(model, optimizer, src_input, mwer=None):
     if mwer is not None:
         loss = _add_mwer(outputs, src_input, mwer)
         guard = mwer_guard(guard_of(outputs), outputs["mwer_loss"])
+    if distill is not None:
+        loss = _add_distill(model, outputs, src_input, distill, loss)
+        guard = mwer_guard(guard_of(outputs) if guard is None else guard, outputs["ensemble_kd_loss"])
     ops.fork_ledger_begin()
     try:
         loss.backward()
@@ -109,17 +137,25 @@ def read_report(outputs):
     `skipped` (the update did not happen: `guard` was not finite, the test FusedAdam makes on
     the device).  Raises the reference's ValueError (model/__init__.py:130-235) when a checked
     tensor was not finite.  After a step with `mwer=`, also `mwer_loss` and `mwer_risk` (the mean
-    over the clips), from the same single copy; a non-finite `mwer_loss` counts as `skipped`."""
-    extra = outputs.get("mwer_report")
-    if extra is None:
+    over the clips), from the same single copy; a non-finite `mwer_loss` counts as `skipped`.
+    After a step with `distill=`, also `ensemble_kd_loss`, from that copy too and with the same rule."""
+    mwer, kd = outputs.get("mwer_report"), outputs.get("ensemble_kd_report")
+    if mwer is None and kd is None:
         rep = model_read_report(outputs)
         rep["skipped"] = not math.isfinite(rep["guard"])
     else:
         report = outputs["finite_report"]
-        words = torch.cat([report, extra.view(report.dtype)]).cpu()
+        words = torch.cat([report] + [x.view(report.dtype) for x in (mwer, kd) if x is not None]).cpu()
         rep = model_read_report({**outputs, "finite_report": words[:report.numel()]})
-        rep["mwer_loss"], rep["mwer_risk"] = (float(v) for v in words[report.numel():].view(torch.float32))
-        rep["skipped"] = not (math.isfinite(rep["guard"]) and math.isfinite(rep["mwer_loss"]))
+        extra = [float(v) for v in words[report.numel():].view(torch.float32)]
+        terms = []
+        if mwer is not None:
+            rep["mwer_loss"], rep["mwer_risk"] = extra[:2]
+            terms.append(rep["mwer_loss"])
+        if kd is not None:
+            rep["ensemble_kd_loss"] = extra[-1]
+            terms.append(extra[-1])
+        rep["skipped"] = not all(math.isfinite(v) for v in [rep["guard"]] + terms)
     msg = first_error(rep["flags"], flag_names(_students_of(outputs)))
     if msg is not None:
         raise ValueError(msg)

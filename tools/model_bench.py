@@ -61,6 +61,10 @@ first head: the figure to compare is the third step's minus the `mwer` step's, w
 --ensemble-members left,right,body names other members than all five.  --learned adds a fourth step
 with the same members in a LearnedEnsemble (weights on the device, d theta in the graph, the parameter in
 the optimizer), timed in the same alternated windows.
+
+--distill (with --mixed): BucketedTrainStep with and without distill=Distill(teacher, {left, right, body}):
+the fuse head as the teacher, with --ensemble also the five-member ensemble, with --learned also a
+LearnedEnsemble; ms per step, the difference to the plain step, the mean ensemble_kd_loss.
 """
 import argparse
 import json
@@ -370,6 +374,52 @@ def mixed_mwer(a, dev):
     print(json.dumps(res))
 
 
+def mixed_distill(a, dev):
+    """--mixed --distill: BucketedTrainStep over the same stream in alternated windows, plain and with
+    distill=Distill(teacher, {left, right, body}) on top of the model's own distillation terms: the
+    teacher is the fuse head (the grouped call at G = 1), with --ensemble the five-member ensemble
+    (--ensemble-members names others) formed inside the kernels, with --learned its weights from a
+    LearnedEnsemble's scores on the device.  ms per step, the per-window difference to the plain
+    step and the mean ensemble_kd_loss over the stream."""
+    import scattennet_amd as S
+    from scattennet_amd.model import _LOGITS
+    adam = dict(lr=1e-4, betas=(0.9, 0.998), weight_decay=1e-3, max_grad_norm=1.0)
+    buckets = tuple(int(b) for b in a.buckets.split(","))
+    students = {"left": 1.0, "right": 1.0, "body": 1.0}
+    variants = [("plain", None), ("distill_head", S.Distill("fuse_coord_gloss_logits", students))]
+    if a.ensemble:
+        members = tuple(a.ensemble_members.split(",")) if a.ensemble_members else _LOGITS
+        variants.append(("distill_ensemble", S.Distill(S.EnsembleSpec(members), students)))
+        if a.learned:
+            variants.append(("distill_learned", S.Distill(S.LearnedEnsemble(members).to(dev), students)))
+    steps = {}
+    for name, spec in variants:
+        model, _, w, _ = build(a, dev)
+        model.check = "defer"
+        opt = S.FusedAdam(list(model.parameters()), capture_slots=len(buckets), **adam)
+        steps[name] = S.BucketedTrainStep(model, opt, a.B, buckets, a.S, distill=spec)
+    n_pool = (len(w["residual_blocks"]) + 1) // 2
+    batches = mixed_batches(a, w, dev, n_pool)
+    g = torch.Generator().manual_seed(a.seed + 1)
+    for step in steps.values():
+        capture_all(step, batches, lambda f: _batch(a, w, dev, g, [f] * a.B, n_pool)[0])
+    ms = {k: [] for k in steps}
+    for _ in range(a.windows):  # alternated windows
+        for k, step in steps.items():
+            ms[k].append(_pass(step.step, batches))
+    res = {"workload": "MSCA_Net BucketedTrainStep over a mixed-length stream with and without the ensemble "
+                       "distillation term, eval mode, no report read in the timed passes",
+           "B": a.B, "max_len": a.T, "C": a.C, "S": a.S, "seed": a.seed, "buckets": list(buckets),
+           "batch_lengths": [T for _, T in batches], "plain_ms_per_step": _spread(ms["plain"])}
+    for name, spec in variants[1:]:
+        reps = [S.read_report(steps[name].step(src)) for src, _ in batches]
+        res[name] = {"spec": repr(spec), "ms_per_step": _spread(ms[name]),
+                     "minus_plain_ms_per_step": _spread([x - y for x, y in zip(ms[name], ms["plain"])]),
+                     "ensemble_kd_loss_mean": round(statistics.mean(r["ensemble_kd_loss"] for r in reps), 6),
+                     "skipped_steps": sum(r["skipped"] for r in reps)}
+    print(json.dumps(res))
+
+
 def eval_loop(S, model, beam):
     """One batch of the loop a user writes from the parts: returns what it read."""
     def step(src):
@@ -576,6 +626,9 @@ def main():
                                                           "comes from the fused search (Rescoring(fusion=True))")
     ap.add_argument("--rescore", default=None, help="with --mixed --eval: N[:score|mbr], the bucketed pass with and "
                                                     "without the rescored n-best decode")
+    ap.add_argument("--distill", action="store_true", help="with --mixed: BucketedTrainStep with and without the "
+                                                           "ensemble distillation term (--ensemble, --learned: the "
+                                                           "teacher), alternated windows")
     ap.add_argument("--mwer", action="store_true", help="with --mixed: BucketedTrainStep with and without the MWER "
                                                         "loss (beam --beam), alternated windows")
     ap.add_argument("--mwer-reference", action="store_true", help="with --mixed --mwer: a third step whose MWER "
@@ -603,6 +656,8 @@ def main():
             return eval_rescore(a, dev)
         if a.mwer and not a.eval:
             return mixed_mwer(a, dev)
+        if a.distill and not a.eval:
+            return mixed_distill(a, dev)
         return eval_mixed(a, dev) if a.eval else mixed(a, dev)
     model, src, w, t4 = build(a, dev)
     graphs = {k: capture(model, src, k, dev) for k in ("off", "defer")}
