@@ -899,6 +899,65 @@ int sca_mwer_heads_bwd(const sca_decode_heads* heads, int G, const int* in_len, 
                        int C, int H, int R, int with_ref, const float* dloss, const float* ws,
                        const sca_mwer_grads* dlogits, void* stream);
 
+/* ---- the backoff n-gram gloss model: a sparse trigram for the second pass and MWER -----------
+ * sca_ngram_lm: an ARPA-style backoff model of order 1 to 3 over the C classes, natural-log
+ * fp32 values, on the device as a sorted trie.  Class 0 is the sentence boundary on both sides:
+ * <s> as context, </s> as predicted word.  Passed by pointer; the entry points copy the struct
+ * by value into the kernel arguments, the arrays stay the caller's.
+ *   unigrams  uni_lp[C], uni_bo[C]
+ *   bigrams   bi_ptr[C + 1]: the CSR row pointer by context v; bi_tok[n_bi]: the successors w,
+ *             strictly ascending inside a row; bi_lp[n_bi], bi_bo[n_bi]
+ *   trigrams  tri_ptr[n_bi + 1]: the CSR row pointer over the bigram entry of (u, v);
+ *             tri_tok[n_tri]: the successors w, strictly ascending; tri_lp[n_tri]
+ * Arrays of orders above `order` may be NULL (and arrays of a count of 0).
+ *
+ * For a labelling h of len tokens, path = [0] + h + [0] and
+ *   lm(h) = sum_{k = 1 .. len + 1} p(path[k] | context),
+ * so lm(empty) = p2(0 | 0) (order 1: uni_lp[0]).  The term at k uses the two previous path
+ * elements with order = 3 and k >= 2, one at k = 1 and everywhere with order = 2, none with
+ * order = 1.  The backoff rule, in fp32 with the additions in exactly this order:
+ *   p3(w | u, v) = tri_lp[u, v, w] if stored; else bi_bo[u, v] + p2(w | v) if the bigram (u, v)
+ *                  is stored; else p2(w | v)
+ *   p2(w | v)    = bi_lp[v, w] if stored; else uni_bo[v] + uni_lp[w]
+ *   p1(w)        = uni_lp[w]
+ * A look-up is a binary search inside one row: a trigram term needs at most three, (u, v) in
+ * row u, w in that entry's trigram row, w in row v.  Tokens are clamped into [0, C) only to stay
+ * in bounds, and every row range is clamped into [0, n_bi] or [0, n_tri] before the search: a
+ * corrupt table can neither read out of bounds nor loop.  The terms of one labelling are summed
+ * by the lane stride and the butterfly of the dense table's sum, so an order-2 model whose dense
+ * form holds fp32(uni_bo[v] + uni_lp[w]) in the backed-off cells gives bitwise the dense result.
+ *
+ * sca_nbest_rescore_ngram is sca_nbest_rescore, and sca_mwer_heads_fwd_ngram is
+ * sca_mwer_heads_fwd, with `const sca_ngram_lm* lm` (NULL: lm(h) = 0) in place of the dense
+ * table (and its C): lm(h) enters total and lmterm as lm_weight * lm(h) + length_bonus * len.
+ * sca_mwer_heads_bwd serves both forwards (the prior does not reach the gradient) and the
+ * workspace size is unchanged.  Validated before any GPU call: order in 1..3, 1 <= C <=
+ * SCA_CTC_MAX_C (for MWER: C equal to the logits'), n_bi, n_tri >= 0, non-NULL arrays for the
+ * orders in use, finite lm_weight and length_bonus, and the limits of the dense entry point.
+ * Neither allocates, copies or synchronises (capturable).  With lm_weight = 0, length_bonus = 0
+ * and finite stored values every output is bitwise the lm = NULL call's.  The fused beam search
+ * takes the dense table only: its frame scans a dense row per beam.                          */
+typedef struct {
+  int order, C, n_bi, n_tri;
+  const float* uni_lp;
+  const float* uni_bo;
+  const int* bi_ptr;
+  const int* bi_tok;
+  const float* bi_lp;
+  const float* bi_bo;
+  const int* tri_ptr;
+  const int* tri_tok;
+  const float* tri_lp;
+} sca_ngram_lm;
+int sca_nbest_rescore_ngram(const int* tokens, const int* out_len, const float* score, const int* count, int G,
+                            int B, int N, int T, const sca_ngram_lm* lm, float lm_weight, float length_bonus,
+                            float posterior_scale, float* total, float* posterior, int* order, void* stream);
+int sca_mwer_heads_fwd_ngram(const sca_decode_heads* heads, int G, const int* in_len, const int* tokens,
+                             const int* out_len, const int* count, const int* ref, const int* ref_len, int B, int N,
+                             int T, int C, int H, int R, int with_ref, const sca_ngram_lm* lm, float lm_weight,
+                             float length_bonus, float posterior_scale, float* loglik, float* posterior, int* errors,
+                             int* ref_valid, float* risk, float* loss, float* ws, void* stream);
+
 /* ---- evaluation: CTC forced alignment (gloss spans and confidences) -----------------------
  * The best single path of G heads' logits through given label sequences: for every (head g,
  * clip b) the frames at which each label is emitted.  Logits as for the decoders (fp32

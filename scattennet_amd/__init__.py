@@ -31,6 +31,7 @@ from .nbest import (BigramLM, NBest, Rescoring, ctc_decode_fused_nbest, ctc_deco
                     ctc_decode_fused_nbest_heads_device, ctc_decode_nbest, ctc_decode_nbest_device,
                     ctc_decode_nbest_heads_device, mbr_select_device, rescore_nbest_device, rescored_decode,
                     select_device)
+from .ngram import NGramLM  # noqa: F401
 from .evaluate import BucketedEvalStep, EvalState, ctc_decode_heads_device, eval_step  # noqa: F401
 from .recognize import BucketedRecognizer, Recognition, recognize_step  # noqa: F401
 from . import library  # noqa: F401  (torch.ops.scatten.*)

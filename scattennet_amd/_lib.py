@@ -152,6 +152,12 @@ class MwerGrads(ctypes.Structure):
     _fields_ = [("dlogits", c_void_p * EVAL_MAX_HEADS)]
 
 
+class NgramLm(ctypes.Structure):  # sca_ngram_lm
+    _fields_ = [("order", c_int), ("C", c_int), ("n_bi", c_int), ("n_tri", c_int), ("uni_lp", c_void_p),
+                ("uni_bo", c_void_p), ("bi_ptr", c_void_p), ("bi_tok", c_void_p), ("bi_lp", c_void_p),
+                ("bi_bo", c_void_p), ("tri_ptr", c_void_p), ("tri_tok", c_void_p), ("tri_lp", c_void_p)]
+
+
 class EnsembleWeights(ctypes.Structure):
     _fields_ = [("w", c_float * EVAL_MAX_HEADS)]
 
@@ -248,6 +254,7 @@ EXPORTS = {
     "sca_ctc_beam_decode_heads_fused_nbest": ([c_void_p, c_int, c_void_p] + [c_int] * 6 +
                                               [c_void_p, c_float, c_float] + [c_void_p] * 6, c_int),
     "sca_nbest_rescore": ([c_void_p] * 4 + [c_int] * 4 + [c_void_p, c_int] + [c_float] * 3 + [c_void_p] * 4, c_int),
+    "sca_nbest_rescore_ngram": ([c_void_p] * 4 + [c_int] * 4 + [c_void_p] + [c_float] * 3 + [c_void_p] * 4, c_int),
     "sca_nbest_mbr": ([c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 4, c_int),
     "sca_nbest_gather": ([c_void_p] * 4 + [c_int] * 5 + [c_void_p] * 4, c_int),
     "sca_mwer_workspace_floats": ([c_int] * 4, c_long),
@@ -256,6 +263,8 @@ EXPORTS = {
     "sca_mwer_heads_workspace_floats": ([c_int] * 7, c_long),
     "sca_mwer_heads_fwd": ([c_void_p, c_int] + [c_void_p] * 6 + [c_int] * 7 + [c_void_p] + [c_float] * 3 +
                            [c_void_p] * 8, c_int),
+    "sca_mwer_heads_fwd_ngram": ([c_void_p, c_int] + [c_void_p] * 6 + [c_int] * 7 + [c_void_p] + [c_float] * 3 +
+                                 [c_void_p] * 8, c_int),
     "sca_mwer_heads_bwd": ([c_void_p, c_int] + [c_void_p] * 6 + [c_int] * 7 + [c_void_p] * 4, c_int),
     "sca_eval_accumulate": ([c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
                              c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p], c_int),

@@ -65,6 +65,104 @@ __device__ __forceinline__ float ctc_bigram_prior(const float* __restrict__ lm, 
   return lm_weight * acc + length_bonus * (float)len;
 }
 
+// The backoff n-gram gloss model (include/scatten.h, sca_ngram_lm) by value in the kernel
+// arguments: a sorted trie, bigram rows by context in CSR form, trigram rows by bigram entry.
+// order = 0 stands for "no model" (the entry points' lm = NULL).
+using NgramLm = sca_ngram_lm;
+
+// The entry of tok in the ascending row [lo, hi) of toks (n entries in all), or -1.  The range is
+// clamped into [0, n] first and shrinks in every step: a corrupt row pointer can neither read
+// out of bounds nor loop.
+__device__ __forceinline__ int ngram_find(const int* __restrict__ toks, int lo, int hi, int n, int tok) {
+  int a = clampi(lo, 0, n), b = clampi(hi, a, n);
+  const int end = b;
+  while (a < b) {
+    const int mid = a + ((b - a) >> 1);
+    if (toks[mid] < tok) {
+      a = mid + 1;
+    } else {
+      b = mid;
+    }
+  }
+  return a < end && toks[a] == tok ? a : -1;
+}
+
+// p2(w | v): the stored bigram, or uni_bo[v] + uni_lp[w]
+__device__ __forceinline__ float ngram_p2(const NgramLm& m, int v, int w) {
+  const int j = ngram_find(m.bi_tok, m.bi_ptr[v], m.bi_ptr[v + 1], m.n_bi, w);
+  return j >= 0 ? m.bi_lp[j] : m.uni_bo[v] + m.uni_lp[w];
+}
+
+// p3(w | u, v): the stored trigram; else bi_bo[u, v] + p2(w | v) with (u, v) stored; else p2(w | v)
+__device__ __forceinline__ float ngram_p3(const NgramLm& m, int u, int v, int w) {
+  const int c = ngram_find(m.bi_tok, m.bi_ptr[u], m.bi_ptr[u + 1], m.n_bi, v);
+  if (c < 0) return ngram_p2(m, v, w);
+  const int t = ngram_find(m.tri_tok, m.tri_ptr[c], m.tri_ptr[c + 1], m.n_tri, w);
+  return t >= 0 ? m.tri_lp[t] : m.bi_bo[c] + ngram_p2(m, v, w);
+}
+
+// ctc_bigram_prior's contract for the backoff n-gram model of order 1 to 3: path = [0] + h + [0],
+// lm(h) = sum_{k = 1 .. len + 1} p(path[k] | the order - 1 elements before it), the term at k = 1
+// with one element of context at most.  The lanes stride over the len + 1 independent look-ups
+// (up to three binary searches each, plain loads), the same butterfly sums them; every lane
+// returns lm_weight * lm(h) + length_bonus * len.  Tokens are clamped into [0, C) only to stay in
+// bounds.
+__device__ __forceinline__ float ctc_ngram_prior(const NgramLm& m, const int* __restrict__ h, int len, int lane,
+                                                 float lm_weight, float length_bonus) {
+  float acc = 0.0f;
+  if (m.order >= 1) {
+    for (int i = lane; i <= len; i += 64) {
+      const int w = i == len ? 0 : clampi(h[i], 0, m.C - 1);
+      float term;
+      if (m.order == 1) {
+        term = m.uni_lp[w];
+      } else {
+        const int v = i == 0 ? 0 : clampi(h[i - 1], 0, m.C - 1);
+        if (m.order == 2 || i == 0) {
+          term = ngram_p2(m, v, w);
+        } else {
+          term = ngram_p3(m, i == 1 ? 0 : clampi(h[i - 2], 0, m.C - 1), v, w);
+        }
+      }
+      acc += term;
+    }
+    acc = wave_sum(acc);
+  }
+  return lm_weight * acc + length_bonus * (float)len;
+}
+
+// The prior of a kernel as a functor: the dense table (lm = NULL: lm(h) = 0) or the trie
+struct CtcBigramPrior {
+  const float* lm;
+  int C;
+  __device__ __forceinline__ float operator()(const int* __restrict__ h, int len, int lane, float lm_weight,
+                                              float length_bonus) const {
+    return ctc_bigram_prior(lm, C, h, len, lane, lm_weight, length_bonus);
+  }
+};
+
+struct CtcNgramPrior {
+  NgramLm m;
+  __device__ __forceinline__ float operator()(const int* __restrict__ h, int len, int lane, float lm_weight,
+                                              float length_bonus) const {
+    return ctc_ngram_prior(m, h, len, lane, lm_weight, length_bonus);
+  }
+};
+
+// The validation of an entry point's `lm` (NULL allowed): order in 1..3, 1 <= C <= SCA_CTC_MAX_C,
+// counts >= 0 and the arrays of the orders in use; the by-value copy, order 0 for NULL.
+inline bool ctc_ngram_ok(const sca_ngram_lm* lm) {
+  if (!lm) return true;
+  bool ok = lm->order >= 1 && lm->order <= 3 && lm->C >= 1 && lm->C <= SCA_CTC_MAX_C && lm->n_bi >= 0 &&
+            lm->n_tri >= 0 && lm->uni_lp;
+  if (ok && lm->order >= 2) ok = lm->uni_bo && lm->bi_ptr && (lm->n_bi == 0 || (lm->bi_tok && lm->bi_lp));
+  if (ok && lm->order >= 3)
+    ok = lm->tri_ptr && (lm->n_bi == 0 || lm->bi_bo) && (lm->n_tri == 0 || (lm->tri_tok && lm->tri_lp));
+  return ok;
+}
+
+inline NgramLm ctc_ngram_of(const sca_ngram_lm* lm) { return lm ? *lm : NgramLm{}; }
+
 // heads.hip: ctc_row_stat over the rows of one tensor, rowstat (rows, 2); the CTC loss, the MWER
 // loss and a decoder call over one tensor use it
 __attribute__((visibility("hidden"))) void sca_ctc_rowstat_launch(const float* x, float* rowstat, long rows, int C,

@@ -769,12 +769,13 @@ __global__ __launch_bounds__(64) void eval_advance_kernel(const unsigned* __rest
 // One wave per (head, clip).  The lanes stride over the len + 1 bigram terms of one entry at a
 // time (independent gathers), a butterfly sums them; lane n then holds entry n's total for the
 // softmax over the valid entries and the rank count that gives `order`.
+// Prior: the gloss model as a functor of ctc.h, the dense table or the backoff trie.
+template <class Prior>
 __global__ __launch_bounds__(64) void nbest_rescore_kernel(const int* __restrict__ tokens,
                                                            const int* __restrict__ out_len,
                                                            const float* __restrict__ score,
-                                                           const int* __restrict__ count, int N, int T,
-                                                           const float* __restrict__ lm, int C, float lm_weight,
-                                                           float length_bonus, float posterior_scale,
+                                                           const int* __restrict__ count, int N, int T, Prior prior,
+                                                           float lm_weight, float length_bonus, float posterior_scale,
                                                            float* __restrict__ total, float* __restrict__ posterior,
                                                            int* __restrict__ order) {
   __shared__ unsigned long long key[DEC_MAX_W];
@@ -785,7 +786,7 @@ __global__ __launch_bounds__(64) void nbest_rescore_kernel(const int* __restrict
   for (int n = 0; n < cnt; ++n) {
     const int len = clampi(out_len[s * N + n], 0, T);
     const int* h = tokens + (s * N + n) * T;
-    const float t = score[s * N + n] + ctc_bigram_prior(lm, C, h, len, lane, lm_weight, length_bonus);
+    const float t = score[s * N + n] + prior(h, len, lane, lm_weight, length_bonus);
     mine = lane == n ? t : mine;
   }
   const bool valid = lane < cnt;
@@ -1103,10 +1104,28 @@ extern "C" int sca_nbest_rescore(const int* tokens, const int* out_len, const fl
                   "table, finite weights)");
     return SCA_ERR_ARG;
   }
-  hipLaunchKernelGGL(nbest_rescore_kernel, dim3((unsigned)(G * B)), dim3(64), 0, reinterpret_cast<hipStream_t>(stream),
-                     tokens, out_len, score, count, N, T, lm, C, lm_weight, length_bonus, posterior_scale, total,
-                     posterior, order);
+  hipLaunchKernelGGL(nbest_rescore_kernel<CtcBigramPrior>, dim3((unsigned)(G * B)), dim3(64), 0,
+                     reinterpret_cast<hipStream_t>(stream), tokens, out_len, score, count, N, T, CtcBigramPrior{lm, C},
+                     lm_weight, length_bonus, posterior_scale, total, posterior, order);
   return sca_launch_status("sca_nbest_rescore");
+}
+
+extern "C" int sca_nbest_rescore_ngram(const int* tokens, const int* out_len, const float* score, const int* count,
+                                       int G, int B, int N, int T, const sca_ngram_lm* lm, float lm_weight,
+                                       float length_bonus, float posterior_scale, float* total, float* posterior,
+                                       int* order, void* stream) {
+  if (!nbest_dims_ok(G, B, N, T) || !tokens || !out_len || !score || !count || !total || !posterior || !order ||
+      !ctc_ngram_ok(lm) || !(lm_weight - lm_weight == 0.0f) || !(length_bonus - length_bonus == 0.0f) ||
+      !(posterior_scale - posterior_scale == 0.0f)) {
+    sca_set_error("sca_nbest_rescore_ngram: bad arguments (1 <= G <= 8, B, T >= 1, 1 <= N <= 32; with a model: order "
+                  "in 1..3, 1 <= C <= 8192, counts >= 0, the arrays of the orders in use; finite weights)");
+    return SCA_ERR_ARG;
+  }
+  hipLaunchKernelGGL(nbest_rescore_kernel<CtcNgramPrior>, dim3((unsigned)(G * B)), dim3(64), 0,
+                     reinterpret_cast<hipStream_t>(stream), tokens, out_len, score, count, N, T,
+                     CtcNgramPrior{ctc_ngram_of(lm)}, lm_weight, length_bonus, posterior_scale, total, posterior,
+                     order);
+  return sca_launch_status("sca_nbest_rescore_ngram");
 }
 
 extern "C" int sca_nbest_mbr(const int* tokens, const int* out_len, const int* count, const float* posterior, int G,

@@ -37,7 +37,13 @@ MwDims mw_dims(int G, int B, int N, int T, int C, int H, int R, int with_ref, in
   return MwDims{B, N, T, C, H, R, G * B, N + (with_ref ? 1 : 0), with_ref && R > H ? R : H, with_ref ? 1 : 0, prior};
 }
 
-// The gloss model of the prior (sca_nbest_rescore's arguments)
+// The gloss model of the prior (sca_nbest_rescore's arguments); Prior: the functor of ctc.h, the
+// dense table (MwPrior, what the call record holds) or the backoff trie
+template <class Prior>
+struct MwPriorOf {
+  Prior lm;
+  float weight, bonus;
+};
 struct MwPrior {
   const float* lm;
   float weight, bonus;
@@ -196,10 +202,11 @@ __device__ __forceinline__ void mwer_alpha_beta(const CtcHeads& heads, const int
 // num_sub of reference b against entry n; 0 for the entries past count and for the reference
 // slot, which needs no alignment.  With the prior, wave 1 computes the slot's lmterm once it has
 // left wer_pair's last barrier, beside thread 0's serial back-trace.
+template <class Prior>
 __device__ __forceinline__ void mwer_pair(const int* __restrict__ tokens, const int* __restrict__ out_len,
                                           const int* __restrict__ count, const int* __restrict__ ref,
-                                          const int* __restrict__ ref_len, MwDims d, MwPrior prior, float* ws,
-                                          int* __restrict__ errors) {
+                                          const int* __restrict__ ref_len, MwDims d, const MwPriorOf<Prior>& prior,
+                                          float* ws, int* __restrict__ errors) {
   __shared__ int c4[4];
   const int n = blockIdx.x, p = blockIdx.y;
   const int b = p % d.B;
@@ -218,7 +225,7 @@ __device__ __forceinline__ void mwer_pair(const int* __restrict__ tokens, const 
     float v = 0.0f;
     if (listed || n == d.N) {
       const MwSlot slot = mw_slot(tokens, out_len, ref, ref_len, d, p, b, n);
-      v = ctc_bigram_prior(prior.lm, d.C, slot.tok, slot.len, lane, prior.weight, prior.bonus);
+      v = prior.lm(slot.tok, slot.len, lane, prior.weight, prior.bonus);
     }
     if (lane == 0) MwWs(ws, d).lmterm[e] = v;
   }
@@ -228,12 +235,14 @@ __device__ __forceinline__ void mwer_pair(const int* __restrict__ tokens, const 
 // that the alignment (an anti-diagonal sweep and a serial back-trace) and the prior run beside
 // the two recursions instead of after them.  z = 0, 1: wave 0 runs the recursion, wave 1 leaves
 // at once (the recursion uses no workgroup barrier); z = 2: both waves run wer_pair.
+template <class Prior>
 __global__ __launch_bounds__(128) void mwer_entry_kernel(CtcHeads heads, const int* __restrict__ in_len,
                                                          const int* __restrict__ tokens,
                                                          const int* __restrict__ out_len,
                                                          const int* __restrict__ count, const int* __restrict__ ref,
-                                                         const int* __restrict__ ref_len, MwDims d, MwPrior prior,
-                                                         float* ws, int* __restrict__ errors) {
+                                                         const int* __restrict__ ref_len, MwDims d,
+                                                         MwPriorOf<Prior> prior, float* ws,
+                                                         int* __restrict__ errors) {
   if (blockIdx.z == 2) {
     mwer_pair(tokens, out_len, count, ref, ref_len, d, prior, ws, errors);
   } else if (threadIdx.x < 64) {
@@ -393,6 +402,8 @@ bool mwer_dims_ok(int G, int B, int N, int T, int C, int H, int R) {
 }
 
 #define MWER_LIMITS "bad arguments (1 <= B <= 65535, T >= 1, C <= 8192, 1 <= N <= 32, 1 <= H, R <= 128)"
+#define MWER_NGRAM_LIMITS \
+  "; with a model: order in 1..3, C the logits', counts >= 0, the arrays of the orders in use"
 #define MWER_HEADS_LIMITS \
   "bad arguments (1 <= G <= 8, B >= 1, G B <= 65535, T >= 1, C <= 8192, 1 <= N <= 32, 1 <= H, R <= 128, finite weights)"
 
@@ -411,6 +422,8 @@ struct MwCall {
   const float* dloss;  // backward
   const sca_mwer_grads* dlogits;
   MwPrior prior;  // forward
+  const sca_ngram_lm* ngram;  // forward, the _ngram entry point: the trie in place of prior.lm (NULL: none)
+  bool sparse;                // the _ngram entry point
   float posterior_scale;
   float *loglik, *posterior;
   int *errors, *ref_valid;
@@ -428,9 +441,11 @@ bool mw_call_ok(const MwCall& c, bool bwd) {
          (c.ref_valid || !c.grouped) && c.risk && c.loss;
   }
   for (int g = 0; ok && g < c.G; ++g) ok = c.heads->logits[g] && (!bwd || c.dlogits->dlogits[g]);
+  if (ok && !bwd && c.sparse) ok = ctc_ngram_ok(c.ngram) && (!c.ngram || c.ngram->C == c.C);
   if (!ok) {
-    char msg[256];
-    snprintf(msg, sizeof(msg), "%s: %s", c.name, c.grouped ? MWER_HEADS_LIMITS : MWER_LIMITS);
+    char msg[384];
+    snprintf(msg, sizeof(msg), "%s: %s%s", c.name, c.grouped ? MWER_HEADS_LIMITS : MWER_LIMITS,
+             c.sparse ? MWER_NGRAM_LIMITS : "");
     sca_set_error(msg);
   }
   return ok;
@@ -441,15 +456,23 @@ bool mw_call_ok(const MwCall& c, bool bwd) {
 int mwer_fwd(const MwCall& c, void* stream) {
   if (!mw_call_ok(c, false)) return SCA_ERR_ARG;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const MwDims d = mw_dims(c.G, c.B, c.N, c.T, c.C, c.H, c.R, c.with_ref, c.prior.lm || c.prior.bonus != 0.0f);
+  const MwDims d = mw_dims(c.G, c.B, c.N, c.T, c.C, c.H, c.R, c.with_ref,
+                           c.prior.lm || c.ngram || c.prior.bonus != 0.0f);
   float* ws = const_cast<float*>(c.ws);
   if (c.G == 1) {
     sca_ctc_rowstat_launch(c.heads->logits[0], ws, (long)d.B * d.T, d.C, st);
   } else {
     sca_ctc_rowstat_heads_launch(c.heads, c.G, ws, (long)d.B * d.T, d.C, st);
   }
-  hipLaunchKernelGGL(mwer_entry_kernel, dim3(d.M, d.P, 3), dim3(128), 0, st, ctc_heads_of(c.heads, c.G), c.in_len,
-                     c.tokens, c.out_len, c.count, c.ref, c.ref_len, d, c.prior, ws, c.errors);
+  if (c.sparse) {
+    hipLaunchKernelGGL(mwer_entry_kernel<CtcNgramPrior>, dim3(d.M, d.P, 3), dim3(128), 0, st,
+                       ctc_heads_of(c.heads, c.G), c.in_len, c.tokens, c.out_len, c.count, c.ref, c.ref_len, d,
+                       MwPriorOf<CtcNgramPrior>{{ctc_ngram_of(c.ngram)}, c.prior.weight, c.prior.bonus}, ws, c.errors);
+  } else {
+    hipLaunchKernelGGL(mwer_entry_kernel<CtcBigramPrior>, dim3(d.M, d.P, 3), dim3(128), 0, st,
+                       ctc_heads_of(c.heads, c.G), c.in_len, c.tokens, c.out_len, c.count, c.ref, c.ref_len, d,
+                       MwPriorOf<CtcBigramPrior>{{c.prior.lm, d.C}, c.prior.weight, c.prior.bonus}, ws, c.errors);
+  }
   const int groups = d.P <= MW_CLIPS_ONE_GROUP ? 1 : (d.P + 3) / 4;
   hipLaunchKernelGGL(mwer_clip_kernel, dim3(groups), dim3(256), 0, st, c.count, c.errors, d, c.posterior_scale, ws,
                      c.loglik, c.posterior, c.ref_valid, c.risk, c.loss);
@@ -487,7 +510,8 @@ extern "C" int sca_mwer_fwd(const float* logits, const int* in_len, const int* t
                             float* loss, float* ws, void* stream) {
   const sca_decode_heads one = {{logits}};
   return mwer_fwd({"sca_mwer_fwd", false, &one, 1, in_len, tokens, out_len, count, ref, ref_len, B, N, T, C, H, R, 0,
-                   ws, nullptr, nullptr, {}, posterior_scale, loglik, posterior, errors, nullptr, risk, loss},
+                   ws, nullptr, nullptr, {}, nullptr, false, posterior_scale, loglik, posterior, errors, nullptr, risk,
+                   loss},
                   stream);
 }
 
@@ -507,8 +531,20 @@ extern "C" int sca_mwer_heads_fwd(const sca_decode_heads* heads, int G, const in
                                   float length_bonus, float posterior_scale, float* loglik, float* posterior,
                                   int* errors, int* ref_valid, float* risk, float* loss, float* ws, void* stream) {
   return mwer_fwd({"sca_mwer_heads_fwd", true, heads, G, in_len, tokens, out_len, count, ref, ref_len, B, N, T, C, H, R,
-                   with_ref, ws, nullptr, nullptr, {lm, lm_weight, length_bonus}, posterior_scale, loglik, posterior,
-                   errors, ref_valid, risk, loss},
+                   with_ref, ws, nullptr, nullptr, {lm, lm_weight, length_bonus}, nullptr, false, posterior_scale,
+                   loglik, posterior, errors, ref_valid, risk, loss},
+                  stream);
+}
+
+extern "C" int sca_mwer_heads_fwd_ngram(const sca_decode_heads* heads, int G, const int* in_len, const int* tokens,
+                                        const int* out_len, const int* count, const int* ref, const int* ref_len,
+                                        int B, int N, int T, int C, int H, int R, int with_ref,
+                                        const sca_ngram_lm* lm, float lm_weight, float length_bonus,
+                                        float posterior_scale, float* loglik, float* posterior, int* errors,
+                                        int* ref_valid, float* risk, float* loss, float* ws, void* stream) {
+  return mwer_fwd({"sca_mwer_heads_fwd_ngram", true, heads, G, in_len, tokens, out_len, count, ref, ref_len, B, N, T,
+                   C, H, R, with_ref, ws, nullptr, nullptr, {nullptr, lm_weight, length_bonus}, lm, true,
+                   posterior_scale, loglik, posterior, errors, ref_valid, risk, loss},
                   stream);
 }
 

@@ -26,8 +26,9 @@ from .ensemble import EnsembleSpec, LearnedEnsemble
 from .decode import MAX_BEAM, WER_MAX_LEN, _check_lengths, _check_logits, check_heads, check_on_device
 from .heads import _dev_i32
 from .model import _LOGITS
-from .nbest import (MAX_CLASSES, MAX_HEADS, BigramLM, _check_beam, _check_fusion, _check_nbest, _finite,
-                    _fusion_table, _nbest_decode)
+from .nbest import (MAX_CLASSES, MAX_HEADS, BigramLM, _check_beam, _check_fusion, _check_nbest, _dense_only,
+                    _finite, _fusion_table, _nbest_decode)
+from .ngram import NGramLM
 
 
 class MWERLossOp(Function):
@@ -37,7 +38,8 @@ class MWERLossOp(Function):
     caller's backward needs no indexing kernels; in_len (B),
     tokens (G, B, N, H), out_len (G, B, N), count (G, B), ref (B, R), ref_len (B) int32 device
     tensors; `with_ref`: the reference is slot N of every list (M = N + 1, else M = N); `table`:
-    the (C, C) fp32 device table of the prior or None, with `lm_weight` and `length_bonus`.
+    the (C, C) fp32 device table of the prior, an `NGramLM` on the device (`sca_mwer_heads_fwd_ngram`;
+    the backward is the same) or None, with `lm_weight` and `length_bonus`.
     Only `loss` is differentiable, with respect to every head's logits; the workspace is kept for
     the backward."""
 
@@ -45,7 +47,8 @@ class MWERLossOp(Function):
     def forward(ctx, in_len, tokens, out_len, count, ref, ref_len, posterior_scale, with_ref, table, lm_weight,
                 length_bonus, grouped, *logits):
         xs = [x.contiguous() for x in logits]
-        L.require_device(*xs, table)
+        sparse = isinstance(table, NGramLM)
+        L.require_device(*xs, table.uni_lp if sparse else table)
         G = len(xs)
         B, T, C = xs[0].shape
         N, H = tokens.shape[-2], tokens.shape[-1]
@@ -61,11 +64,13 @@ class MWERLossOp(Function):
         ref_valid = torch.empty(lead, dtype=torch.int32, device=x.device)
         risk = x.new_empty(lead)
         hx = L.decode_heads(xs)
-        L.check(lib.sca_mwer_heads_fwd(ctypes.byref(hx), G, L.ptr(in_len), L.ptr(tokens), L.ptr(out_len), L.ptr(count),
-                                       L.ptr(ref), L.ptr(ref_len), B, N, T, C, H, R, int(with_ref), L.ptr(table),
-                                       lm_weight, length_bonus, posterior_scale, L.ptr(loglik), L.ptr(posterior),
-                                       L.ptr(errors), L.ptr(ref_valid), L.ptr(risk), L.ptr(loss), L.ptr(ws),
-                                       L.stream_handle()), "sca_mwer_heads_fwd")
+        fwd, name = (lib.sca_mwer_heads_fwd_ngram, "sca_mwer_heads_fwd_ngram") if sparse else \
+            (lib.sca_mwer_heads_fwd, "sca_mwer_heads_fwd")
+        L.check(fwd(ctypes.byref(hx), G, L.ptr(in_len), L.ptr(tokens), L.ptr(out_len), L.ptr(count), L.ptr(ref),
+                    L.ptr(ref_len), B, N, T, C, H, R, int(with_ref),
+                    ctypes.byref(table.struct) if sparse else L.ptr(table), lm_weight, length_bonus, posterior_scale, L.ptr(loglik), L.ptr(posterior), L.ptr(errors),
+                    L.ptr(ref_valid), L.ptr(risk), L.ptr(loss), L.ptr(ws), L.stream_handle()), name)
+        ctx.lm = table if sparse else None  # the trie's tensors stay alive with the graph of this call
         ctx.save_for_backward(in_len, tokens, out_len, count, ref, ref_len, ws, *xs)
         ctx.with_ref = int(with_ref)
         ctx.mark_non_differentiable(loglik, posterior, errors, ref_valid, risk)
@@ -114,12 +119,15 @@ def _check_refs(labels, lengths, B, C, what):
 
 
 def _check_prior(lm, lm_weight, length_bonus, fusion, num_classes, what):
-    """The prior's arguments, validated on the host: (lm as a BigramLM or None, lm_weight,
-    length_bonus).  `lm` may also be a (C, C) table of finite log-probabilities (a device table
-    is then read once: hand over a `BigramLM` under capture)."""
-    if lm is not None and not isinstance(lm, BigramLM):
+    """The prior's arguments, validated on the host: (lm as a BigramLM, an NGramLM or None,
+    lm_weight, length_bonus).  `lm` may also be a (C, C) table of finite log-probabilities (a
+    device table is then read once: hand over a `BigramLM` under capture)."""
+    if fusion is True:
+        _dense_only(lm, what)
+    if lm is not None and not isinstance(lm, (BigramLM, NGramLM)):
         if not (torch.is_tensor(lm) or hasattr(lm, "__array__")):
-            raise ValueError(f"{what}: lm must be a BigramLM, a (C, C) table or None, got {type(lm).__name__}")
+            raise ValueError(f"{what}: lm must be a BigramLM, an NGramLM, a (C, C) table or None, got "
+                             f"{type(lm).__name__}")
         lm = BigramLM(lm)
     try:
         if num_classes is None and lm is not None:
@@ -155,7 +163,7 @@ def mwer_loss(gloss_logits, input_lengths, gloss_labels, gloss_lengths, nbest=No
     `ref_valid` (B) int32 in the details says where it counts, and `loglik[:, N]` is the
     reference's likelihood wherever it fits.  A list whose hypotheses are all equally wrong then
     has a gradient, towards the transcript.
-    `lm` (a `BigramLM` on the logits' device, or a (C, C) table), `lm_weight`, `length_bonus`: the
+    `lm` (a `BigramLM` or an `NGramLM` on the logits' device, or a (C, C) table), `lm_weight`, `length_bonus`: the
     posterior is the softmax of posterior_scale * (ll + lm_weight * lm(h) + length_bonus * len(h)),
     the total `rescore_nbest_device` ranks by, for the reference slot too.
     `fusion=True` (with `nbest=None`) takes the list from `ctc_decode_fused_nbest_device(...,
@@ -232,7 +240,7 @@ class MWER:
     like on any head, so the gradient reaches every member; a `LearnedEnsemble` stands where an
     `EnsembleSpec` does, and its `weight_logits` takes a gradient too (the steps clear it with the
     model's).  `reference`, `lm`
-    (a `BigramLM` on the model's device, or a (C, C) table), `lm_weight`, `length_bonus` and
+    (a `BigramLM` or an `NGramLM` on the model's device, or a (C, C) table), `lm_weight`, `length_bonus` and
     `fusion` are `mwer_loss`'s: the reference as one more entry of every list, the gloss model's
     prior inside the posterior, the list from the fused search.  ValueError for anything else."""
 

@@ -14,6 +14,9 @@ of this.
   length_bonus * len; scores stay acoustic.  `Rescoring(..., fusion=True)` selects it in the steps.
 * `BigramLM` — a dense (C, C) table of log-probabilities; class 0, the blank, is the sentence
   boundary.  `BigramLM.from_sequences` estimates one with add-k smoothing on the host.
+* `NGramLM` (ngram.py) — a backoff n-gram model of order 1 to 3 as a sorted trie on the device,
+  taken wherever a `BigramLM` is, except by the fused search (`NGramLM.to_bigram()` gives its
+  dense form).
 * `rescore_nbest_device` — (total, posterior, order); `mbr_select_device` — (best, risk, loss);
   `select_device` — one entry per list as a 1-best (tokens, lengths, values) triple.
 * `Rescoring` — the validated spec that `decode_and_align`, `eval_step`, `BucketedEvalStep`,
@@ -25,6 +28,7 @@ No call reads the device or allocates outside the caching allocator: everything 
 entries are merged and the list re-sorted, so entry 0 may differ from `ctc_decode_device`'s result.
 """
 import collections
+import ctypes
 import math
 
 import numpy as np
@@ -33,6 +37,7 @@ import torch
 from . import _lib as L
 from .decode import MAX_BEAM, WER_MAX_LEN, _check_lengths, _check_logits, _decoder, check_heads, check_on_device
 from .heads import _dev_i32
+from .ngram import NGramLM
 
 MAX_HEADS = L.EVAL_MAX_HEADS
 MAX_CLASSES = 8192  # SCA_CTC_MAX_C
@@ -64,6 +69,7 @@ def _nbest_decode(xs, grouped, input_lengths, beam_size, nbest, collapse_repeats
     lm, lw, lb = None, 0.0, 0.0
     if fusion is not None:
         lm = fusion[0]
+        _dense_only(lm, what)
         lw, lb = _check_fusion(*fusion, C, what)
     check_on_device(None, xs[0])
     table = _fusion_table(lm, xs[0].device, what)
@@ -124,10 +130,18 @@ def _host_lists(nb):
 
 
 # ----------------------------------------------------------------------- shallow fusion
+def _dense_only(lm, what):
+    """The fused search scans a dense row per beam: it takes no `NGramLM`."""
+    if isinstance(lm, NGramLM):
+        raise ValueError(f"{what}: the fused search takes a BigramLM (a dense table), not an NGramLM; an order-1 "
+                         "or order-2 model has one: lm.to_bigram()")
+
+
 def _check_fusion(lm, lm_weight, length_bonus, num_classes, what):
-    """Host-side validation; (lm_weight, length_bonus) as floats."""
-    if lm is not None and not isinstance(lm, BigramLM):
-        raise ValueError(f"{what}: lm must be a BigramLM or None, got {type(lm).__name__}")
+    """Host-side validation of a gloss model (a `BigramLM`, an `NGramLM` or None) and its weights;
+    (lm_weight, length_bonus) as floats."""
+    if lm is not None and not isinstance(lm, (BigramLM, NGramLM)):
+        raise ValueError(f"{what}: lm must be a BigramLM, an NGramLM or None, got {type(lm).__name__}")
     lw, lb = _finite("lm_weight", lm_weight, what), _finite("length_bonus", length_bonus, what)
     if lm is not None and lm.num_classes != num_classes:
         raise ValueError(f"{what}: the gloss model has {lm.num_classes} classes, the logits {num_classes}")
@@ -135,11 +149,13 @@ def _check_fusion(lm, lm_weight, length_bonus, num_classes, what):
 
 
 def _fusion_table(lm, device, what):
+    """What the ops take for a validated gloss model on the logits' device: a `BigramLM`'s table,
+    an `NGramLM` itself (its struct holds the pointers), or None."""
     if lm is None:
         return None
-    if lm.table.device != device:
-        raise RuntimeError(f"{what}: the gloss model is on {lm.table.device}, the logits on {device}; use lm.to(device)")
-    return lm.table
+    if lm.device != device:
+        raise RuntimeError(f"{what}: the gloss model is on {lm.device}, the logits on {device}; use lm.to(device)")
+    return lm if isinstance(lm, NGramLM) else lm.table
 
 
 def ctc_decode_fused_nbest_device(gloss_logits, input_lengths, beam_size, lm, lm_weight=0.0, length_bonus=0.0,
@@ -193,6 +209,10 @@ class BigramLM:
     @property
     def num_classes(self):
         return self.table.shape[0]
+
+    @property
+    def device(self):
+        return self.table.device
 
     def to(self, device):
         return BigramLM(self.table, device)
@@ -266,21 +286,29 @@ def rescore_nbest_device(nb, lm=None, lm_weight=0.0, length_bonus=0.0, posterior
     """`sca_nbest_rescore` over an `NBest`: total = score + lm_weight * lm(h) + length_bonus *
     len(h), posterior = softmax over the valid entries of posterior_scale * total, order = the
     valid entries by total descending (ties to the lower entry), invalid entries after them.
-    `lm`: a `BigramLM` on the device, or None (lm(h) = 0: the call only produces the posterior).
+    `lm`: a `BigramLM` or an `NGramLM` (`sca_nbest_rescore_ngram`: the backoff rule over the trie)
+    on the device, or None (lm(h) = 0: the call only produces the posterior).
     Returns (total, posterior, order) shaped like `nb.scores`, fp32 / fp32 / int32."""
     what = "rescore_nbest"
     G, B, N, T = _check_nbest(nb, what)
-    if lm is not None and not isinstance(lm, BigramLM):
-        raise ValueError(f"{what}: lm must be a BigramLM or None, got {type(lm).__name__}")
+    if lm is not None and not isinstance(lm, (BigramLM, NGramLM)):
+        raise ValueError(f"{what}: lm must be a BigramLM, an NGramLM or None, got {type(lm).__name__}")
     lw, lb, ps = (_finite(n, v, what) for n, v in (("lm_weight", lm_weight), ("length_bonus", length_bonus),
                                                    ("posterior_scale", posterior_scale)))
     check_on_device(what, *nb)
     if lm is not None:
-        check_on_device(what, lm.table)
+        check_on_device(what, lm.uni_lp if isinstance(lm, NGramLM) else lm.table)
+    if isinstance(lm, NGramLM):
+        _fusion_table(lm, nb.tokens.device, what)
     tokens, lengths, count = _i32(nb.tokens), _i32(nb.lengths), _i32(nb.count)
     scores = _f32(nb.scores)
     total, posterior = torch.empty_like(scores), torch.empty_like(scores)
     order = torch.empty_like(lengths)
+    if isinstance(lm, NGramLM):
+        L.check(L.lib().sca_nbest_rescore_ngram(L.ptr(tokens), L.ptr(lengths), L.ptr(scores), L.ptr(count), G, B, N, T,
+                                                ctypes.byref(lm.struct), lw, lb, ps, L.ptr(total), L.ptr(posterior),
+                                                L.ptr(order), L.stream_handle()), "sca_nbest_rescore_ngram")
+        return total, posterior, order
     L.check(L.lib().sca_nbest_rescore(L.ptr(tokens), L.ptr(lengths), L.ptr(scores), L.ptr(count), G, B, N, T,
                                       None if lm is None else L.ptr(lm.table), 0 if lm is None else lm.num_classes,
                                       lw, lb, ps, L.ptr(total), L.ptr(posterior), L.ptr(order), L.stream_handle()),
@@ -333,20 +361,22 @@ def select_device(nb, values, index):
 class Rescoring:
     """What the evaluation and recognition steps run in place of the 1-best decode: the `nbest`
     best labellings of the beam search (1 <= nbest <= 32, and at most the step's beam_size),
-    rescored with `lm` (a `BigramLM` or None), `lm_weight`, `length_bonus` and `posterior_scale`
+    rescored with `lm` (a `BigramLM`, an `NGramLM` or None; the spec holds it, so a captured
+    graph's pointers stay alive), `lm_weight`, `length_bonus` and `posterior_scale`
     as `rescore_nbest_device` takes them, and the hypothesis picked by `select`: "score", the
     best total, or "mbr", the minimum expected error count under the posterior.  `fusion=True`:
     the list comes from the fused search (`ctc_decode_fused_nbest_heads_device` with this spec's
     `lm`, `lm_weight` and `length_bonus`), so the search keeps what the rescorer would have
-    preferred; everything after the decode is unchanged.  ValueError for anything else, and for
-    `fusion=True` with neither a table nor a length bonus (nothing to fuse)."""
+    preferred; everything after the decode is unchanged.  ValueError for anything else, for
+    `fusion=True` with neither a table nor a length bonus (nothing to fuse), and for `fusion=True`
+    with an `NGramLM` (the fused search takes a `BigramLM`: `lm.to_bigram()`)."""
 
     def __init__(self, nbest, lm=None, lm_weight=0.0, length_bonus=0.0, posterior_scale=1.0, select="score",
                  fusion=False):
         if isinstance(nbest, bool) or not isinstance(nbest, int) or not 1 <= nbest <= MAX_BEAM:
             raise ValueError(f"Rescoring: nbest must be an int in [1, {MAX_BEAM}], got {nbest!r}")
-        if lm is not None and not isinstance(lm, BigramLM):
-            raise ValueError(f"Rescoring: lm must be a BigramLM or None, got {type(lm).__name__}")
+        if lm is not None and not isinstance(lm, (BigramLM, NGramLM)):
+            raise ValueError(f"Rescoring: lm must be a BigramLM, an NGramLM or None, got {type(lm).__name__}")
         if select not in SELECT:
             raise ValueError(f"Rescoring: select must be one of {SELECT}, got {select!r}")
         self.nbest, self.lm, self.select = nbest, lm, select
@@ -358,6 +388,8 @@ class Rescoring:
             raise ValueError("Rescoring: lm_weight, length_bonus and posterior_scale must be numbers") from None
         if not isinstance(fusion, bool):
             raise ValueError(f"Rescoring: fusion must be a bool, got {fusion!r}")
+        if fusion:
+            _dense_only(lm, "Rescoring")
         if fusion and lm is None and self.length_bonus == 0.0:
             raise ValueError("Rescoring: fusion=True needs a gloss model or a length bonus: there is nothing to fuse")
         self.fusion = fusion

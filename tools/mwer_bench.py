@@ -21,13 +21,16 @@ Needs a GPU.
 
 --reference, --lm, --heads G time the extended loss (the reference as a list entry, the bigram table
 inside the posterior, G tensors in one grouped call) beside its yardsticks instead: see `extended`.
+--ngram ORDER (with --lm implied) adds `mwer_ngram`, the loss with an `NGramLM` of that order
+(`sca_mwer_heads_fwd_ngram`; tools/nbest_bench.ngram_model on the same lists) beside `mwer_lm`, and
+the forwards alone (`*_fwd`, under no_grad), which is where the prior runs.
 --ensemble G times the loss on the differentiable ensemble of G member tensors beside the loss on the
 torch composition of the same members (autograd through log_softmax / stack / logsumexp): see `on_ensemble`.
 --dump PATH saves the plain loss's outputs and gradient, for a bit-for-bit comparison of two builds
 (SCA_LIB_PATH selects the library).
 
 Usage: python tools/mwer_bench.py [--B 8] [--T 64] [--C 1124] [--beam 5] [--nbest 5] [--steps 200]
-                                  [--reference] [--lm] [--heads G] [--ensemble G] [--dump PATH]
+                                  [--reference] [--lm] [--ngram ORDER] [--heads G] [--ensemble G] [--dump PATH]
 """
 import argparse
 import json
@@ -65,6 +68,8 @@ def extended(a, S, dev):
     * `mwer_reference`   reference=True at N entries              (--reference)
     * `mwer_n_plus_1`    the plain loss over a list of N + 1 entries: the slot's yardstick
     * `mwer_lm`          the table on, everything else as the widest variant above   (--lm)
+    * `mwer_ngram`       the same with the backoff n-gram model in place of the table  (--ngram ORDER)
+    * `mwer_fwd`, `mwer_lm_fwd`, `mwer_ngram_fwd`  the forwards alone, under no_grad     (--ngram ORDER)
     * `mwer_heads`       one grouped call over G tensors                             (--heads G)
     * `mwer_calls`       G single calls on the same tensors"""
     g = torch.Generator().manual_seed(0)
@@ -102,6 +107,21 @@ def extended(a, S, dev):
         fns["mwer_n_plus_1"] = single(nb6)
     if a.lm:
         fns["mwer_lm"] = single(nbs[0], **kw)
+    sizes = None
+    if a.ngram:
+        from tools.nbest_bench import ngram_model, ngram_outcomes
+        ng, sizes = ngram_model(S, a.ngram, a.C, nbs[0], dev)
+        sizes["outcomes"] = ngram_outcomes(ng, nbs[0])
+        fns["mwer_ngram"] = single(nbs[0], **dict(kw, lm=ng))
+
+        def forward(**kw):
+            def fn():
+                with torch.no_grad():
+                    S.mwer_loss(xs[0], il, ref, ref_len, nbest=nbs[0], **kw)
+            return fn
+
+        fns["mwer_fwd"], fns["mwer_lm_fwd"] = forward(reference=a.reference), forward(**kw)
+        fns["mwer_ngram_fwd"] = forward(**dict(kw, lm=ng))
     if G > 1:
         zg, zc = leaves(), leaves()
 
@@ -132,6 +152,9 @@ def extended(a, S, dev):
     res = {"workload": "extended MWER loss forward + backward beside its yardsticks, graph replays", "B": a.B, "T": a.T,
            "C": a.C, "beam": a.beam, "nbest": N, "heads": G, "reference": a.reference, "lm": a.lm, "R": R,
            "steps": a.steps, "repeats": a.repeats, "unit": "us per call", "statistics": stats, "graph": timed}
+    if sizes:
+        res["ngram"] = sizes
+        res["ngram_fwd_minus_lm_fwd"] = round(timed["mwer_ngram_fwd"]["median"] - timed["mwer_lm_fwd"]["median"], 2)
     if G > 1:
         res["heads_over_calls"] = round(timed["mwer_heads"]["median"] / timed["mwer_calls"]["median"], 3)
     print(json.dumps(res))
@@ -212,6 +235,8 @@ def main():
                     "members beside the loss on their torch composition (with --reference: the slot on)")
     ap.add_argument("--reference", action="store_true", help="time reference=True beside N and N + 1 entries")
     ap.add_argument("--lm", action="store_true", help="time the bigram table inside the posterior")
+    ap.add_argument("--ngram", type=int, default=0, help="time an NGramLM of this order inside the posterior beside "
+                    "the bigram table (implies --lm)")
     ap.add_argument("--heads", type=int, default=1, help="time one grouped call over G tensors beside G calls")
     ap.add_argument("--dump", default=None, help="save the plain loss's outputs and dlogits here (torch.save), to "
                     "compare two builds bit for bit")
@@ -231,6 +256,7 @@ def main():
     dev = torch.device("cuda")
     if a.ensemble:
         return on_ensemble(a, S, dev)
+    a.lm = a.lm or a.ngram > 0
     if a.reference or a.lm or a.heads > 1:
         return extended(a, S, dev)
     g = torch.Generator().manual_seed(0)
